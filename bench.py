@@ -3,7 +3,7 @@
 next to the kernel's roofline and the CPU path timed on the same box.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload default|m1|m2a|m2b|m3a|m3b|m4]
-                    [--scaling strong|weak] [--repeats R] [--no-cpu-baseline]
+                    [--scaling strong|weak] [--repeats R] [--no-cpu-baseline] [--dump-outputs DIR]
 
 Default (what the driver runs): the two shapes the metric is quoted on, in ONE JSON line
   * main block  = M2A, the reference's benches/bench_matrix_mul_gpu.rs:20-34 shape: n=2^14, L=15 (24-bit),
@@ -14,6 +14,8 @@ Default (what the driver runs): the two shapes the metric is quoted on, in ONE J
   * "kernels"   = the NTT / INTT / pointwise mod-mul kernels of BASELINE configs[1] (M1: n=2^14, L=4,
     1024 polynomials) with their achieved HBM GB/s from hipEvents.
 Always synchronises before stopping the clock (the reference's mat-mul bench does not).
+--dump-outputs DIR: what the headline workload's last timed step returned (M2A's product by default), as DIR/<name>.npy
+for output-for-output comparison of two builds (`dump_outputs`; deterministic workloads only).
 
 Timing: W untimed warm-up steps, then EXACTLY K steps between barrier + device-synchronise brackets, MAX over
 ranks (`value`, `ms_per_step`); after that R further repetitions of the K steps give `repeats` (median / min)
@@ -69,7 +71,20 @@ def parse_args(argv=None):
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo rehearses the launcher / rendezvous on a GPU-less box (with --dry-run) and the whole sharded path with more ranks than GPUs (ranks share devices; not a measurement)")
     ap.add_argument("--dry-run", action="store_true", help="launch + rendezvous + one all-reduce, no GPU work")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the headline workload's last timed step returned as DIR/<name>.npy "
+                         "(residues in float32 / float64, at most 64 MB in all: a fixed, seeded sample of entries when larger)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None:
+        if args.inproc or args.dry_run:
+            ap.error("--dump-outputs needs a run of the workload in this process tree (no --inproc, no --dry-run)")
+        wl = "m2a" if args.workload == "default" else args.workload
+        if not hasattr(WORKLOADS[wl], "outputs"):
+            ap.error(f"--dump-outputs: workload {wl} draws fresh randomness per call, its outputs cannot be compared run to run; "
+                     f"use one of {sorted(k for k, c in WORKLOADS.items() if hasattr(c, 'outputs'))}")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -328,6 +343,9 @@ class M1(Workload):
         if mark:
             self.mark(i, 2)
 
+    def outputs(self):
+        return {"x": self.x}
+
     def standalone_kernels(self, reps=10):
         """the unfused kernels of the same chain, each between its own hipEvent marks: point-wise mod-mul and the
         plain inverse transform (BASELINE.json asks for the NTT and mod-mul kernels' GB/s)"""
@@ -451,6 +469,9 @@ class MatMul(Workload):
     def local_block(self):
         return self.out if self.c_local else self.out.slice_columns(0, 0)
 
+    def outputs(self):
+        return {"product": self.full if self.full is not None else self.out}
+
     def drain(self):
         if self.gather is not None and self.lazy_gather:
             if self._ungathered:  # the region's one exchange step
@@ -523,6 +544,9 @@ class M2BDecompose(Workload):
         if mark:
             self.mark(i, 1)
 
+    def outputs(self):
+        return {"digits": self.out}
+
     def check(self):
         g = self.mx.GpuDCRTPolyMatrix.gadget_matrix(self.params, 64)
         assert g * self.out == self.m, "G * G^-1(M) != M"
@@ -557,6 +581,9 @@ class M2BMulDecompose(Workload):
         self.out = self.s.mul_decompose(self.b)
         if mark:
             self.mark(i, 1)
+
+    def outputs(self):
+        return {"product": self.out}
 
     def check(self):
         assert self.out == self.s * self.b.decompose(), "S * G^-1(B) differs from the two-step form"
@@ -782,8 +809,9 @@ WORKLOADS = {"m1": M1, "m2a": M2A, "m2b": M2B, "m2b_decompose": M2BDecompose, "m
 # ---------------------------------------------------------------------------------------------------
 # measurement
 # ---------------------------------------------------------------------------------------------------
-def run_block(wl: Workload, d: Dist, steps: int, warmup: int, repeats: int, sustain_s: float = 0.0):
-    """The contract's timed region (K steps, barrier + synchronise on both sides, MAX over ranks), then
+def run_block(wl: Workload, d: Dist, steps: int, warmup: int, repeats: int, sustain_s: float = 0.0, capture=None):
+    """The contract's timed region (K steps, barrier + synchronise on both sides, MAX over ranks), `capture(wl)` (if given)
+    on the result of its last step, then
     `repeats` more repetitions of the same K steps for median / min, then - `sustain_s` > 0, the headline workload - ONE
     contiguous region of about that many seconds of the same steps (K steps of a sub-millisecond product last 12 ms, too
     short for an outside utilisation sampler to ever see the device busy; VERDICT r4 weak #2)."""
@@ -807,6 +835,8 @@ def run_block(wl: Workload, d: Dist, steps: int, warmup: int, repeats: int, sust
     d.barrier_sync(mx.gpu_device_sync)
     elapsed = d.max_over_ranks(time.perf_counter() - t0)
     wl.ctx.marker(2)
+    if capture is not None:  # outside the clock, before any later step writes the buffers again
+        capture(wl)
     kernel_ms = wl.kernel_ms(steps)
     reps = []
     for _ in range(repeats):
@@ -871,6 +901,44 @@ def run_block(wl: Workload, d: Dist, steps: int, warmup: int, repeats: int, sust
                     "min_ms_per_step": min(all_ms), "max_ms_per_step": max(all_ms),
                     "value_at_median": wl.units / (statistics.median(all_ms) * 1e-3)},
     }
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6  # every file of one --dump-outputs run together, npy headers included
+DUMP_SEED = 0
+
+
+def dump_outputs(wl: Workload, out_dir: str) -> dict:
+    """--dump-outputs: the matrices `wl.outputs()` names (what its last step returned to the caller) as out_dir/<name>.npy.
+    Residues in the matrix's current form (EVAL or COEFF), shape (rows, cols, limbs, n), float32 when every modulus is below
+    2^24 and float64 otherwise - exact either way.  A matrix over its share of DUMP_LIMIT_BYTES is stored as a fixed sample:
+    the whole entries at DUMP_SEED-drawn row-major positions (ascending), shape (entries, limbs, n); the returned record
+    lists the positions.  The workloads' inputs come from fixed seeds, so two runs with the same arguments (two builds of
+    the library) compare file for file."""
+    import numpy as np
+
+    top = max(wl.params.moduli())
+    assert top < 1 << 53, "residues beyond float64's exact integers"
+    dtype = np.dtype(np.float32 if top < 1 << 24 else np.float64)
+    outs = wl.outputs()
+    share = (DUMP_LIMIT_BYTES - 4096 * len(outs)) // len(outs)
+    os.makedirs(out_dir, exist_ok=True)
+    record = {"dir": out_dir, "dtype": dtype.name, "files": {}}
+    for name, m in outs.items():
+        entry_bytes = (m.level + 1) * wl.params.ring_dimension() * dtype.itemsize
+        info = {"format": "eval" if m.is_ntt else "coeff", "rows": m.nrow, "cols": m.ncol, "limbs": m.level + 1}
+        if m.nrow * m.ncol * entry_bytes <= share:
+            arr = m.to_rns().astype(dtype)
+        else:
+            count = share // entry_bytes
+            assert count > 0, f"one entry of {name} exceeds the dump limit"
+            pos = np.sort(np.random.default_rng(DUMP_SEED).choice(m.nrow * m.ncol, size=count, replace=False))
+            arr = np.stack([m.slice(p // m.ncol, p // m.ncol + 1, p % m.ncol, p % m.ncol + 1).to_rns()[0, 0].astype(dtype)
+                            for p in pos.tolist()])
+            info["sampled_entries"] = pos.tolist()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        info["shape"] = list(arr.shape)
+        record["files"][name + ".npy"] = info
+    return record
 
 
 def roofline_of(wl: Workload, kernel_ms):
@@ -1627,10 +1695,15 @@ def main():
         device = d.local_rank % mx.detected_gpu_device_count()
     steps, warmup = args.steps, args.warmup
 
-    def run(name, steps_, warmup_, repeats_, sustain_s=0.0):
+    dumped = {}
+    capture = None
+    if args.dump_outputs is not None and d.rank == 0:
+        capture = lambda w: dumped.update(dump_outputs(w, args.dump_outputs))  # noqa: E731
+
+    def run(name, steps_, warmup_, repeats_, sustain_s=0.0, capture=None):
         wl = WORKLOADS[name](mx, d, args, device)
         wl.setup()
-        res = run_block(wl, d, steps_, warmup_, repeats_, sustain_s)
+        res = run_block(wl, d, steps_, warmup_, repeats_, sustain_s, capture)
         return wl, res
 
     def independent_units(name):
@@ -1662,7 +1735,7 @@ def main():
         return w, r, blk
 
     if args.workload == "default":
-        wl, res = run("m2a", steps, warmup, args.repeats, args.sustain)
+        wl, res = run("m2a", steps, warmup, args.repeats, args.sustain, capture)
         line = block_json(wl, res, d, args, steps, warmup)
         line["output_buffers"] = ("the product writes into pre-allocated output matrices; the reference's timed `&left * &right` "
                                   "also creates its output (src/matrix/gpu_dcrt_poly.rs:1792-1815) - microseconds from the stream-ordered cache")
@@ -1744,7 +1817,7 @@ def main():
             line["preimage"]["cpu_baseline"] = cpu_baseline("m3a", args.cpu_seconds)
             line["kernels"]["cpu_baseline"] = cpu_baseline("m1", args.cpu_seconds / 2)
     else:
-        wl, res = run(args.workload, steps, warmup, args.repeats, args.sustain if args.workload == "m2a" else 0.0)
+        wl, res = run(args.workload, steps, warmup, args.repeats, args.sustain if args.workload == "m2a" else 0.0, capture)
         line = block_json(wl, res, d, args, steps, warmup)
         if args.workload == "m1":
             line["kernels"] = kernels_block(wl, res)
@@ -1758,6 +1831,8 @@ def main():
             line["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_seconds)
     if d.rank == 0:
         line.setdefault("cpu_baseline", None)
+        if dumped:
+            line["dump_outputs"] = dumped
         emit(line)
     d.finish()
 

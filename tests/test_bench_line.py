@@ -171,3 +171,85 @@ def test_committed_counter_records_match_the_library_or_are_flagged():
     mix = bench.load_valu_mix(cur)
     for base, k in mix.items():
         assert k["isa_hash"] == cur[base] and 2.5 <= k["cycles_per_inst"] <= 4.5
+
+
+# ---------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------
+class _HostMatrix:
+    """host stand-in for GpuDCRTPolyMatrix with the members bench.dump_outputs reads"""
+
+    def __init__(self, data, is_ntt=True):
+        self.data, self.is_ntt = data, is_ntt
+        self.nrow, self.ncol = data.shape[:2]
+        self.level = data.shape[2] - 1
+
+    def to_rns(self):
+        return self.data.copy()
+
+    def slice(self, r0, r1, c0, c1):
+        return _HostMatrix(self.data[r0:r1, c0:c1], self.is_ntt)
+
+
+class _HostParams:
+    def __init__(self, moduli, n):
+        self._moduli, self._n = moduli, n
+
+    def moduli(self):
+        return list(self._moduli)
+
+    def ring_dimension(self):
+        return self._n
+
+
+class _HostWorkload:
+    def __init__(self, moduli, shape, seed=1):
+        import numpy as np
+
+        rows, cols, n = shape
+        self.params = _HostParams(moduli, n)
+        rng = np.random.default_rng(seed)
+        self.data = np.stack([rng.integers(0, q, size=(rows, cols, n), dtype=np.uint64) for q in moduli], axis=2)
+
+    def outputs(self):
+        return {"product": _HostMatrix(self.data)}
+
+
+def test_dump_outputs_writes_the_whole_matrix_exactly_when_it_fits(tmp_path):
+    import numpy as np
+
+    wl = _HostWorkload([(1 << 24) - 3, (1 << 23) + 9], (2, 3, 16))
+    rec = bench.dump_outputs(wl, str(tmp_path / "out"))
+    got = np.load(tmp_path / "out" / "product.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 3, 2, 16)
+    assert np.array_equal(got.astype(np.uint64), wl.data)  # 24-bit residues are exact in float32
+    assert rec["dtype"] == "float32" and rec["files"]["product.npy"]["shape"] == [2, 3, 2, 16]
+    assert "sampled_entries" not in rec["files"]["product.npy"]
+
+
+def test_dump_outputs_samples_fixed_entries_under_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 10 * 3 * 64 * 8)  # room for 10 of the 48 entries
+    wl = _HostWorkload([(1 << 50) - 27, (1 << 40) + 15, (1 << 30) + 3], (4, 12, 64))
+    rec = bench.dump_outputs(wl, str(tmp_path / "a"))
+    got = np.load(tmp_path / "a" / "product.npy")
+    assert got.dtype == np.float64 and got.shape == (10, 3, 64)
+    assert os.path.getsize(tmp_path / "a" / "product.npy") <= bench.DUMP_LIMIT_BYTES
+    pos = rec["files"]["product.npy"]["sampled_entries"]
+    assert len(pos) == 10 and pos == sorted(set(pos))
+    for k, p in enumerate(pos):
+        assert np.array_equal(got[k].astype(np.uint64), wl.data[p // 12, p % 12])
+    # another run (another build) with the same shapes samples the same entries
+    rec2 = bench.dump_outputs(_HostWorkload(wl.params.moduli(), (4, 12, 64), seed=2), str(tmp_path / "b"))
+    assert rec2["files"]["product.npy"]["sampled_entries"] == pos
+
+
+def test_steps_and_dump_outputs_arguments_are_checked(capsys):
+    args = bench.parse_args(["--steps", "7", "--warmup", "0", "--dump-outputs", "d"])
+    assert args.steps == 7 and args.dump_outputs == "d"
+    assert bench.parse_args(["--workload", "m2b_decompose", "--dump-outputs", "d"]).workload == "m2b_decompose"
+    for bad in (["--steps", "0"], ["--workload", "m3a", "--dump-outputs", "d"], ["--inproc", "--dump-outputs", "d"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    capsys.readouterr()
