@@ -287,6 +287,27 @@ int gpupoly_matrix_gauss_samp_gq_arb_base_segments(GpuMatrix *src, uint32_t base
  * side's format tag.                                                                                              */
 int gpupoly_matrix_concat_columns(GpuMatrix *out, const GpuMatrix *const *blocks, size_t n);
 int gpupoly_matrix_split_columns(const GpuMatrix *src, GpuMatrix *const *blocks, size_t n);
+/* Several preimage requests against ONE trapdoor in one call: x_j with A x_j = targets[j] for j < n - for every request
+ * the SAME matrix, bit for bit, that the one-request preimage (src/sampler/trapdoor/gpu.rs:228-369) produces for
+ * targets[j] alone under the seeds seeds[3j] (p2), seeds[3j+1] (p1), seeds[3j+2] (z).  Replaces the per-request loop
+ * of preimage_batched_sharded (gpu.rs:371-397) for one key group.
+ *   re            [R; E] of the trapdoor, 2d x dk, EVAL (dk = d * digits per tower * limbs)
+ *   cache         the trapdoor's p1 covariance cache; it carries the widths c = cache sigma, s and dgg_stddev, and
+ *                 the large width is sqrt(s*s - c*c)
+ *   public_matrix A = [left | right], d x (2d + dk), EVAL
+ *   targets[j]    d x cols_j, EVAL;  outs[j]: (2d + dk) x cols_j, made by the caller, tagged EVAL on success
+ * The requests go out in groups of up to 64 (p2 capped at 1 GiB per group), each group one sequence of launches:
+ * p1 and p2 sampled into one stacked matrix P = [p1; p2] (padded per request to a multiple of d columns), A P as one
+ * product, u - A P by one gather over the targets, the G-sampler, [R;E] z, and one scatter of
+ * [P_top + [R;E] z ; P_bottom + z] into the outputs.  Temporaries come from the context's allocator and are released
+ * stream-ordered; the host does not block.  Zero-column requests give zero-column outputs; n = 0 does nothing.
+ * A refused call launches nothing and writes no output, not even a format tag: context or level mismatch, wrong
+ * shapes, a target not in EVAL form, an output that aliases an input or another output.  Shapes the segmented
+ * samplers do not cover (n not a multiple of 128, d > 2, more than four digits per tower, MXX_HIP_RNG_COMPAT=reference,
+ * MXX_HIP_P1=simple) are refused with an error whose text contains "unsupported": issue those requests one by one. */
+int gpupoly_trapdoor_preimage_many(const GpuMatrix *re, const GpuP1CovarianceCache *cache, const GpuMatrix *public_matrix,
+                                   uint32_t base_bits, const GpuMatrix *const *targets, size_t n, const GpuRngSeed *seeds,
+                                   GpuMatrix *const *outs);
 /* kernel launches issued by the library since it was loaded (every context; copies / memsets not counted): bench.py
  * reports launches per step for the launch-bound small-ring chain                                              */
 uint64_t gpupoly_launch_count(void);

@@ -1,0 +1,339 @@
+// preimage.hip — several preimage requests against ONE trapdoor in one ABI call (gpupoly_trapdoor_preimage_many).
+//
+// The body of `preimage` (src/sampler/trapdoor/gpu.rs:228-369, :423-474) over the column-wise concatenation of up to 64
+// requests per group, each with its own seed triple (the gpupoly_*_segments samplers key every element by its position
+// inside its own request, so a request's output is the matrix it would get alone).  Per group:
+//   P = [p1; p2]       one stacked matrix, every request padded to a multiple of d columns; p2 is sampled into P's
+//                      bottom rows, p1 (from [R;E] p2) into its top rows - row views, no copies
+//   A P                one product: the residues of left p1 + right p2, without slicing A
+//   u - A P            gather-subtract: reads every target through a pointer table, skips the padding columns
+//   z                  the G-sampler over the perturbed syndromes, [R;E] z one product
+//   outs[j]            scatter-assemble: [P_top + [R;E] z ; P_bottom + z], written straight into each caller's output
+// The mirror's sequence (mxx_amd/trapdoor.py, `_preimage_segments`) adds a concatenation of the targets, two
+// drop-padding passes, two products for the image, a sum, a difference, two row-block sums and a split.
+#include "common.h"
+#include "modarith.h"
+#include "rng.h"
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+namespace {
+
+constexpr size_t kGroupMax = RNG_MAX_SEGMENTS;  // requests per group: one segment table per sampler launch
+constexpr size_t kGroupBytes = size_t(1) << 30;  // cap on a group's p2 block (trapdoor.py: BATCH_BYTES)
+
+// the requests of one group as a kernel argument: request j owns columns [start[j], start[j + 1]) of the group's
+// target-shaped matrices and columns [pad_start[j], pad_start[j] + start[j + 1] - start[j]) of the padded ones
+struct RequestTable {
+    uint32_t count;
+    uint32_t start[kGroupMax + 1];
+    uint32_t pad_start[kGroupMax];
+    void *ptr[kGroupMax];  // request j's target (gather) or output (scatter): rows x (start[j + 1] - start[j])
+};
+
+__device__ __forceinline__ uint32_t request_of(const RequestTable &t, uint32_t col) {
+    uint32_t lo = 0, hi = t.count;  // start[lo] <= col < start[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (col >= t.start[mid]) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <typename W, int VN>
+struct Words {
+    typedef typename std::conditional<VN == 1, W, typename std::conditional<sizeof(W) == 4, uint4, ulonglong2>::type>::type V;
+    static_assert(sizeof(V) == sizeof(W) * VN, "vector width");
+};
+
+// out[r, c] = target_j[r, c - start[j]] - ap[r, pad_start[j] + c - start[j]]  (out: rows x start[count], ap: rows x ap_cols).
+// blockIdx.y/z = the output polynomial, blockIdx.x strides its words VN per lane (16 bytes when VN > 1).
+template <typename W, int VN>
+__global__ void preimage_gather_sub_kernel(W *__restrict__ out, const W *__restrict__ ap, RequestTable req,
+                                           const LimbConst *__restrict__ limbs, size_t rows, size_t ap_cols, uint32_t logN,
+                                           size_t words_per_poly) {
+    typedef typename Words<W, VN>::V V;
+    const size_t cols = req.start[req.count];
+    const size_t entry = static_cast<size_t>(blockIdx.z) * gridDim.y + blockIdx.y;
+    if (entry >= rows * cols) return;
+    const size_t r = entry / cols;
+    const uint32_t c = static_cast<uint32_t>(entry - r * cols);
+    const uint32_t j = request_of(req, c);
+    const uint32_t lc = c - req.start[j];
+    const size_t tcols = req.start[j + 1] - req.start[j];
+    const W *t = static_cast<const W *>(req.ptr[j]) + (r * tcols + lc) * words_per_poly;
+    const W *a = ap + (r * ap_cols + req.pad_start[j] + lc) * words_per_poly;
+    W *o = out + (r * cols + c) * words_per_poly;
+    for (size_t w0 = (static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x) * VN; w0 < words_per_poly;
+         w0 += static_cast<size_t>(gridDim.x) * blockDim.x * VN) {
+        const W q = static_cast<W>(limbs[w0 >> logN].q);  // VN divides N: one limb per vector
+        W tv[VN], av[VN], ov[VN];
+        *reinterpret_cast<V *>(tv) = *reinterpret_cast<const V *>(t + w0);
+        *reinterpret_cast<V *>(av) = *reinterpret_cast<const V *>(a + w0);
+#pragma unroll
+        for (int v = 0; v < VN; ++v) ov[v] = sub_mod<W>(tv[v], av[v], q);
+        *reinterpret_cast<V *>(o + w0) = *reinterpret_cast<const V *>(ov);
+    }
+}
+
+// out_j[r, c - start[j]] = p[r, pad_start[j] + c - start[j]] + (r < top ? rez[r, c] : z[r - top, c])
+// (p: rows x p_cols, rez: top x start[count], z: (rows - top) x start[count]); grid as above
+template <typename W, int VN>
+__global__ void preimage_scatter_kernel(RequestTable req, const W *__restrict__ p, const W *__restrict__ rez,
+                                        const W *__restrict__ z, const LimbConst *__restrict__ limbs, size_t top, size_t rows,
+                                        size_t p_cols, uint32_t logN, size_t words_per_poly) {
+    typedef typename Words<W, VN>::V V;
+    const size_t cols = req.start[req.count];
+    const size_t entry = static_cast<size_t>(blockIdx.z) * gridDim.y + blockIdx.y;
+    if (entry >= rows * cols) return;
+    const size_t r = entry / cols;
+    const uint32_t c = static_cast<uint32_t>(entry - r * cols);
+    const uint32_t j = request_of(req, c);
+    const uint32_t lc = c - req.start[j];
+    const size_t ocols = req.start[j + 1] - req.start[j];
+    const W *pp = p + (r * p_cols + req.pad_start[j] + lc) * words_per_poly;
+    const W *s = r < top ? rez + (r * cols + c) * words_per_poly : z + ((r - top) * cols + c) * words_per_poly;
+    W *o = static_cast<W *>(req.ptr[j]) + (r * ocols + lc) * words_per_poly;
+    for (size_t w0 = (static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x) * VN; w0 < words_per_poly;
+         w0 += static_cast<size_t>(gridDim.x) * blockDim.x * VN) {
+        const W q = static_cast<W>(limbs[w0 >> logN].q);
+        W pv[VN], sv[VN], ov[VN];
+        *reinterpret_cast<V *>(pv) = *reinterpret_cast<const V *>(pp + w0);
+        *reinterpret_cast<V *>(sv) = *reinterpret_cast<const V *>(s + w0);
+#pragma unroll
+        for (int v = 0; v < VN; ++v) ov[v] = add_mod<W>(pv[v], sv[v], q);
+        *reinterpret_cast<V *>(o + w0) = *reinterpret_cast<const V *>(ov);
+    }
+}
+
+// grid over `entries` polynomials of `words_per_poly` words, VN words per lane (column_blocks' shape, matrix.hip)
+static bool poly_grid(size_t entries, size_t words_per_poly, int vn, dim3 &grid) {
+    const size_t vecs = words_per_poly / vn;
+    const size_t gy = std::min<size_t>(entries, 65535), gz = (entries + gy - 1) / gy;
+    if (gz > 65535) return false;
+    grid = dim3(static_cast<unsigned>(std::min<size_t>((vecs + 255) / 256, 64)), static_cast<unsigned>(gy), static_cast<unsigned>(gz));
+    return true;
+}
+
+template <typename W>
+static int launch_gather_sub(GpuContext *ctx, GpuMatrix *out, const GpuMatrix *ap, const RequestTable &req) {
+    const size_t wpp = matrix_limbs(out) * static_cast<size_t>(ctx->N), entries = out->rows * out->cols;
+    // 16 bytes per lane where a limb vector holds whole 16-byte words (every ring the segmented samplers take);
+    // a word per lane below that
+    const int vn = (static_cast<size_t>(ctx->N) * sizeof(W)) % 16 == 0 ? static_cast<int>(16 / sizeof(W)) : 1;
+    dim3 grid;
+    if (!poly_grid(entries, wpp, vn, grid)) return set_error("gpupoly_trapdoor_preimage_many: matrix too large");
+    MXX_TRACE_BYTES(3.0 * entries * wpp * sizeof(W));
+    if (vn == 1)
+        MXX_LAUNCH((preimage_gather_sub_kernel<W, 1>), grid, dim3(256), 0, ctx->stream, static_cast<W *>(out->data),
+                   static_cast<const W *>(ap->data), req, ctx->d_limbs, out->rows, ap->cols, ctx->logN, wpp);
+    else
+        MXX_LAUNCH((preimage_gather_sub_kernel<W, 16 / sizeof(W)>), grid, dim3(256), 0, ctx->stream, static_cast<W *>(out->data),
+                   static_cast<const W *>(ap->data), req, ctx->d_limbs, out->rows, ap->cols, ctx->logN, wpp);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename W>
+static int launch_scatter(GpuContext *ctx, const RequestTable &req, const GpuMatrix *p, const GpuMatrix *rez, const GpuMatrix *z) {
+    const size_t wpp = matrix_limbs(p) * static_cast<size_t>(ctx->N), entries = p->rows * req.start[req.count];
+    const int vn = (static_cast<size_t>(ctx->N) * sizeof(W)) % 16 == 0 ? static_cast<int>(16 / sizeof(W)) : 1;
+    dim3 grid;
+    if (!poly_grid(entries, wpp, vn, grid)) return set_error("gpupoly_trapdoor_preimage_many: matrix too large");
+    MXX_TRACE_BYTES(3.0 * entries * wpp * sizeof(W));
+    if (vn == 1)
+        MXX_LAUNCH((preimage_scatter_kernel<W, 1>), grid, dim3(256), 0, ctx->stream, req, static_cast<const W *>(p->data),
+                   static_cast<const W *>(rez->data), static_cast<const W *>(z->data), ctx->d_limbs, rez->rows, p->rows,
+                   p->cols, ctx->logN, wpp);
+    else
+        MXX_LAUNCH((preimage_scatter_kernel<W, 16 / sizeof(W)>), grid, dim3(256), 0, ctx->stream, req,
+                   static_cast<const W *>(p->data), static_cast<const W *>(rez->data), static_cast<const W *>(z->data),
+                   ctx->d_limbs, rez->rows, p->rows, p->cols, ctx->logN, wpp);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// a temporary of the context's allocator, released stream-ordered when the scope ends (error paths included)
+struct TempMatrix {
+    GpuMatrix *m = nullptr;
+    TempMatrix() = default;
+    TempMatrix(const TempMatrix &) = delete;
+    TempMatrix &operator=(const TempMatrix &) = delete;
+    ~TempMatrix() { release(); }
+    int make(GpuContext *ctx, int level, size_t rows, size_t cols) {
+        return gpu_matrix_create(ctx, level, rows, cols, GPU_POLY_FORMAT_EVAL, &m);
+    }
+    void release() {
+        gpu_matrix_destroy(m);
+        m = nullptr;
+    }
+};
+
+// rows [row, row + rows) of m as a matrix that shares its storage (gpupoly_matrix_row_view without the allocation)
+static GpuMatrix row_block(const GpuMatrix *m, size_t row, size_t rows) {
+    const size_t poly_bytes = matrix_limbs(m) * static_cast<size_t>(m->ctx->N) * m->ctx->word_bytes;
+    GpuMatrix v = *m;
+    v.rows = rows;
+    v.data = rows && m->cols ? static_cast<char *>(m->data) + row * m->cols * poly_bytes : nullptr;
+    v.bytes = rows * m->cols * poly_bytes;
+    v.borrowed = true;
+    return v;
+}
+
+static bool storage_overlaps(const GpuMatrix *a, const GpuMatrix *b) {
+    if (!a->data || !b->data || !a->bytes || !b->bytes) return false;
+    const char *a0 = static_cast<const char *>(a->data), *b0 = static_cast<const char *>(b->data);
+    return a0 < b0 + b->bytes && b0 < a0 + a->bytes;
+}
+
+static int fail(const std::string &msg) { return set_error("gpupoly_trapdoor_preimage_many: " + msg); }
+
+struct PreimageCall {
+    GpuContext *ctx;
+    const GpuMatrix *re, *a;
+    const GpuP1CovarianceCache *cache;
+    uint32_t base_bits;
+    double sigma_large;
+    size_t d, dk;
+};
+
+// one group of requests (all with columns): the sequence of launches described at the top of this file
+static int preimage_group(const PreimageCall &call, const GpuMatrix *const *targets, const GpuRngSeed *seeds,
+                          GpuMatrix *const *outs, const std::vector<size_t> &group) {
+    GpuContext *ctx = call.ctx;
+    const int level = call.re->level;
+    const size_t top = 2 * call.d, ng = group.size();
+    std::vector<size_t> cols(ng), pads(ng);
+    std::vector<GpuRngSeed> seed_p2(ng), seed_p1(ng), seed_z(ng);
+    RequestTable gather{}, scatter{};
+    gather.count = scatter.count = static_cast<uint32_t>(ng);
+    size_t at = 0, pad_at = 0;
+    for (size_t g = 0; g < ng; ++g) {
+        const size_t j = group[g];
+        cols[g] = targets[j]->cols;
+        pads[g] = (cols[g] + call.d - 1) / call.d * call.d;
+        seed_p2[g] = seeds[3 * j];
+        seed_p1[g] = seeds[3 * j + 1];
+        seed_z[g] = seeds[3 * j + 2];
+        gather.start[g] = scatter.start[g] = static_cast<uint32_t>(at);
+        gather.pad_start[g] = scatter.pad_start[g] = static_cast<uint32_t>(pad_at);
+        gather.ptr[g] = targets[j]->data;
+        scatter.ptr[g] = outs[j]->data;
+        at += cols[g];
+        pad_at += pads[g];
+    }
+    if (pad_at >> 32) return fail("a group of requests wider than 2^32 columns");
+    for (size_t g = ng; g <= kGroupMax; ++g) gather.start[g] = scatter.start[g] = static_cast<uint32_t>(at);
+    for (size_t g = ng; g < kGroupMax; ++g) {
+        gather.pad_start[g] = scatter.pad_start[g] = static_cast<uint32_t>(pad_at);
+        gather.ptr[g] = scatter.ptr[g] = nullptr;
+    }
+    // P = [p1; p2]: p2 into the bottom rows, [R;E] p2 (to the coefficient domain) feeds p1 into the top rows
+    TempMatrix p, tp2, ap, perturbed, z, rez;
+    int rc = p.make(ctx, level, top + call.dk, pad_at);
+    if (rc) return rc;
+    GpuMatrix p1 = row_block(p.m, 0, top), p2 = row_block(p.m, top, call.dk);
+    rc = gpupoly_matrix_sample_distribution_segments(&p2, GPU_MATRIX_DIST_GAUSS, call.sigma_large, seed_p2.data(), pads.data(), ng);
+    if (rc) return rc;
+    if ((rc = tp2.make(ctx, level, top, pad_at)) || (rc = gpu_matrix_mul(tp2.m, call.re, &p2)) || (rc = gpu_matrix_intt_all(tp2.m)))
+        return rc;
+    rc = gpupoly_matrix_sample_p1_full_cached_segments(call.cache, tp2.m, seed_p1.data(), pads.data(), ng, &p1);
+    if (rc) return rc;
+    tp2.release();
+    p.m->format = GPU_POLY_FORMAT_EVAL;  // both row blocks were written in EVAL form
+    // the image A P in one product, then u - A P over the targets' columns only
+    if ((rc = ap.make(ctx, level, call.d, pad_at)) || (rc = gpu_matrix_mul(ap.m, call.a, p.m))) return rc;
+    if ((rc = perturbed.make(ctx, level, call.d, at))) return rc;
+    rc = ctx->wide ? launch_gather_sub<uint64_t>(ctx, perturbed.m, ap.m, gather) : launch_gather_sub<uint32_t>(ctx, perturbed.m, ap.m, gather);
+    if (rc) return rc;
+    ap.release();
+    // z = G-sampler over the perturbed syndromes (EVAL), [R;E] z
+    if ((rc = z.make(ctx, level, call.dk, at))) return rc;
+    rc = gpupoly_matrix_gauss_samp_gq_arb_base_segments(perturbed.m, call.base_bits, call.cache->sigma, call.cache->dgg_stddev,
+                                                        seed_z.data(), cols.data(), ng, z.m);
+    if (rc) return rc;
+    perturbed.release();
+    if ((rc = rez.make(ctx, level, top, at)) || (rc = gpu_matrix_mul(rez.m, call.re, z.m))) return rc;
+    // x_j = [p1 + [R;E] z ; p2 + z], straight into the callers' outputs
+    return ctx->wide ? launch_scatter<uint64_t>(ctx, scatter, p.m, rez.m, z.m) : launch_scatter<uint32_t>(ctx, scatter, p.m, rez.m, z.m);
+}
+
+}  // namespace
+
+extern "C" int gpupoly_trapdoor_preimage_many(const GpuMatrix *re, const GpuP1CovarianceCache *cache,
+                                              const GpuMatrix *public_matrix, uint32_t base_bits,
+                                              const GpuMatrix *const *targets, size_t n, const GpuRngSeed *seeds,
+                                              GpuMatrix *const *outs) {
+    ABI_GUARD_BEGIN
+    // ---- every check before the first launch: a refused call launches nothing and writes no output, not even a tag
+    if (!re || !cache || !public_matrix) return fail("null trapdoor, covariance cache or public matrix");
+    if (n == 0) return 0;
+    if (!targets || !seeds || !outs) return fail("null targets, seeds or outputs");
+    GpuContext *ctx = re->ctx;
+    const int level = re->level;
+    if (cache->ctx != ctx || public_matrix->ctx != ctx) return fail("context mismatch");
+    if (cache->level != level || public_matrix->level != level) return fail("level mismatch");
+    if (base_bits == 0 || base_bits >= 63) return fail("invalid base_bits");
+    const size_t d = public_matrix->rows, L = matrix_limbs(re);
+    const uint32_t dpt = (ctx->crt_bits + base_bits - 1) / base_bits;
+    const size_t top = 2 * d, dk = d * dpt * L;
+    if (d == 0 || re->rows != top || re->cols != dk || public_matrix->cols != top + dk || cache->d != d || cache->m != top)
+        return fail("shape mismatch: needs [R; E] 2d x dk, A d x (2d + dk) and a covariance cache of dimension d");
+    if (re->format != GPU_POLY_FORMAT_EVAL || public_matrix->format != GPU_POLY_FORMAT_EVAL)
+        return fail("[R; E] and the public matrix must be in EVAL form");
+    for (size_t j = 0; j < n; ++j) {
+        const GpuMatrix *t = targets[j], *o = outs[j];
+        if (!t || !o) return fail("null target or output " + std::to_string(j));
+        if (t->ctx != ctx || o->ctx != ctx) return fail("context mismatch in request " + std::to_string(j));
+        if (t->level != level || o->level != level) return fail("level mismatch in request " + std::to_string(j));
+        if (t->rows != d) return fail("target " + std::to_string(j) + " must have d rows");
+        if (o->rows != top + dk || o->cols != t->cols)
+            return fail("output " + std::to_string(j) + " must be (2d + dk) x its target's columns");
+        if (t->format != GPU_POLY_FORMAT_EVAL) return fail("target " + std::to_string(j) + " must be in EVAL form");
+        if (t->cols >> 31) return fail("target " + std::to_string(j) + " too wide");
+    }
+    for (size_t j = 0; j < n; ++j) {
+        const GpuMatrix *o = outs[j];
+        bool alias = storage_overlaps(o, re) || storage_overlaps(o, public_matrix);
+        for (size_t i = 0; i < n && !alias; ++i) alias = storage_overlaps(o, targets[i]) || (i != j && storage_overlaps(o, outs[i]));
+        if (alias) return fail("output " + std::to_string(j) + " aliases an input or another output");
+    }
+    // what the segmented samplers cover (include/gpupoly.h); the caller issues such requests one by one
+    if ((static_cast<size_t>(ctx->N) >> 1) % SAMPLER_THREADS)
+        return fail("unsupported: ring dimension not a multiple of 128 (segmented samplers)");
+    if (cache->m > 4 || ctx->env.p1_simple) return fail("unsupported: trapdoor dimension above 2 or MXX_HIP_P1=simple (no p1 lane kernel)");
+    if (dpt > 4) return fail("unsupported: more than four digits per tower (G-sampler lane kernel)");
+    if (ctx->env.rng_compat) return fail("unsupported under MXX_HIP_RNG_COMPAT=reference");
+    // the widths as trapdoor.py evaluates them: c = cache->sigma, s = cache->s, large = sqrt(s^2 - c^2)
+    const double sigma_large = std::sqrt(cache->s * cache->s - cache->sigma * cache->sigma);
+    if (!(sigma_large > 0.0) || !(cache->sigma > 0.0)) return fail("invalid Gaussian widths in the covariance cache");
+    if (ctx_activate(ctx)) return 1;
+    // ---- groups of at most 64 requests with columns, p2 capped at 1 GiB (trapdoor.py: preimage_many)
+    const PreimageCall call{ctx, re, public_matrix, cache, base_bits, sigma_large, d, dk};
+    const size_t poly_bytes = L * static_cast<size_t>(ctx->N) * ctx->word_bytes;
+    std::vector<size_t> group;
+    size_t group_bytes = 0;
+    for (size_t j = 0; j < n; ++j) {
+        if (targets[j]->cols == 0) continue;  // a zero-column request: a zero-column output, nothing to launch
+        const size_t bytes = dk * ((targets[j]->cols + d - 1) / d * d) * poly_bytes;
+        if (!group.empty() && (group.size() == kGroupMax || group_bytes + bytes > kGroupBytes)) {
+            const int rc = preimage_group(call, targets, seeds, outs, group);
+            if (rc) return rc;
+            group.clear();
+            group_bytes = 0;
+        }
+        group.push_back(j);
+        group_bytes += bytes;
+    }
+    if (!group.empty()) {
+        const int rc = preimage_group(call, targets, seeds, outs, group);
+        if (rc) return rc;
+    }
+    for (size_t j = 0; j < n; ++j) outs[j]->format = GPU_POLY_FORMAT_EVAL;
+    return 0;
+    ABI_GUARD_END
+}

@@ -474,6 +474,35 @@ class GpuDCRTPolyTrapdoorSampler:
         out.add_rows_from(p1_rows, p2, z_hat)
         return out.split_columns(cols)
 
+    def preimage_many_abi(self, params, td: GpuDCRTTrapdoor, public_matrix, targets, _seeds=None) -> list:
+        """`preimage_many` through ONE library call (`gpupoly_trapdoor_preimage_many`): the grouping, the launches and the
+        assembly into every request's output happen inside the C entry - what a Rust caller of the library gets.  Same
+        matrices, bit for bit, for the same seeds (drawn here request by request, in `preimage_many`'s order).  Targets must
+        be EVAL matrices of `params`' context.  Shapes the segmented samplers do not cover (the entry's "unsupported"
+        error) go through `preimage` one by one."""
+        from . import _ffi
+
+        targets = list(targets)
+        seeds = list(_seeds) if _seeds is not None else [self._draw_seeds() for _ in targets]
+        if not targets:
+            return []
+        d = public_matrix.row_size()
+        n, k = params.ring_dimension(), params.modulus_digits()
+        s = preimage_smoothing_parameter(self.base, self.sigma, d, n, k)
+        cache = td.p1_covariance_cache(self.c, s, self.sigma)
+        rows = td.re.row_size() + td.re.col_size()
+        outs = [GpuDCRTPolyMatrix(params, rows, t.col_size(), public_matrix.level, True) for t in targets]
+        flat = (_ffi.GpuRngSeed * (3 * len(seeds)))(*[x for triple in seeds for x in triple])
+        raw = GpuDCRTPolyMatrix._raw_array
+        st = _ffi.lib().gpupoly_trapdoor_preimage_many(td.re.raw, cache.raw, public_matrix.raw, params.base_bits(),
+                                                       raw(targets), len(targets), flat, raw(outs))
+        if st != 0:
+            msg = _ffi.last_error_string()
+            if "unsupported" in msg:
+                return [self.preimage(params, td, public_matrix, t, _seeds=sd) for t, sd in zip(targets, seeds)]
+            raise _ffi.GpuPolyError(f"gpupoly_trapdoor_preimage_many failed: {msg}")
+        return outs
+
     def preimage_batched_sharded(self, requests):
         """`preimage_batched_sharded` (gpu.rs:371-397): requests = [(entry_idx, params, trapdoor, A, target)];
         every request runs on the device context its params name, and the contexts work concurrently - the
