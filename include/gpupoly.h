@@ -308,6 +308,26 @@ int gpupoly_matrix_split_columns(const GpuMatrix *src, GpuMatrix *const *blocks,
 int gpupoly_trapdoor_preimage_many(const GpuMatrix *re, const GpuP1CovarianceCache *cache, const GpuMatrix *public_matrix,
                                    uint32_t base_bits, const GpuMatrix *const *targets, size_t n, const GpuRngSeed *seeds,
                                    GpuMatrix *const *outs);
+/* Exact scale-and-round of every coefficient (extension): coefficient k of out[i][j] becomes
+ *   floor((t * c + h) / Q) mod t,   h = round_half ? floor(Q/2) : 0,
+ * c the coefficient of in[i][j] as coeffs() gives it (in [0, Q)), Q the context's FULL modulus; written as its residue
+ * mod every limb of `out`, which is tagged COEFF on success.  round_half = 0 is modulus_switch
+ * (src/matrix/gpu_dcrt_poly.rs:1352-1372, src/element/finite_ring.rs:22-26; the reference then re-NTTs through
+ * from_coeffs / from_poly_vec), round_half = 1 the centred decode of decode_centered_masked_matrix
+ * (src/decoder/masked_high_bit.rs:21-29,39-70; from_biguints / set_entry there).  One thread per coefficient: two Garner
+ * passes and the exact quotient mod the prime 2^64 - 59, no floating point.  `in` may be COEFF or EVAL (an EVAL input is
+ * inverse-transformed in `out`'s storage) and is left as it was unless out == in.  `out` has in's context and shape and
+ * is at full level.  Enqueued on the context's stream; the host does not block.
+ * Refused, with nothing launched and `out` (contents and tag) untouched: a null matrix, t = 0, a context, shape or
+ * level mismatch.  Refused with an error containing "unsupported", likewise untouched: t >= 2^64 - 59, an input below
+ * full level (rescale those on the host).                                                                         */
+int gpupoly_matrix_scale_round(GpuMatrix *out, const GpuMatrix *in, uint64_t t, int round_half);
+/* Every coefficient of `mat` as its value in [0, Q_level): little-endian 64-bit words, words_per_coeff words each
+ * (zero above the words Q_level needs), order [row][col][k], into host memory `out` (synchronous).  COEFF or EVAL
+ * input (an EVAL input is inverse-transformed in scratch; `mat` is left as it was).  Replaces the host CRT of
+ * coeffs() / coeffs_biguints() (src/poly/dcrt/gpu.rs:959-994).  A words_per_coeff below what Q_level needs is
+ * refused with nothing launched.                                                                                  */
+int gpupoly_matrix_store_coeff_words(const GpuMatrix *mat, uint64_t *out, size_t words_per_coeff);
 /* kernel launches issued by the library since it was loaded (every context; copies / memsets not counted): bench.py
  * reports launches per step for the launch-bound small-ring chain                                              */
 uint64_t gpupoly_launch_count(void);

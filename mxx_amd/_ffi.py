@@ -140,6 +140,8 @@ SIGNATURES = {
     "gpupoly_matrix_split_columns": (C.c_int, [_vp, C.POINTER(C.c_void_p), _sz]),
     "gpupoly_trapdoor_preimage_many": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(C.c_void_p), _sz, C.POINTER(GpuRngSeed), C.POINTER(C.c_void_p)]),
     "gpupoly_launch_count": (C.c_uint64, []),
+    "gpupoly_matrix_scale_round": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int]),
+    "gpupoly_matrix_store_coeff_words": (C.c_int, [_vp, C.POINTER(C.c_uint64), _sz]),
     "gpupoly_detmath_eval": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _sz]),
     "gpupoly_device_can_access_peer": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "gpupoly_marker_launch": (C.c_int, [_vp, C.c_uint32]),

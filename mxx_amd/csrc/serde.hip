@@ -15,6 +15,7 @@
 // (pass 2) ORs its w bits into the zeroed payload.  Nothing is staged per coefficient in HBM:
 // the value is recomputed in pass 2 (O(L^2) modmuls, cheaper than a round trip of L words).
 #include "common.h"
+#include "crt.h"
 #include "modarith.h"
 
 #include <algorithm>
@@ -116,57 +117,8 @@ __device__ __forceinline__ uint32_t reconstruct_centered(const W *__restrict__ s
         }
     }
     uint64_t v[ML];
-    // Garner: v_k = (r_k - (v_0 + v_1 q_0 + ...)) / (q_0 .. q_{k-1})  mod q_k, computed incrementally
-    auto garner_step = [&](int k, int j, uint64_t t, uint64_t qk, uint64_t mu, uint32_t kb) {
-        uint64_t vj = v[j];
-        if (vj >= qk) vj %= qk;  // only when an earlier modulus is wider than this one
-        const uint64_t d = t >= vj ? t - vj : t + qk - vj;
-        const uint64_t g = garner[k * garner_stride + j];
-        if constexpr (sizeof(W) == 4) return static_cast<uint64_t>(barrett_reduce(d * g, static_cast<uint32_t>(qk), mu, kb));
-        else return barrett_reduce(static_cast<u128_t>(d) * g, qk, mu, kb);
-    };
-    if constexpr (ML <= 16) {  // fully unrolled, guarded: everything stays in registers
-#pragma unroll
-        for (int k = 0; k < ML; ++k)
-            if (k < L) {
-                const uint64_t qk = sc.q[k], mu = limbs[k].mu;
-                const uint32_t kb = limbs[k].kbits;
-                uint64_t t = res[k];
-#pragma unroll
-                for (int j = 0; j < ML; ++j)
-                    if (j < k) t = garner_step(k, j, t, qk, mu, kb);
-                v[k] = t;
-            }
-    } else {
-        for (int k = 0; k < L; ++k) {
-            const uint64_t qk = sc.q[k], mu = limbs[k].mu;
-            const uint32_t kb = limbs[k].kbits;
-            uint64_t t = res[k];
-            for (int j = 0; j < k; ++j) t = garner_step(k, j, t, qk, mu, kb);
-            v[k] = t;
-        }
-    }
-    // Horner: x = (..(v_{L-1} q_{L-2} + v_{L-2}) q_{L-3} + ..) q_0 + v_0
-    for (int w = 0; w < WC; ++w) x[w] = 0;
-    auto horner_step = [&](int k) {
-        const uint64_t m = sc.q[k];
-        u128_t carry = v[k];
-        for (int w = 0; w < WC; ++w) {
-            const u128_t p = static_cast<u128_t>(x[w]) * m + carry;
-            x[w] = static_cast<uint64_t>(p);
-            carry = p >> 64;
-        }
-    };
-    if constexpr (ML <= 16) {
-#pragma unroll
-        for (int k = ML - 1; k >= 0; --k) {
-            if (k == L - 1) x[0] = v[k];
-            else if (k < L - 1) horner_step(k);
-        }
-    } else {
-        x[0] = v[L - 1];
-        for (int k = L - 2; k >= 0; --k) horner_step(k);
-    }
+    crt_garner_digits<W, ML>(res, v, L, sc.q, garner, garner_stride, limbs);
+    crt_horner_words<ML>(v, L, sc.q, WC, x);
     // centre: negative iff x > floor(Q/2)
     int cmp = 0;
     for (int w = WC - 1; w >= 0; --w) {

@@ -450,7 +450,27 @@ class GpuDCRTPolyMatrix:
         return out
 
     def coeffs(self) -> list:
-        """CRT-reconstructed coefficients as python ints, [row][col][i] (gpu.rs:959-994)."""
+        """CRT-reconstructed coefficients as python ints in [0, Q_level), [row][col][i] (gpu.rs:959-994).  The device
+        rebuilds every coefficient as little-endian 64-bit words (gpupoly_matrix_store_coeff_words, the matrix left as
+        it is); the host makes one int per coefficient from its words, in one pass over the buffer."""
+        n = self.params.ring_dimension()
+        if self.nrow == 0 or self.ncol == 0:
+            return [[] for _ in range(self.nrow)]
+        Q = 1
+        for q in self.params.moduli()[: self.level + 1]:
+            Q *= q
+        wpc = -(-Q.bit_length() // 64)
+        words = np.empty((self.nrow, self.ncol, n, wpc), dtype=np.uint64)
+        st = _ffi.lib().gpupoly_matrix_store_coeff_words(self.raw, words.ctypes.data_as(C.POINTER(C.c_uint64)), wpc)
+        check_status(st, "gpupoly_matrix_store_coeff_words")
+        if wpc == 1:
+            return words[..., 0].tolist()
+        mv, step = memoryview(words).cast("B"), 8 * wpc
+        flat = [int.from_bytes(mv[i : i + step], "little") for i in range(0, len(mv), step)]
+        return [[flat[(r * self.ncol + c) * n : (r * self.ncol + c + 1) * n] for c in range(self.ncol)] for r in range(self.nrow)]
+
+    def _coeffs_host(self) -> list:
+        """coeffs() as a host CRT over the residues: the form before the device store (kept for comparison)."""
         res = self.to_coeff_rns()
         moduli = self.params.moduli()[: self.level + 1]
         Q = 1
@@ -561,8 +581,15 @@ class GpuDCRTPolyMatrix:
         return out
 
     def modulus_switch(self, new_modulus: int) -> "GpuDCRTPolyMatrix":
-        """`modulus_switch` (gpu_dcrt_poly.rs:1352-1372): a host round trip, as in the reference - every coefficient c
-        becomes floor(c * new_modulus / Q) mod new_modulus (src/element/finite_ring.rs:22-26); params are unchanged."""
+        """`modulus_switch` (gpu_dcrt_poly.rs:1352-1372): every coefficient c becomes floor(c * new_modulus / Q) mod
+        new_modulus (src/element/finite_ring.rs:22-26), Q = params.modulus(); params are unchanged, the result is EVAL at
+        full level.  One device call (gpupoly_matrix_scale_round); the host round trip of the reference where the entry
+        reports "unsupported" (an input below full level, new_modulus >= 2^64 - 59) or new_modulus is not a 64-bit word."""
+        out = self._scale_round(new_modulus, False)
+        return out if out is not None else self._modulus_switch_host(new_modulus)
+
+    def _modulus_switch_host(self, new_modulus: int) -> "GpuDCRTPolyMatrix":
+        """modulus_switch as the reference runs it: coeffs() -> big-integer rescale -> from_coeffs -> from_poly_vec."""
         from .poly import GpuDCRTPoly
 
         Q = self.params.modulus()
@@ -570,6 +597,40 @@ class GpuDCRTPolyMatrix:
         for row in self.coeffs():
             rows.append([GpuDCRTPoly.from_coeffs(self.params, [(c * new_modulus // Q) % new_modulus for c in poly]) for poly in row])
         return GpuDCRTPolyMatrix.from_poly_vec(self.params, rows)
+
+    def decode_centered(self, plaintext_modulus: int) -> "GpuDCRTPolyMatrix":
+        """Extension: `decode_centered_masked_matrix` (src/decoder/masked_high_bit.rs:39-70) on the device - every
+        coefficient c becomes floor((t c + floor(Q/2)) / Q) mod t, t = plaintext_modulus >= 2, Q = params.modulus(); the
+        result is EVAL at full level, as from_biguints + set_entry give.  The host loop where the entry reports
+        "unsupported" or t is not a 64-bit word."""
+        assert plaintext_modulus > 1, "plaintext modulus must be at least two"
+        out = self._scale_round(plaintext_modulus, True)
+        return out if out is not None else self._decode_centered_host(plaintext_modulus)
+
+    def _decode_centered_host(self, plaintext_modulus: int) -> "GpuDCRTPolyMatrix":
+        """decode_centered as the reference runs it: coeffs -> big-integer rounding -> from_biguints -> set_entry."""
+        from .poly import GpuDCRTPoly
+
+        Q = self.params.modulus()
+        half = Q // 2
+        out = GpuDCRTPolyMatrix.zero(self.params, self.nrow, self.ncol)
+        for i, row in enumerate(self.coeffs()):
+            for j, poly in enumerate(row):
+                vals = [((plaintext_modulus * c + half) // Q) % plaintext_modulus for c in poly]
+                out.set_entry(i, j, GpuDCRTPoly.from_biguints(self.params, vals))
+        return out
+
+    def _scale_round(self, t: int, round_half: bool):
+        """gpupoly_matrix_scale_round into a new full-level matrix, brought to EVAL; None where the host path applies."""
+        if self.nrow == 0 or self.ncol == 0 or not (1 <= t < 1 << 64):
+            return None
+        out = GpuDCRTPolyMatrix(self.params, self.nrow, self.ncol, self.params.crt_depth() - 1, False)
+        st = _ffi.lib().gpupoly_matrix_scale_round(out.raw, self.raw, t, 1 if round_half else 0)
+        if st != 0 and "unsupported" in _ffi.last_error_string():
+            return None
+        check_status(st, "gpupoly_matrix_scale_round")
+        out.ntt_all_in_place()
+        return out
 
     @classmethod
     def from_compact_bytes(cls, params, data: bytes) -> "GpuDCRTPolyMatrix":
