@@ -3,23 +3,29 @@
 next to the kernel's roofline and the CPU path timed on the same box.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload default|m1|m2a|m2b|m3a|m3b|m4]
-                    [--scaling strong|weak] [--repeats R] [--no-cpu-baseline] [--dump-outputs DIR]
+                    [--scaling strong|weak] [--repeats R] [--no-cpu-baseline] [--dump-outputs DIR] [--full]
 
-Default (what the driver runs): the two shapes the metric is quoted on, in ONE JSON line
+A plain run does only what the headline figure needs: it sets up the headline workload (M2A by default), warms up,
+times the K steps, writes --dump-outputs and prints the line (`metric`, `value`, `unit`, `ms_per_step`, ...; `roofline`
+from the timed steps' own hipEvent marks).  --full adds everything else, as one record:
   * main block  = M2A, the reference's benches/bench_matrix_mul_gpu.rs:20-34 shape: n=2^14, L=15 (24-bit),
     (1x30)*(30x120) in EVAL form = 3600 ring-ops per step, metric dcrt_ring_ops_per_s
-    (1 ring-op = one R_q multiply-accumulate = n*L modular MACs, SURVEY.md 8d);
+    (1 ring-op = one R_q multiply-accumulate = n*L modular MACs), with its repeats, a sustained region,
+    self-validation and CPU baseline;
   * "preimage"  = M3A, benches/bench_preimage_gpu.rs:7-56: n=2^14, L=10, base 2^12, sigma=4.578, d=1,
     50 uniform target columns per call, unit preimages/s (target columns per second);
   * "kernels"   = the NTT / INTT / pointwise mod-mul kernels of BASELINE configs[1] (M1: n=2^14, L=4,
-    1024 polynomials) with their achieved HBM GB/s from hipEvents.
+    1024 polynomials) with their achieved HBM GB/s from hipEvents;
+  * the remaining BASELINE configurations, composed rooflines from the launch trace, CPU baselines and, at N>1, the
+    other gather policy, the weak-scaling figure and the exchange report.
 Always synchronises before stopping the clock (the reference's mat-mul bench does not).
 --dump-outputs DIR: what the headline workload's last timed step returned (M2A's product by default), as DIR/<name>.npy
 for output-for-output comparison of two builds (`dump_outputs`; deterministic workloads only).
 
 Timing: W untimed warm-up steps, then EXACTLY K steps between barrier + device-synchronise brackets, MAX over
 ranks (`value`, `ms_per_step`); after that R further repetitions of the K steps give `repeats` (median / min)
-- BASELINE.md section 4 asks for both.  `roofline.kernel` is the kernel with the largest hipEvent total.
+- BASELINE.md section 4 asks for both; R is 10 under --full and 0 in a plain run unless given.  `roofline.kernel` is
+the kernel with the largest hipEvent total.
 
 N>1: `python bench.py --gpus N` spawns its N ranks itself (before any GPU call; the driver's torchrun launch is
 detected through WORLD_SIZE and used as is).  One process per GPU; `--scaling strong` (default) splits the
@@ -58,16 +64,23 @@ def parse_args(argv=None):
     ap.add_argument("--gather", default="step", choices=["lazy", "step"],
                     help="sharded runs: all-gather the column blocks (product, preimage) after every step, overlapped with the "
                          "next one (default: every step's result exists on every GPU), or once per timed region - the consumer "
-                         "gathers when it needs the whole matrix; the line carries the other mode's figure as `other_gather`")
+                         "gathers when it needs the whole matrix; with --full the line carries the other mode's figure as "
+                         "`other_gather`")
     ap.add_argument("--inproc", action="store_true",
                     help="N>1 in ONE process, as the reference runs (a context per device, a worker thread per context, the "
                          "exchange through gpupoly_matrix_all_gather_columns - RCCL behind the C ABI, no torch)")
-    ap.add_argument("--repeats", type=int, default=10, help="extra repetitions of the K steps for median / min")
-    ap.add_argument("--sustain", type=float, default=5.0,
-                    help="seconds of one contiguous region of the headline workload after the timed K steps (0 = none)")
-    ap.add_argument("--no-trace", action="store_true", help="skip the per-kernel launch trace (composed rooflines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline budget per block")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything, not only the headline figure: the other BASELINE configurations, "
+                         "repeats, a sustained region, self-validation, composed rooflines, CPU baselines, the other gather "
+                         "policy and the exchange report")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="extra repetitions of the K steps for median / min (default: 10 with --full, else 0)")
+    ap.add_argument("--sustain", type=float, default=None,
+                    help="seconds of one contiguous region of the headline workload after the timed K steps "
+                         "(0 = none; default: 5 with --full, else 0)")
+    ap.add_argument("--no-trace", action="store_true", help="--full: skip the per-kernel launch trace (composed rooflines)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU-baseline budget per block")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo rehearses the launcher / rendezvous on a GPU-less box (with --dry-run) and the whole sharded path with more ranks than GPUs (ranks share devices; not a measurement)")
     ap.add_argument("--dry-run", action="store_true", help="launch + rendezvous + one all-reduce, no GPU work")
@@ -75,6 +88,10 @@ def parse_args(argv=None):
                     help="after the timed steps, write what the headline workload's last timed step returned as DIR/<name>.npy "
                          "(residues in float32 / float64, at most 64 MB in all: a fixed, seeded sample of entries when larger)")
     args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 10 if args.full else 0
+    if args.sustain is None:
+        args.sustain = 5.0 if args.full else 0.0
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs is not None:
@@ -809,12 +826,14 @@ WORKLOADS = {"m1": M1, "m2a": M2A, "m2b": M2B, "m2b_decompose": M2BDecompose, "m
 # ---------------------------------------------------------------------------------------------------
 # measurement
 # ---------------------------------------------------------------------------------------------------
-def run_block(wl: Workload, d: Dist, steps: int, warmup: int, repeats: int, sustain_s: float = 0.0, capture=None):
+def run_block(wl: Workload, d: Dist, steps: int, warmup: int, repeats: int, sustain_s: float = 0.0, capture=None,
+              extras: bool = True):
     """The contract's timed region (K steps, barrier + synchronise on both sides, MAX over ranks), `capture(wl)` (if given)
     on the result of its last step, then
     `repeats` more repetitions of the same K steps for median / min, then - `sustain_s` > 0, the headline workload - ONE
     contiguous region of about that many seconds of the same steps (K steps of a sub-millisecond product last 12 ms, too
-    short for an outside utilisation sampler to ever see the device busy; VERDICT r4 weak #2)."""
+    short for an outside utilisation sampler to ever see the device busy).  `extras` (--full): then
+    the other gather policy's K steps and the workload's self-validation."""
     mx = wl.mx
     for i in range(steps):  # create every hipEvent before the timed region (creation on the host would be timed)
         for j in range(wl.nmarks):
@@ -860,7 +879,7 @@ def run_block(wl: Workload, d: Dist, steps: int, warmup: int, repeats: int, sust
         dt = d.max_over_ranks(time.perf_counter() - t1)
         sustained = {"steps": count, "seconds": dt, "ms_per_step": dt * 1e3 / count, "value": wl.units * count / dt}
     other = None
-    if wl.gather is not None and hasattr(wl, "lazy_gather"):
+    if extras and wl.gather is not None and hasattr(wl, "lazy_gather"):
         # the same K steps under the other exchange policy (per step <-> once per region), so that the line shows what the
         # choice is worth; `value` above is the policy named in the top-level "gather" field
         wl.lazy_gather = not wl.lazy_gather
@@ -879,16 +898,17 @@ def run_block(wl: Workload, d: Dist, steps: int, warmup: int, repeats: int, sust
         wl.drain()
     # every rank validates (its own block and every gathered foreign block); the verdict is collective so that one rank's
     # failure fails the whole job instead of leaving the others in the next barrier
-    failure = None
-    try:
-        wl.check()
-    except Exception as e:  # noqa: BLE001 - any failure (a GpuPolyError, an allocation) must still reach the collective below
-        failure = e
-    all_ok = d.min_over_ranks(0.0 if failure else 1.0)
-    if failure is not None:
-        raise failure
-    if all_ok < 1.0:
-        raise AssertionError(f"rank {d.rank}: another rank's self-validation failed")
+    if extras:
+        failure = None
+        try:
+            wl.check()
+        except Exception as e:  # noqa: BLE001 - any failure (a GpuPolyError, an allocation) must still reach the collective below
+            failure = e
+        all_ok = d.min_over_ranks(0.0 if failure else 1.0)
+        if failure is not None:
+            raise failure
+        if all_ok < 1.0:
+            raise AssertionError(f"rank {d.rank}: another rank's self-validation failed")
     all_ms = [elapsed * 1e3 / steps] + reps
     return {
         "other_gather": other,
@@ -1151,7 +1171,8 @@ def block_json(wl: Workload, res, d: Dist, args, steps, warmup):
         **({"sustained": res["sustained"]} if res.get("sustained") else {}),
         "roofline": roofline_of(wl, res["kernel_ms"]),
         **({"kernel_launches_per_step": int(wl.launches_per_step)} if hasattr(wl, "launches_per_step") else {}),
-        **({"exchange": torch_exchange_report(wl, d)} if d.active and not d.inproc and getattr(wl, "strong", False)
+        # the exchange report states what the self-validation (--full) found
+        **({"exchange": torch_exchange_report(wl, d)} if args.full and d.active and not d.inproc and getattr(wl, "strong", False)
            and isinstance(wl, (MatMul, Preimage)) else {}),
     }
 
@@ -1225,10 +1246,11 @@ def torch_exchange_report(wl, d):
             "comm_verified_by_this_run": bool(ok and distinct and len(devices) > 1 and d.backend == "nccl")}
 
 
-def run_block_inproc(mx, wls, comm, steps, warmup, repeats):
+def run_block_inproc(mx, wls, comm, steps, warmup, repeats, extras=True):
     """run_block for N contexts of one process: a worker thread per context issues that context's steps (the ABI calls
     release the GIL and never block), a barrier per step lets one thread enqueue the step's all-gather through the C ABI
-    once every context has enqueued its block; ONE host clock around the region, every device synchronised on both sides."""
+    once every context has enqueued its block; ONE host clock around the region, every device synchronised on both sides.
+    `extras` (--full): then the other gather policy's K steps and every context's self-validation."""
     import threading
 
     n = len(wls)
@@ -1286,7 +1308,7 @@ def run_block_inproc(mx, wls, comm, steps, warmup, repeats):
     kernel_ms = wls[0].kernel_ms(steps)
     reps = [region(steps, False) * 1e3 / steps for _ in range(repeats)]
     other = None
-    if comm is not None:
+    if extras and comm is not None:
         for wl in wls:
             wl.lazy_gather = not wl.lazy_gather
         region(1, False)
@@ -1295,8 +1317,9 @@ def run_block_inproc(mx, wls, comm, steps, warmup, repeats):
         for wl in wls:
             wl.lazy_gather = not wl.lazy_gather
         region(1, False)
-    for wl in wls:
-        wl.check()
+    if extras:
+        for wl in wls:
+            wl.check()
     all_ms = [elapsed * 1e3 / steps] + reps
     return {"other_gather": other, "elapsed_s": elapsed, "ms_per_step": elapsed * 1e3 / steps, "value": wls[0].units * steps / elapsed,
             "kernel_ms": kernel_ms,
@@ -1323,25 +1346,24 @@ def main_inproc(args, emit):
         for wl in wls:
             wl.setup()
         comm = GpuComm([wl.params for wl in wls]) if wls[0].strong and isinstance(wls[0], (MatMul, Preimage)) else None
-        res = run_block_inproc(mx, wls, comm, args.steps, args.warmup, repeats)
+        res = run_block_inproc(mx, wls, comm, args.steps, args.warmup, repeats, args.full)
         line = block_json(wls[0], res, ranks[0], args, args.steps, args.warmup)
         line["config"]["comm_backend"] = comm.backend if comm is not None else None
         line["config"]["devices"] = [r % ndev for r in range(n)]
-        line["exchange"] = exchange_report(mx, wls, len(comm) if comm is not None else n, comm.backend if comm is not None else None,
-                                           [r % ndev for r in range(n)])
+        if args.full:  # what the self-validation found
+            line["exchange"] = exchange_report(mx, wls, len(comm) if comm is not None else n, comm.backend if comm is not None else None,
+                                               [r % ndev for r in range(n)])
         if comm is not None:
             comm.close()
         return line
 
-    if args.workload == "default":
-        line = run("m2a", args.repeats)
+    line = run("m2a" if args.workload == "default" else args.workload, args.repeats)
+    if args.workload == "default" and args.full:
         pre = run("m3a", min(args.repeats, 3))
         for key in ("n_gpus", "higher_is_better", "vs_baseline", "data", "scaling", "roofline"):
             pre.pop(key, None)
         line["preimage"] = pre
-    else:
-        line = run(args.workload, args.repeats)
-    line["cpu_baseline"] = None  # an N = 1 leg (run `python bench.py`)
+    line["cpu_baseline"] = None  # an N = 1 leg (run `python bench.py --full`)
     emit(line)
 
 
@@ -1700,10 +1722,10 @@ def main():
     if args.dump_outputs is not None and d.rank == 0:
         capture = lambda w: dumped.update(dump_outputs(w, args.dump_outputs))  # noqa: E731
 
-    def run(name, steps_, warmup_, repeats_, sustain_s=0.0, capture=None):
+    def run(name, steps_, warmup_, repeats_, sustain_s=0.0, capture=None, extras=True):
         wl = WORKLOADS[name](mx, d, args, device)
         wl.setup()
-        res = run_block(wl, d, steps_, warmup_, repeats_, sustain_s, capture)
+        res = run_block(wl, d, steps_, warmup_, repeats_, sustain_s, capture, extras)
         return wl, res
 
     def independent_units(name):
@@ -1734,11 +1756,14 @@ def main():
             blk["cpu_baseline"] = cpu_baseline(name, args.cpu_seconds / 2)
         return w, r, blk
 
+    # the headline workload: all that a plain run does; --full adds the blocks below
+    headline = "m2a" if args.workload == "default" else args.workload
+    wl, res = run(headline, steps, warmup, args.repeats, args.sustain if headline == "m2a" else 0.0, capture, args.full)
+    line = block_json(wl, res, d, args, steps, warmup)
     if args.workload == "default":
-        wl, res = run("m2a", steps, warmup, args.repeats, args.sustain, capture)
-        line = block_json(wl, res, d, args, steps, warmup)
         line["output_buffers"] = ("the product writes into pre-allocated output matrices; the reference's timed `&left * &right` "
                                   "also creates its output (src/matrix/gpu_dcrt_poly.rs:1792-1815) - microseconds from the stream-ordered cache")
+    if args.full and args.workload == "default":
         del wl
         if d.world > 1 and args.scaling == "strong":
             line["independent_units"] = independent_units("m2a")
@@ -1816,9 +1841,7 @@ def main():
             line["cpu_baseline"] = cpu_baseline("m2a", args.cpu_seconds)
             line["preimage"]["cpu_baseline"] = cpu_baseline("m3a", args.cpu_seconds)
             line["kernels"]["cpu_baseline"] = cpu_baseline("m1", args.cpu_seconds / 2)
-    else:
-        wl, res = run(args.workload, steps, warmup, args.repeats, args.sustain if args.workload == "m2a" else 0.0, capture)
-        line = block_json(wl, res, d, args, steps, warmup)
+    elif args.full:
         if args.workload == "m1":
             line["kernels"] = kernels_block(wl, res)
             if d.world == 1:

@@ -253,3 +253,15 @@ def test_steps_and_dump_outputs_arguments_are_checked(capsys):
         with pytest.raises(SystemExit):
             bench.parse_args(bad)
     capsys.readouterr()
+
+
+def test_a_plain_run_leaves_the_extras_to_full():
+    """A plain run times the headline steps only: no repeats and no sustained region unless asked for; --full brings
+    back the defaults of a complete record, and explicit values hold in both modes."""
+    plain = bench.parse_args(["--steps", "5", "--warmup", "2"])
+    assert plain.full is False and plain.repeats == 0 and plain.sustain == 0.0
+    assert plain.steps == 5 and plain.warmup == 2
+    full = bench.parse_args(["--full"])
+    assert full.full is True and full.repeats == 10 and full.sustain == 5.0
+    assert bench.parse_args(["--repeats", "3", "--sustain", "1"]).repeats == 3
+    assert bench.parse_args(["--full", "--repeats", "0", "--sustain", "0"]).sustain == 0.0

@@ -207,9 +207,9 @@ def test_gathered_blocks_self_validation_and_shifted_offset(gpu, oracle):
 
 
 def test_bench_inproc_two_contexts_validates_foreign_blocks_and_fails_on_a_shift(gpu):
-    """`bench.py --gpus 2 --inproc` (two contexts sharing this box's device): the line reports the exchange - ranks seen,
-    backend, peer access, foreign blocks checked by every rank - and the same run with the gathered matrix rotated by one
-    column (MXX_BENCH_FAULT_INJECT=shift) exits non-zero."""
+    """`bench.py --gpus 2 --inproc --full` (two contexts sharing this box's device): the line reports the exchange - ranks
+    seen, backend, peer access, foreign blocks checked by every rank - and the same run with the gathered matrix rotated by
+    one column (MXX_BENCH_FAULT_INJECT=shift) exits non-zero."""
     import json
     import os
     import subprocess
@@ -218,7 +218,7 @@ def test_bench_inproc_two_contexts_validates_foreign_blocks_and_fails_on_a_shift
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MXX_BENCH_INPROC_SHARE_DEVICES="1")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--inproc", "--steps", "2", "--warmup", "1", "--repeats", "0",
-           "--no-trace"]
+           "--no-trace", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     stdout_lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

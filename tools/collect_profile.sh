@@ -12,6 +12,6 @@ run fetch "FETCH_SIZE"
 run write "WRITE_SIZE"
 run sq "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES"
 python3 tools/pmc_summary.py $OUT "" > $OUT/pmc_summary_$WL.txt
-python3 bench.py --workload $WL --steps 20 --warmup 3 > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err
+python3 bench.py --workload $WL --steps 20 --warmup 3 --full > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err
 tail -1 $OUT/bench_$WL.json | cut -c1-400
 rm -rf $OUT/trace/*/*kernel_trace.csv $OUT/fetch $OUT/write $OUT/sq

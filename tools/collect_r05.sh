@@ -16,7 +16,7 @@ export MXX_HEAD=${MXX_HEAD:-unknown}
 for S in $STAGES; do
 case $S in
 a)
-  python3 bench.py > $OUT/bench_short.json 2> $OUT/bench_default.err || { echo "bench default failed"; tail -20 $OUT/bench_default.err; exit 1; }
+  python3 bench.py --full > $OUT/bench_short.json 2> $OUT/bench_default.err || { echo "bench default failed"; tail -20 $OUT/bench_default.err; exit 1; }
   cp bench_detail.json $OUT/bench_detail.json
   wc -c $OUT/bench_short.json; cat $OUT/bench_short.json
   ;;
@@ -34,7 +34,7 @@ b)
   done
   ;;
 c)
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_default -- python3 bench.py --steps 20 --warmup 3 --repeats 0 --sustain 0 --no-cpu-baseline --no-trace > $OUT/under_rocprof_default.log 2>&1 || { echo "kernel trace failed"; tail -5 $OUT/under_rocprof_default.log; exit 1; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_default -- python3 bench.py --steps 20 --warmup 3 --repeats 0 --sustain 0 --full --no-cpu-baseline --no-trace > $OUT/under_rocprof_default.log 2>&1 || { echo "kernel trace failed"; tail -5 $OUT/under_rocprof_default.log; exit 1; }
   cp $OUT/trace_default/*/*kernel_stats.csv $OUT/r05_kernel_stats_default.csv 2>/dev/null
   rm -rf $OUT/trace_default
   head -12 $OUT/r05_kernel_stats_default.csv | cut -c1-160
