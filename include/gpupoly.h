@@ -59,6 +59,8 @@ typedef struct GpuRngSeed {
 #define GPU_MATRIX_DIST_GAUSS 1
 #define GPU_MATRIX_DIST_BIT 2
 #define GPU_MATRIX_DIST_TERNARY 3
+#define GPU_MATRIX_LAYOUT_WORDS 0    /* one 4- or 8-byte word per residue */
+#define GPU_MATRIX_LAYOUT_PACKED24 1 /* 3 bytes per residue (moduli below 2^24): uniform samples, until first words use */
 
 /* ---- runtime: cuda/include/Runtime.cuh:20-44,108 ------------------------- */
 /* L = moduli_len - 1 (top level); gpu_ids[0] is the device the context lives on. */
@@ -232,8 +234,13 @@ int gpupoly_timer_stop(GpuContext *ctx, float *out_ms);
  * time between two marks once both have completed (blocks on the later one).    */
 int gpupoly_timer_mark(GpuContext *ctx, uint32_t slot);
 int gpupoly_timer_elapsed(GpuContext *ctx, uint32_t slot_begin, uint32_t slot_end, float *out_ms);
-/* raw device pointer / byte size of a matrix (zero-copy interop, e.g. RCCL).  */
+/* raw device pointer / byte size of a matrix (zero-copy interop, e.g. RCCL).  Always the words layout: a
+ * GPU_MATRIX_LAYOUT_PACKED24 matrix is unpacked first (once, on its context's stream) and stays in words.  */
 int gpupoly_matrix_device_ptr(const GpuMatrix *mat, void **out_ptr, size_t *out_bytes);
+/* storage layout of a matrix now: GPU_MATRIX_LAYOUT_WORDS, or GPU_MATRIX_LAYOUT_PACKED24 - a uniform sample of a
+ * 32-bit context whose moduli are all below 2^24 (MXX_HIP_PACK24=0 turns it off).  Any operation without a packed
+ * path unpacks the matrix to words first; only the register-tile product reads the packed bytes.  */
+int gpupoly_matrix_layout(const GpuMatrix *mat, int *out);
 /* Replica of `src` in another context (same ring; any device): one device-to-device / peer copy over
  * xGMI, ordered on both contexts' streams - replaces the reference's host round trip
  * to_cpu_staging_bytes -> from_cpu_staging_bytes (src/lookup/ggh15/pubkey_gpu.rs:153-196).     */

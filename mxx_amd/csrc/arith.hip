@@ -104,11 +104,34 @@ __global__ void equal_kernel(const W *__restrict__ a, const W *__restrict__ b, s
 }
 
 // ---- matrix product ---------------------------------------------------------------------
-template <typename W, int TR, int TC, int SV, bool PF = false, bool NTB = false>
+// the 4 residues of a lane's slots from a PACKED24 row (layout.hip): 12 bytes, one dwordx3 load
+template <bool NT>
+__device__ __forceinline__ void load_packed4(const uint32_t *p, uint32_t *o) {
+    uint32_t w0, w1, w2;
+    if constexpr (NT) {
+        w0 = __builtin_nontemporal_load(p);
+        w1 = __builtin_nontemporal_load(p + 1);
+        w2 = __builtin_nontemporal_load(p + 2);
+    } else {
+        w0 = p[0];
+        w1 = p[1];
+        w2 = p[2];
+    }
+    o[0] = w0 & 0xffffffu;
+    o[1] = __builtin_amdgcn_alignbit(w1, w0, 24) & 0xffffffu;
+    o[2] = __builtin_amdgcn_alignbit(w2, w1, 16) & 0xffffffu;
+    o[3] = w2 >> 8;
+}
+
+// PK (32-bit words, 4 slots per lane): 1 = A, 2 = B is PACKED24 (never both: launch_matmul_cfg).  Its offsets and strides then count 3 words per
+// 4 residues - 3/4 of the words layout's, all whole: N % 4 == 0 and i % 4 == 0.
+template <typename W, int TR, int TC, int SV, bool PF = false, bool NTB = false, int PK = 0>
 __global__ void __launch_bounds__(256)
     matmul_kernel(W *__restrict__ C, const W *__restrict__ A, const W *__restrict__ B,
                   const LimbConst *__restrict__ limbs, uint32_t rows, uint32_t inner, uint32_t cols, uint32_t L,
                   uint32_t N, uint32_t col_tiles) {
+    static_assert(PK == 0 || (sizeof(W) == 4 && SV == 4), "packed operands: 4 slots of 32-bit words per lane");
+    constexpr bool PA = (PK & 1) != 0, PB = (PK & 2) != 0;
     const uint32_t limb = blockIdx.z;
     const uint32_t rt = blockIdx.y / col_tiles, ct = blockIdx.y - rt * col_tiles;
     const uint32_t r0 = rt * TR, c0 = ct * TC;
@@ -119,20 +142,22 @@ __global__ void __launch_bounds__(256)
     typedef typename std::conditional<sizeof(W) * SV == 16, uint4, typename std::conditional<sizeof(W) * SV == 8, uint2, W>::type>::type VT;
     static_assert(sizeof(VT) == sizeof(W) * SV, "vector width");
 
-    const size_t strideA = static_cast<size_t>(L) * N;  // words between consecutive polys
+    const size_t strideA = PA ? static_cast<size_t>(L) * N / 4 * 3 : static_cast<size_t>(L) * N;  // words between consecutive polys
     // clamp out-of-range tile rows/cols to a valid entry; their results are never stored
     size_t a_off[TR], b_off[TC];
 #pragma unroll
     for (int r = 0; r < TR; ++r) {
         uint32_t rr = min(r0 + r, rows - 1);
         a_off[r] = (static_cast<size_t>(rr) * inner * L + limb) * N + i;
+        if constexpr (PA) a_off[r] = a_off[r] / 4 * 3;
     }
 #pragma unroll
     for (int c = 0; c < TC; ++c) {
         uint32_t cc = min(c0 + c, cols - 1);
         b_off[c] = (static_cast<size_t>(cc) * L + limb) * N + i;
+        if constexpr (PB) b_off[c] = b_off[c] / 4 * 3;
     }
-    const size_t strideBk = static_cast<size_t>(cols) * L * N;
+    const size_t strideBk = PB ? static_cast<size_t>(cols) * L * N / 4 * 3 : static_cast<size_t>(cols) * L * N;
 
     if constexpr (sizeof(W) == 4) {
         uint64_t acc[TR][TC][SV];
@@ -152,10 +177,16 @@ __global__ void __launch_bounds__(256)
         W av[PF ? 2 : 1][TR][SV], bv[PF ? 2 : 1][TC][SV];
         auto load = [&](int set, uint32_t k) {
 #pragma unroll
-            for (int r = 0; r < TR; ++r)
-                *reinterpret_cast<VT *>(av[set][r]) = *reinterpret_cast<const VT *>(A + a_off[r] + k * strideA);
+            for (int r = 0; r < TR; ++r) {
+                if constexpr (PA) load_packed4<false>(A + a_off[r] + k * strideA, av[set][r]);
+                else *reinterpret_cast<VT *>(av[set][r]) = *reinterpret_cast<const VT *>(A + a_off[r] + k * strideA);
+            }
 #pragma unroll
             for (int c = 0; c < TC; ++c) {
+                if constexpr (PB) {  // the non-temporal hint as for words (below)
+                    load_packed4<NTB>(B + b_off[c] + k * strideBk, bv[set][c]);
+                    continue;
+                }
                 // NTB (the host sets it when there is ONE row tile): B is then streamed exactly once, and non-temporal loads
                 // keep it from displacing A (read by every column tile) in L2 / the Infinity Cache - M2A 608-629 -> 588 us.
                 // With several row tiles the other tiles re-read B from cache and the hint costs 25-55 %
@@ -442,8 +473,8 @@ static int launch_matmul_lds_u32(GpuMatrix *out, const GpuMatrix *lhs, const Gpu
     const uint32_t remap = (groups % 8 == 0) ? 1u : 0u;
     ctx->last_kernel = "matmul_lds_kernel_u32 (64 slots x 16x16 tile, operands staged through registers into LDS)";
     MXX_LAUNCH(matmul_lds_kernel_u32, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, ctx->stream,
-                       static_cast<uint32_t *>(out->data), static_cast<const uint32_t *>(lhs->data),
-                       static_cast<const uint32_t *>(rhs->data), ctx->d_limbs, rows, inner, cols, L, N, row_tiles,
+                       static_cast<uint32_t *>(words_ptr(out)), static_cast<const uint32_t *>(words_ptr(lhs)),
+                       static_cast<const uint32_t *>(words_ptr(rhs)), ctx->d_limbs, rows, inner, cols, L, N, row_tiles,
                        col_tiles, slot_chunks, remap);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -461,23 +492,52 @@ static int launch_matmul_cfg(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatr
     if (static_cast<uint64_t>(row_tiles) * col_tiles > 65535) return set_error("gpu_matrix_mul: matrix too large");
     dim3 grid(gx, row_tiles * col_tiles, L);
     const bool nt = row_tiles == 1 && rhs->bytes > (size_t(1) << 28);
-    static const std::string name[2] = {
-        std::string("matmul_kernel<") + (sizeof(W) == 4 ? "u32," : "u64,") + std::to_string(TR) + "," + std::to_string(TC) + "," +
-            std::to_string(SV) + (PF ? ",loads-ahead" : "") + "> (register tile rows x cols x slots per lane)",
-        std::string("matmul_kernel<") + (sizeof(W) == 4 ? "u32," : "u64,") + std::to_string(TR) + "," + std::to_string(TC) + "," +
-            std::to_string(SV) + (PF ? ",loads-ahead" : "") + ",nt> (register tile rows x cols x slots per lane, B streamed once with non-temporal loads)"};
-    ctx->last_kernel = name[nt ? 1 : 0].c_str();
+    auto label = [](bool nt_, int pk) {
+        return std::string("matmul_kernel<") + (sizeof(W) == 4 ? "u32," : "u64,") + std::to_string(TR) + "," + std::to_string(TC) + "," +
+               std::to_string(SV) + (PF ? ",loads-ahead" : "") + (nt_ ? ",nt" : "") +
+               (pk == 2 ? ",packed24 B" : pk == 1 ? ",packed24 A" : "") +
+               "> (register tile rows x cols x slots per lane" + (nt_ ? ", B streamed once with non-temporal loads" : "") +
+               (pk ? ", 3-byte residues" : "") + ")";
+    };
+    static const std::string name[2][3] = {{label(false, 0), label(false, 1), label(false, 2)}, {label(true, 0), label(true, 1), label(true, 2)}};
+    W *c = static_cast<W *>(words_ptr(out));  // before the layout lock below: it may unpack
     // B is read by this one row tile only and cannot live in the 256 MB Infinity Cache: streamed with non-temporal loads
     // (a smaller B is often re-used from cache by the next product - the hint made repeated products on a 134 MB operand
     // 40 % slower)
-    if (nt)
-        MXX_LAUNCH((matmul_kernel<W, TR, TC, SV, PF, true>), grid, dim3(threads), 0, ctx->stream,
-                           static_cast<W *>(out->data), static_cast<const W *>(lhs->data),
-                           static_cast<const W *>(rhs->data), ctx->d_limbs, rows, inner, cols, L, N, col_tiles);
-    else
-        MXX_LAUNCH((matmul_kernel<W, TR, TC, SV, PF, false>), grid, dim3(threads), 0, ctx->stream,
-                           static_cast<W *>(out->data), static_cast<const W *>(lhs->data),
-                           static_cast<const W *>(rhs->data), ctx->d_limbs, rows, inner, cols, L, N, col_tiles);
+#define MXX_MM(NT, PK) \
+    MXX_LAUNCH((matmul_kernel<W, TR, TC, SV, PF, NT, PK>), grid, dim3(threads), 0, ctx->stream, c, a, b, ctx->d_limbs, rows, inner, cols, L, N, col_tiles)
+    if constexpr (sizeof(W) == 4 && SV == 4) {
+        if (lhs->ctx == ctx && rhs->ctx == ctx) {
+            // one packed operand per product: with both packed, the products of two 24-bit-masked values came out wrong
+            // in slots 0..2 (each operand packed alone is exact).  A is the small operand: unpacked, once
+            if (lhs->layout.v.load(std::memory_order_acquire) == GPU_MATRIX_LAYOUT_PACKED24 &&
+                rhs->layout.v.load(std::memory_order_acquire) == GPU_MATRIX_LAYOUT_PACKED24)
+                (void)words_ptr(lhs);
+            // either operand may be PACKED24 and is read as it is, under the layout lock: no other thread unpacks (and
+            // frees) it between this look-up and the launch
+            std::lock_guard<std::mutex> lk(ctx->layout_mutex);
+            bool pa = false, pb = false;
+            const W *a = static_cast<const W *>(packed24_ptr(lhs, &pa)), *b = static_cast<const W *>(packed24_ptr(rhs, &pb));
+            if (pa && pb) return set_error("gpu_matrix_mul: both operands packed");  // unreachable: A was unpacked above
+            const int pk = (pa ? 1 : 0) | (pb ? 2 : 0);
+            ctx->last_kernel = name[nt ? 1 : 0][pk].c_str();
+            switch (pk | (nt ? 4 : 0)) {
+                case 0: MXX_MM(false, 0); break;
+                case 1: MXX_MM(false, 1); break;
+                case 2: MXX_MM(false, 2); break;
+                case 4: MXX_MM(true, 0); break;
+                case 5: MXX_MM(true, 1); break;
+                default: MXX_MM(true, 2); break;
+            }
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }
+    }
+    const W *a = static_cast<const W *>(words_ptr(lhs)), *b = static_cast<const W *>(words_ptr(rhs));
+    ctx->last_kernel = name[nt ? 1 : 0][0].c_str();
+    if (nt) MXX_MM(true, 0);
+    else MXX_MM(false, 0);
+#undef MXX_MM
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -586,13 +646,13 @@ static int launch_elementwise_typed(GpuMatrix *out, const GpuMatrix *a, const Gp
         const size_t vecs = words / VNATIVE;
         unsigned blocks = static_cast<unsigned>(std::min<size_t>((vecs + 255) / 256, 16384));
         MXX_LAUNCH((elementwise_kernel<W, OP, BCAST, VNATIVE>), dim3(blocks), dim3(256), 0, ctx->stream,
-                           static_cast<W *>(out->data), static_cast<const W *>(a->data),
-                           static_cast<const W *>(b->data), ctx->d_limbs, L, ctx->logN, wpp, vecs);
+                           static_cast<W *>(words_ptr(out)), static_cast<const W *>(words_ptr(a)),
+                           static_cast<const W *>(words_ptr(b)), ctx->d_limbs, L, ctx->logN, wpp, vecs);
     } else {
         unsigned blocks = static_cast<unsigned>(std::min<size_t>((words + 255) / 256, 16384));
         MXX_LAUNCH((elementwise_kernel<W, OP, BCAST, 1>), dim3(blocks), dim3(256), 0, ctx->stream,
-                           static_cast<W *>(out->data), static_cast<const W *>(a->data),
-                           static_cast<const W *>(b->data), ctx->d_limbs, L, ctx->logN, wpp, words);
+                           static_cast<W *>(words_ptr(out)), static_cast<const W *>(words_ptr(a)),
+                           static_cast<const W *>(words_ptr(b)), ctx->d_limbs, L, ctx->logN, wpp, words);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -614,7 +674,7 @@ static GpuMatrix matrix_view(const GpuMatrix *m, size_t first_poly, size_t rows,
     v.rows = rows;
     v.cols = cols;
     v.format = m->format;
-    v.data = static_cast<char *>(m->data) + first_poly * poly_bytes;
+    v.storage = static_cast<char *>(words_ptr(m)) + first_poly * poly_bytes;
     v.bytes = rows * cols * poly_bytes;
     return v;
 }
@@ -669,19 +729,19 @@ extern "C" int gpupoly_matrix_ntt_add_rows(GpuMatrix *out, size_t dst_row, GpuMa
     GpuMatrix view = matrix_view(out, dst_row * out->cols, coeff->rows, coeff->cols, poly_bytes);
     view.format = GPU_POLY_FORMAT_EVAL;
     if (!ctx->wide) {
-        const int rc = launch_ntt_add_u32(ctx, static_cast<uint32_t *>(view.data), static_cast<const uint32_t *>(coeff->data),
-                                          static_cast<const uint32_t *>(addend->data), polys * L, static_cast<uint32_t>(L));
+        const int rc = launch_ntt_add_u32(ctx, static_cast<uint32_t *>(words_ptr(&view)), static_cast<const uint32_t *>(words_ptr(coeff)),
+                                          static_cast<const uint32_t *>(words_ptr(addend)), polys * L, static_cast<uint32_t>(L));
         if (rc >= 0) return rc;
     }
     if (consume_coeff) {
-        int rc = launch_ntt(ctx, coeff->data, polys * L, static_cast<int>(L), false);
+        int rc = launch_ntt(ctx, words_ptr(coeff), polys * L, static_cast<int>(L), false);
         if (rc) return rc;
         coeff->format = GPU_POLY_FORMAT_EVAL;
         return launch_elementwise<OP_ADD, false>(&view, coeff, addend);
     }
     MXX_TRACED_COPY("copy (device to device)", ctx->stream, 2.0 * view.bytes,
-                    HIP_TRY(hipMemcpyAsync(view.data, coeff->data, view.bytes, hipMemcpyDeviceToDevice, ctx->stream)));
-    int rc = launch_ntt(ctx, view.data, polys * L, static_cast<int>(L), false);
+                    HIP_TRY(hipMemcpyAsync(words_ptr(&view), words_ptr(coeff), view.bytes, hipMemcpyDeviceToDevice, ctx->stream)));
+    int rc = launch_ntt(ctx, words_ptr(&view), polys * L, static_cast<int>(L), false);
     if (rc) return rc;
     return launch_elementwise<OP_ADD, false>(&view, &view, addend);  // in place: every word is read, then written
     ABI_GUARD_END
@@ -750,13 +810,13 @@ static int launch_tensor_typed(GpuMatrix *out, const GpuMatrix *a, const GpuMatr
     if (gz > 65535) return set_error("gpupoly_matrix_tensor: matrix too large");
     if (ctx->N >= VNATIVE) {
         const dim3 grid(static_cast<unsigned>(std::min<size_t>((wpp / VNATIVE + 255) / 256, 64)), static_cast<unsigned>(gy), static_cast<unsigned>(gz));
-        MXX_LAUNCH((tensor_kernel<W, VNATIVE>), grid, dim3(256), 0, ctx->stream, static_cast<W *>(out->data),
-                           static_cast<const W *>(a->data), static_cast<const W *>(b->data), ctx->d_limbs, ctx->logN, wpp,
+        MXX_LAUNCH((tensor_kernel<W, VNATIVE>), grid, dim3(256), 0, ctx->stream, static_cast<W *>(words_ptr(out)),
+                           static_cast<const W *>(words_ptr(a)), static_cast<const W *>(words_ptr(b)), ctx->d_limbs, ctx->logN, wpp,
                            a->cols, b->rows, b->cols, polys);
     } else {
         const dim3 grid(static_cast<unsigned>(std::min<size_t>((wpp + 255) / 256, 64)), static_cast<unsigned>(gy), static_cast<unsigned>(gz));
-        MXX_LAUNCH((tensor_kernel<W, 1>), grid, dim3(256), 0, ctx->stream, static_cast<W *>(out->data),
-                           static_cast<const W *>(a->data), static_cast<const W *>(b->data), ctx->d_limbs, ctx->logN, wpp,
+        MXX_LAUNCH((tensor_kernel<W, 1>), grid, dim3(256), 0, ctx->stream, static_cast<W *>(words_ptr(out)),
+                           static_cast<const W *>(words_ptr(a)), static_cast<const W *>(words_ptr(b)), ctx->d_limbs, ctx->logN, wpp,
                            a->cols, b->rows, b->cols, polys);
     }
     HIP_TRY(hipGetLastError());
@@ -796,7 +856,7 @@ extern "C" int gpu_matrix_mul(GpuMatrix *out, const GpuMatrix *lhs, const GpuMat
     if (matrix_polys(out) == 0) return 0;
     if (ctx_activate(out->ctx)) return 1;
     if (lhs->cols == 0) {
-        HIP_TRY(hipMemsetAsync(out->data, 0, out->bytes, out->ctx->stream));
+        HIP_TRY(hipMemsetAsync(words_ptr(out), 0, out->bytes, out->ctx->stream));
         return 0;
     }
     MXX_TRACE_BYTES(static_cast<double>(lhs->bytes) + rhs->bytes + out->bytes);  // (r m + m c + r c) n L w
@@ -829,7 +889,7 @@ static int mul_tensor_identity_impl(GpuMatrix *out, const GpuMatrix *lhs, const 
     if (matrix_polys(out) == 0) return 0;
     if (ctx_activate(ctx)) return 1;
     if (w == 0) {
-        HIP_TRY(hipMemsetAsync(out->data, 0, out->bytes, ctx->stream));
+        HIP_TRY(hipMemsetAsync(words_ptr(out), 0, out->bytes, ctx->stream));
         return 0;
     }
     const size_t poly_bytes = L * static_cast<size_t>(ctx->N) * ctx->word_bytes;
@@ -1043,13 +1103,13 @@ extern "C" int gpupoly_matrix_mul_batch(GpuMatrix *const *outs, const GpuMatrix 
             const size_t total = matrix_polys(out) * L * static_cast<size_t>(ctx->N);
             if (total == 0) continue;
             if (lhss[p0 + j]->cols == 0) {
-                HIP_TRY(hipMemsetAsync(out->data, 0, out->bytes, ctx->stream));
+                HIP_TRY(hipMemsetAsync(words_ptr(out), 0, out->bytes, ctx->stream));
                 continue;
             }
             MulBatchItem &it = args.item[live++];
-            it.c = out->data;
-            it.a = lhss[p0 + j]->data;
-            it.b = rhss[p0 + j]->data;
+            it.c = words_ptr(out);
+            it.a = words_ptr(lhss[p0 + j]);
+            it.b = words_ptr(rhss[p0 + j]);
             it.rows = static_cast<uint32_t>(out->rows);
             it.inner = static_cast<uint32_t>(lhss[p0 + j]->cols);
             it.cols = static_cast<uint32_t>(out->cols);
@@ -1191,9 +1251,9 @@ extern "C" int gpupoly_batch(const GpuBatchOp *ops, size_t count, uint32_t base_
             const size_t words = matrix_words(o.out);
             if (words == 0) continue;
             EwBatchItem &it = args.item[live++];
-            it.out = o.out->data;
-            it.a = o.lhs->data;
-            it.b = b->data;
+            it.out = words_ptr(o.out);
+            it.a = words_ptr(o.lhs);
+            it.b = words_ptr(b);
             it.words = words;
             it.words_per_poly = static_cast<uint32_t>(matrix_limbs(o.out) << logN);
             it.op = (o.kind == GPUPOLY_OP_ADD ? OP_ADD : o.kind == GPUPOLY_OP_SUB ? OP_SUB : o.kind == GPUPOLY_OP_NEG ? OP_NEG : OP_MUL) |
@@ -1240,11 +1300,11 @@ extern "C" int gpu_matrix_equal(const GpuMatrix *lhs, const GpuMatrix *rhs, int 
     unsigned blocks = static_cast<unsigned>(std::min<size_t>((words + 255) / 256, 8192));
     if (ctx->wide)
         MXX_LAUNCH(equal_kernel<uint64_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                           static_cast<const uint64_t *>(lhs->data), static_cast<const uint64_t *>(rhs->data), words,
+                           static_cast<const uint64_t *>(words_ptr(lhs)), static_cast<const uint64_t *>(words_ptr(rhs)), words,
                            static_cast<int *>(flag));
     else
         MXX_LAUNCH(equal_kernel<uint32_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                           static_cast<const uint32_t *>(lhs->data), static_cast<const uint32_t *>(rhs->data), words,
+                           static_cast<const uint32_t *>(words_ptr(lhs)), static_cast<const uint32_t *>(words_ptr(rhs)), words,
                            static_cast<int *>(flag));
     HIP_TRY(hipGetLastError());
     int diff = 0;

@@ -260,6 +260,12 @@ extern "C" int gpupoly_matrix_all_gather_columns(GpuComm *comm, const GpuMatrix 
     for (size_t r = 0; r < n; ++r)
         if (full[r]->cols != cols_total)
             return set_error("gpupoly_matrix_all_gather_columns: output must have the sum of the blocks' columns");
+    // packed blocks go to words on their own streams before any event below is recorded (the calls further down then
+    // find words)
+    for (size_t r = 0; r < n; ++r) {
+        (void)words_ptr(local_blocks[r]);
+        (void)words_ptr(full[r]);
+    }
     const int fmt = local_blocks[0]->format;
     const size_t rows = local_blocks[0]->rows;
     const size_t poly_bytes = matrix_limbs(local_blocks[0]) * static_cast<size_t>(comm->ctxs[0]->N) * comm->ctxs[0]->word_bytes;
@@ -288,8 +294,8 @@ extern "C" int gpupoly_matrix_all_gather_columns(GpuComm *comm, const GpuMatrix 
                 const GpuMatrix *b = local_blocks[p];
                 if (b->cols == 0) continue;
                 if (p != r) HIP_TRY(hipStreamWaitEvent(ctx->stream, comm->ready[p], 0));
-                char *dst = static_cast<char *>(full[r]->data) + col_start[p] * poly_bytes;
-                if (copy_rect(comm, r, p, dst, cols_total * poly_bytes, static_cast<const char *>(b->data), b->cols * poly_bytes,
+                char *dst = static_cast<char *>(words_ptr(full[r])) + col_start[p] * poly_bytes;
+                if (copy_rect(comm, r, p, dst, cols_total * poly_bytes, static_cast<const char *>(words_ptr(b)), b->cols * poly_bytes,
                               b->cols * poly_bytes, rows))
                     return 1;
             }
@@ -316,20 +322,20 @@ extern "C" int gpupoly_matrix_all_gather_columns(GpuComm *comm, const GpuMatrix 
         HIP_TRY(hipSetDevice(ctx->device));
         const GpuMatrix *b = local_blocks[r];
         if (direct) {
-            sendp[r] = b->data;
-            recvp[r] = full[r]->data;
+            sendp[r] = words_ptr(b);
+            recvp[r] = words_ptr(full[r]);
             continue;
         }
         recv[r].reset(new CtxBlock(ctx));
         if (recv[r]->alloc(n * slot_bytes)) return 1;
         recvp[r] = recv[r]->ptr;
         if (b->cols == max_cols) {
-            sendp[r] = b->data;  // a full-width block is its own send buffer
+            sendp[r] = words_ptr(b);  // a full-width block is its own send buffer
         } else {
             send[r].reset(new CtxBlock(ctx));
             if (send[r]->alloc(slot_bytes)) return 1;
             sendp[r] = send[r]->ptr;
-            if (copy_rect(comm, r, r, static_cast<char *>(send[r]->ptr), max_cols * poly_bytes, static_cast<const char *>(b->data),
+            if (copy_rect(comm, r, r, static_cast<char *>(send[r]->ptr), max_cols * poly_bytes, static_cast<const char *>(words_ptr(b)),
                           b->cols * poly_bytes, b->cols * poly_bytes, rows))
                 return 1;
         }
@@ -347,7 +353,7 @@ extern "C" int gpupoly_matrix_all_gather_columns(GpuComm *comm, const GpuMatrix 
             for (size_t p = 0; p < n; ++p) {
                 const size_t c = local_blocks[p]->cols;
                 if (c == 0) continue;
-                char *dst = static_cast<char *>(full[r]->data) + col_start[p] * poly_bytes;
+                char *dst = static_cast<char *>(words_ptr(full[r])) + col_start[p] * poly_bytes;
                 const char *src = static_cast<const char *>(recvp[r]) + p * slot_bytes;
                 if (copy_rect(comm, r, r, dst, cols_total * poly_bytes, src, max_cols * poly_bytes, c * poly_bytes, rows)) return 1;
             }

@@ -51,6 +51,7 @@ struct EnvSwitches {
     int ntt_phase = 0;            // MXX_HIP_NTT_PHASE: phase mask of the forward 2^14 transform, GPUPOLY_PHASE_TIMING builds only (ntt14.h)
     bool serde_general = false;   // MXX_HIP_SERDE=general: compact store always through the kernels that carry the general Garner path (tests, A/B)
     bool rng_compat = false;      // MXX_HIP_RNG_COMPAT=reference: sample_distribution* keyed exactly as the reference's device RNG (sampling.hip)
+    bool pack24 = true;           // MXX_HIP_PACK24=0|off: uniform samples stay in 4-byte words (layout.hip)
     void load();
 };
 
@@ -101,6 +102,21 @@ struct GpuContext {
     // name of the kernel the product dispatcher launched last on this context (a string literal or a function-local
     // static: bench.py labels its roofline with what actually ran, gpupoly_context_last_kernel)
     std::atomic<const char *> last_kernel{""};
+    bool pack24_ok = false;  // 32-bit words, every modulus below 2^24, N % 4 == 0: matrices may hold GPU_MATRIX_LAYOUT_PACKED24
+    // guards every matrix's layout tag and storage swap (layout.hip) and the launches that read packed storage, so that
+    // no thread frees packed bytes another thread is about to hand to a kernel
+    std::mutex layout_mutex;
+};
+
+// the layout tag of a matrix's storage, copyable (local views copy a GpuMatrix) and read without the lock on the fast path
+struct LayoutTag {
+    std::atomic<int> v{GPU_MATRIX_LAYOUT_WORDS};
+    LayoutTag() = default;
+    LayoutTag(const LayoutTag &o) : v(o.v.load(std::memory_order_acquire)) {}
+    LayoutTag &operator=(const LayoutTag &o) {
+        v.store(o.v.load(std::memory_order_acquire), std::memory_order_release);
+        return *this;
+    }
 };
 
 struct GpuMatrix {
@@ -108,9 +124,14 @@ struct GpuMatrix {
     int level = 0;
     size_t rows = 0, cols = 0;
     int format = GPU_POLY_FORMAT_EVAL;
-    void *data = nullptr;  // words [rows*cols][level+1][N]
-    size_t bytes = 0;
+    // words [rows*cols][level+1][N], or with layout PACKED24 [rows*cols][level+1][3N] bytes (residue i at bytes
+    // [3i, 3i+3), little-endian).  Never touched directly: words_ptr() / packed24_ptr() (layout.hip)
+    void *storage = nullptr;
+    size_t bytes = 0;  // of the words layout, whatever the storage holds now
+    LayoutTag layout;
     bool borrowed = false;  // a row-block view of another matrix (gpupoly_matrix_row_view): data is not freed with it
+    GpuMatrix *parent = nullptr;  // row views (gpupoly_matrix_row_view): the matrix whose storage they share
+    int views = 0;                // live row views of this matrix (under ctx->layout_mutex): it is then never packed
 };
 
 struct GpuEventSet {
@@ -222,6 +243,20 @@ inline size_t matrix_polys(const GpuMatrix *m) { return m->rows * m->cols; }
 inline size_t matrix_limbs(const GpuMatrix *m) { return static_cast<size_t>(m->level) + 1; }
 inline size_t matrix_words(const GpuMatrix *m) { return matrix_polys(m) * matrix_limbs(m) * static_cast<size_t>(m->ctx->N); }
 
+// ---- storage layout (layout.hip) -------------------------------------------------------------------
+// the storage as 4-byte / 8-byte words: a PACKED24 matrix is unpacked first, once, on its context's stream (the matrix
+// stays in words afterwards).  Throws on failure (ABI_GUARD turns that into the library's error).
+void *words_ptr(const GpuMatrix *m);
+// m's storage as it is now and (*packed) whether that is PACKED24, for the kernels that read either layout.  The caller
+// holds ctx->layout_mutex from this call until its launch is enqueued (words_ptr must not be called meanwhile).
+const void *packed24_ptr(const GpuMatrix *m, bool *packed);
+inline size_t packed24_bytes(const GpuMatrix *m) { return m->bytes / 4 * 3; }
+// whether a fresh uniform sample into m may be stored PACKED24
+bool pack24_eligible(const GpuMatrix *m);
+// m's words (EVAL after the caller's transform) -> PACKED24 storage in a new block; the words block is freed on the stream.
+// `ntt`: run the forward transform on the way (fused into the 2^14 transform's store where it exists)
+int pack24_store(GpuMatrix *m, bool ntt);
+
 // sampling.hip: fills `out` with samples; keep_coeff leaves them in the coefficient domain
 int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t full_ncol, size_t col_offset, bool keep_coeff);
 
@@ -263,6 +298,8 @@ int launch_intt_oop_u32(GpuContext *ctx, uint32_t *out, const uint32_t *in, size
 int launch_ntt_add_u32(GpuContext *ctx, uint32_t *out, const uint32_t *src, const uint32_t *add, size_t vectors, uint32_t L);
 int launch_mul_intt_u32(GpuContext *ctx, uint32_t *out, const uint32_t *in, const uint32_t *w, size_t vectors, uint32_t L);
 int launch_matmul(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs);
+// forward 2^14 transform of `in` (words) into PACKED24 rows at `out` (3N bytes per vector); -1: no fused kernel here
+int launch_ntt_fwd_pack24_u32(GpuContext *ctx, uint32_t *out, const uint32_t *in, size_t vectors, uint32_t L);
 int launch_matmul_dma_u32(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs);  // -1: shape not supported
 int launch_matmul_dma32_u32(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs);  // 32 slots x 32x32 tile, 16 waves
 int launch_matmul_mfma_u32(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs);  // -1: shape / moduli not supported

@@ -112,11 +112,11 @@ static int fill_gadget_impl(GpuMatrix *out, uint32_t base_bits, bool small) {
     const dim3 blocks = item_grid(total, 256);
     if (ctx->wide)
         MXX_LAUNCH(fill_gadget_kernel<uint64_t>, blocks, dim3(256), 0, ctx->stream,
-                           static_cast<uint64_t *>(out->data), ctx->d_limbs, out->rows, out->cols, (uint32_t)L,
+                           static_cast<uint64_t *>(words_ptr(out)), ctx->d_limbs, out->rows, out->cols, (uint32_t)L,
                            (uint32_t)ctx->N, dpt, k, base_bits, small ? 1 : 0);
     else
         MXX_LAUNCH(fill_gadget_kernel<uint32_t>, blocks, dim3(256), 0, ctx->stream,
-                           static_cast<uint32_t *>(out->data), ctx->d_limbs, out->rows, out->cols, (uint32_t)L,
+                           static_cast<uint32_t *>(words_ptr(out)), ctx->d_limbs, out->rows, out->cols, (uint32_t)L,
                            (uint32_t)ctx->N, dpt, k, base_bits, small ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -142,15 +142,15 @@ static int decompose_impl(const GpuMatrix *src, uint32_t base_bits, GpuMatrix *o
     }
     if (ctx_activate(ctx)) return 1;
     // digits are taken from coefficient-domain residues: INTT a private copy if needed
-    const void *coeff = src->data;
+    const void *coeff = words_ptr(src);
     CtxBlock tmp_block(ctx);  // back to the cache at scope exit (stream-ordered behind its readers), error paths included
     if (src->format == GPU_POLY_FORMAT_EVAL) {
         if (tmp_block.alloc(src->bytes)) return 1;
-        int rc = ctx->wide ? -1 : launch_intt_oop_u32(ctx, static_cast<uint32_t *>(tmp_block.ptr), static_cast<const uint32_t *>(src->data),
+        int rc = ctx->wide ? -1 : launch_intt_oop_u32(ctx, static_cast<uint32_t *>(tmp_block.ptr), static_cast<const uint32_t *>(words_ptr(src)),
                                                       polys * L, static_cast<uint32_t>(L));
         if (rc < 0) {  // no out-of-place transform for this context: copy, then in place
             MXX_TRACED_COPY("copy (device to device)", ctx->stream, 2.0 * src->bytes,
-                            HIP_TRY(hipMemcpyAsync(tmp_block.ptr, src->data, src->bytes, hipMemcpyDeviceToDevice, ctx->stream)));
+                            HIP_TRY(hipMemcpyAsync(tmp_block.ptr, words_ptr(src), src->bytes, hipMemcpyDeviceToDevice, ctx->stream)));
             rc = launch_ntt(ctx, tmp_block.ptr, polys * L, static_cast<int>(L), true);
         }
         if (rc) return rc;
@@ -159,10 +159,10 @@ static int decompose_impl(const GpuMatrix *src, uint32_t base_bits, GpuMatrix *o
     const uint32_t towers = small ? 1u : static_cast<uint32_t>(L);
     if (requested == GPU_POLY_FORMAT_EVAL) {
         // digits generated inside the forward transform's load: no COEFF digit matrix is written
-        const int frc = ctx->wide ? launch_ntt_digits_u64(ctx, static_cast<uint64_t *>(out->data), static_cast<const uint64_t *>(coeff),
+        const int frc = ctx->wide ? launch_ntt_digits_u64(ctx, static_cast<uint64_t *>(words_ptr(out)), static_cast<const uint64_t *>(coeff),
                                                           matrix_polys(out) * L, static_cast<uint32_t>(L), (uint32_t)src->cols,
                                                           towers, dpt, base_bits, k)
-                                  : launch_ntt_digits_u32(ctx, static_cast<uint32_t *>(out->data), static_cast<const uint32_t *>(coeff),
+                                  : launch_ntt_digits_u32(ctx, static_cast<uint32_t *>(words_ptr(out)), static_cast<const uint32_t *>(coeff),
                                                           matrix_polys(out) * L, static_cast<uint32_t>(L), (uint32_t)src->cols,
                                                           towers, dpt, base_bits, k);
         if (frc >= 0) {
@@ -174,17 +174,17 @@ static int decompose_impl(const GpuMatrix *src, uint32_t base_bits, GpuMatrix *o
     const dim3 blocks = item_grid(total, 256);
     if (ctx->wide)
         MXX_LAUNCH(decompose_kernel<uint64_t>, blocks, dim3(256), 0, ctx->stream,
-                           static_cast<uint64_t *>(out->data), static_cast<const uint64_t *>(coeff), ctx->d_limbs, polys,
+                           static_cast<uint64_t *>(words_ptr(out)), static_cast<const uint64_t *>(coeff), ctx->d_limbs, polys,
                            (uint32_t)src->cols, (uint32_t)L, (uint32_t)ctx->N, towers, dpt, base_bits, k);
     else
         MXX_LAUNCH(decompose_kernel<uint32_t>, blocks, dim3(256), 0, ctx->stream,
-                           static_cast<uint32_t *>(out->data), static_cast<const uint32_t *>(coeff), ctx->d_limbs, polys,
+                           static_cast<uint32_t *>(words_ptr(out)), static_cast<const uint32_t *>(coeff), ctx->d_limbs, polys,
                            (uint32_t)src->cols, (uint32_t)L, (uint32_t)ctx->N, towers, dpt, base_bits, k);
     HIP_TRY(hipGetLastError());
     out->format = GPU_POLY_FORMAT_COEFF;
     if (requested == GPU_POLY_FORMAT_EVAL) {
         // output honours the format it was created with (MatrixDecompose.cu:910-914,1318-1328)
-        int rc = launch_ntt(ctx, out->data, matrix_polys(out) * L, static_cast<int>(L), false);
+        int rc = launch_ntt(ctx, words_ptr(out), matrix_polys(out) * L, static_cast<int>(L), false);
         if (rc) return rc;
         out->format = GPU_POLY_FORMAT_EVAL;
     }
@@ -234,17 +234,17 @@ extern "C" int gpu_matrix_fill_small_decomposed_identity_chunk(GpuMatrix *out, c
     if (size > 65535) return set_error("gpu_matrix_fill_small_decomposed_identity_chunk: size too large");
     GpuContext *ctx = out->ctx;
     if (ctx_activate(ctx)) return 1;
-    HIP_TRY(hipMemsetAsync(out->data, 0, out->bytes, ctx->stream));
+    HIP_TRY(hipMemsetAsync(words_ptr(out), 0, out->bytes, ctx->stream));
     const size_t wpp = matrix_limbs(out) * static_cast<size_t>(ctx->N);
     const unsigned gx = static_cast<unsigned>(std::min<size_t>((wpp + 255) / 256, 64));
     dim3 grid(gx, static_cast<unsigned>(size));
     if (ctx->wide)
         MXX_LAUNCH(identity_chunk_kernel<uint64_t>, grid, dim3(256), 0, ctx->stream,
-                           static_cast<uint64_t *>(out->data), static_cast<const uint64_t *>(scalar_by_digit->data),
+                           static_cast<uint64_t *>(words_ptr(out)), static_cast<const uint64_t *>(words_ptr(scalar_by_digit)),
                            size, chunk_idx, chunk_count, wpp);
     else
         MXX_LAUNCH(identity_chunk_kernel<uint32_t>, grid, dim3(256), 0, ctx->stream,
-                           static_cast<uint32_t *>(out->data), static_cast<const uint32_t *>(scalar_by_digit->data),
+                           static_cast<uint32_t *>(words_ptr(out)), static_cast<const uint32_t *>(words_ptr(scalar_by_digit)),
                            size, chunk_idx, chunk_count, wpp);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -279,7 +279,8 @@ extern "C" int gpupoly_matrix_sample_decomposed(GpuMatrix *out, int dist_type, d
     if (ctx_activate(ctx)) return 1;
     CtxBlock block(ctx);
     if (block.alloc(src.bytes)) return 1;
-    src.data = block.ptr;
+    src.storage = block.ptr;
+    src.borrowed = true;  // the block is this scope's: never swapped for packed storage
     int rc = sample_impl(&src, dist_type, sigma, seed, src.cols, 0, true);
     if (rc == 0) rc = decompose_impl(&src, base_bits, out, small != 0);
     return rc;

@@ -246,8 +246,8 @@ int launch_matmul_mfma_u32(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix
     ctx->last_kernel = "mmfma::kernel_u32 (16 slots x 32x32 tile, 9 v_mfma_i32_32x32x32_i8 per 32-deep chunk on balanced int8 digits)";
 #define MMFMA_LAUNCH(M)                                                                                                   \
     MXX_LAUNCH(mmfma::kernel_u32<M>, dim3(static_cast<unsigned>(blocks)), dim3(mmfma::THREADS), mmfma::LDS_BYTES, \
-                       ctx->stream, static_cast<uint32_t *>(out->data), static_cast<const uint32_t *>(lhs->data),          \
-                       static_cast<const uint32_t *>(rhs->data), ctx->d_limbs, rows, inner, cols, L, N, row_tiles,        \
+                       ctx->stream, static_cast<uint32_t *>(words_ptr(out)), static_cast<const uint32_t *>(words_ptr(lhs)),          \
+                       static_cast<const uint32_t *>(words_ptr(rhs)), ctx->d_limbs, rows, inner, cols, L, N, row_tiles,        \
                        col_tiles, slot_chunks, remap)
 #ifdef GPUPOLY_PHASE_TIMING
     // phase-timing builds of the same kernel for tools/time_mfma_phases.py (make PHASE_TIMING=1): modes 1 and 2 skip

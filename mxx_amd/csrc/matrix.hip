@@ -146,10 +146,10 @@ int launch_scatter_i64(GpuMatrix *out, const int64_t *vals) {
     MXX_TRACE_BYTES(static_cast<double>(total) * 8 + out->bytes);  // int64 staging read, residues of every limb written
     if (ctx->wide)
         MXX_LAUNCH(scatter_i64_kernel<uint64_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                           static_cast<uint64_t *>(out->data), vals, ctx->d_limbs, polys, L, (uint32_t)ctx->N);
+                           static_cast<uint64_t *>(words_ptr(out)), vals, ctx->d_limbs, polys, L, (uint32_t)ctx->N);
     else
         MXX_LAUNCH(scatter_i64_kernel<uint32_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                           static_cast<uint32_t *>(out->data), vals, ctx->d_limbs, polys, L, (uint32_t)ctx->N);
+                           static_cast<uint32_t *>(words_ptr(out)), vals, ctx->d_limbs, polys, L, (uint32_t)ctx->N);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -173,8 +173,8 @@ int launch_copy_block(GpuMatrix *out, const GpuMatrix *src, size_t dst_row, size
     size_t wpp = matrix_limbs(out) * static_cast<size_t>(ctx->N);
     if (!add) {
         size_t wb = static_cast<size_t>(ctx->word_bytes);
-        const char *s = static_cast<const char *>(src->data) + (src_row * src->cols + src_col) * wpp * wb;
-        char *d = static_cast<char *>(out->data) + (dst_row * out->cols + dst_col) * wpp * wb;
+        const char *s = static_cast<const char *>(words_ptr(src)) + (src_row * src->cols + src_col) * wpp * wb;
+        char *d = static_cast<char *>(words_ptr(out)) + (dst_row * out->cols + dst_col) * wpp * wb;
         if (out == src) {
             // overlapping self-copy: go through the kernel only when disjoint is not guaranteed
             // (hipMemcpy2D has undefined overlap semantics); use a temp
@@ -211,12 +211,12 @@ int launch_copy_block(GpuMatrix *out, const GpuMatrix *src, size_t dst_row, size
         MXX_TRACE_BYTES(3.0 * rr * cols * wpp * ctx->word_bytes);  // destination block read + written, source block read
         if (ctx->wide)
             MXX_LAUNCH((block_rect_kernel<uint64_t, true>), grid, dim3(256), 0, ctx->stream,
-                               static_cast<uint64_t *>(out->data), static_cast<const uint64_t *>(src->data),
+                               static_cast<uint64_t *>(words_ptr(out)), static_cast<const uint64_t *>(words_ptr(src)),
                                ctx->d_limbs, out->cols, src->cols, dst_row + r0, dst_col, src_row + r0, src_col, cols,
                                wpp, (uint32_t)ctx->N);
         else
             MXX_LAUNCH((block_rect_kernel<uint32_t, true>), grid, dim3(256), 0, ctx->stream,
-                               static_cast<uint32_t *>(out->data), static_cast<const uint32_t *>(src->data),
+                               static_cast<uint32_t *>(words_ptr(out)), static_cast<const uint32_t *>(words_ptr(src)),
                                ctx->d_limbs, out->cols, src->cols, dst_row + r0, dst_col, src_row + r0, src_col, cols,
                                wpp, (uint32_t)ctx->N);
         HIP_TRY(hipGetLastError());
@@ -242,7 +242,7 @@ extern "C" int gpu_matrix_create(GpuContext *ctx, int level, size_t rows, size_t
     m->format = format;
     m->bytes = matrix_words(m) * static_cast<size_t>(ctx->word_bytes);
     if (m->bytes) {
-        if (ctx_alloc(ctx, m->bytes, &m->data)) {
+        if (ctx_alloc(ctx, m->bytes, &m->storage)) {
             delete m;
             return 1;
         }
@@ -260,11 +260,18 @@ extern "C" int gpupoly_matrix_row_view(GpuMatrix *m, size_t row, size_t rows, Gp
     if (!m || !out_view) return set_error("gpupoly_matrix_row_view: null argument");
     if (row > m->rows || rows > m->rows - row) return set_error("gpupoly_matrix_row_view: row block out of range");
     const size_t poly_bytes = matrix_limbs(m) * static_cast<size_t>(m->ctx->N) * m->ctx->word_bytes;
+    char *base = static_cast<char *>(words_ptr(m));  // a view shares words: a packed parent is unpacked first
     GpuMatrix *v = new GpuMatrix(*m);
     v->rows = rows;
-    v->data = rows && m->cols ? static_cast<char *>(m->data) + row * m->cols * poly_bytes : nullptr;
+    v->storage = rows && m->cols ? base + row * m->cols * poly_bytes : nullptr;
     v->bytes = rows * m->cols * poly_bytes;
     v->borrowed = true;
+    v->views = 0;
+    v->parent = m;
+    {
+        std::lock_guard<std::mutex> lk(m->ctx->layout_mutex);
+        ++m->views;
+    }
     *out_view = v;
     return 0;
     ABI_GUARD_END
@@ -272,9 +279,13 @@ extern "C" int gpupoly_matrix_row_view(GpuMatrix *m, size_t row, size_t rows, Gp
 
 extern "C" void gpu_matrix_destroy(GpuMatrix *mat) {
     if (!mat) return;
-    if (mat->data && !mat->borrowed) {
+    if (mat->parent) {
+        std::lock_guard<std::mutex> lk(mat->ctx->layout_mutex);
+        --mat->parent->views;
+    }
+    if (mat->storage && !mat->borrowed) {
         (void)hipSetDevice(mat->ctx->device);
-        ctx_free(mat->ctx, mat->data);  // stream-ordered: in-flight kernels finish first
+        ctx_free(mat->ctx, mat->storage);  // stream-ordered: in-flight kernels finish first
     }
     delete mat;
 }
@@ -286,7 +297,7 @@ extern "C" int gpu_matrix_copy(GpuMatrix *dst, const GpuMatrix *src) {
     if (dst->bytes == 0 || dst == src) return 0;
     if (ctx_activate(dst->ctx)) return 1;
     MXX_TRACED_COPY("copy (device to device)", dst->ctx->stream, 2.0 * dst->bytes,
-                    HIP_TRY(hipMemcpyAsync(dst->data, src->data, dst->bytes, hipMemcpyDeviceToDevice, dst->ctx->stream)));
+                    HIP_TRY(hipMemcpyAsync(words_ptr(dst), words_ptr(src), dst->bytes, hipMemcpyDeviceToDevice, dst->ctx->stream)));
     return 0;
     ABI_GUARD_END
 }
@@ -322,13 +333,13 @@ extern "C" int gpupoly_matrix_transpose(GpuMatrix *out, const GpuMatrix *src) {
     if (poly_bytes % 16 != 0 || src->rows == 1 || src->cols == 1) {
         // a vector's transpose is the same bytes; tiny rings (N * word < 16 bytes) go entry by entry
         if (src->rows == 1 || src->cols == 1) {
-            HIP_TRY(hipMemcpyAsync(out->data, src->data, src->bytes, hipMemcpyDeviceToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(words_ptr(out), words_ptr(src), src->bytes, hipMemcpyDeviceToDevice, ctx->stream));
             return 0;
         }
         for (size_t r = 0; r < src->rows; ++r)
             for (size_t c = 0; c < src->cols; ++c)
-                HIP_TRY(hipMemcpyAsync(static_cast<char *>(out->data) + (c * src->rows + r) * poly_bytes,
-                                       static_cast<const char *>(src->data) + (r * src->cols + c) * poly_bytes, poly_bytes,
+                HIP_TRY(hipMemcpyAsync(static_cast<char *>(words_ptr(out)) + (c * src->rows + r) * poly_bytes,
+                                       static_cast<const char *>(words_ptr(src)) + (r * src->cols + c) * poly_bytes, poly_bytes,
                                        hipMemcpyDeviceToDevice, ctx->stream));
         return 0;
     }
@@ -337,7 +348,7 @@ extern "C" int gpupoly_matrix_transpose(GpuMatrix *out, const GpuMatrix *src) {
     const size_t gy = std::min<size_t>(polys, 65535), gz = (polys + gy - 1) / gy;
     if (gz > 65535) return set_error("gpupoly_matrix_transpose: matrix too large");
     MXX_LAUNCH(transpose_kernel, dim3(gx, static_cast<unsigned>(gy), static_cast<unsigned>(gz)), dim3(256), 0, ctx->stream,
-                       static_cast<uint4 *>(out->data), static_cast<const uint4 *>(src->data), src->rows, src->cols, vec_per_poly);
+                       static_cast<uint4 *>(words_ptr(out)), static_cast<const uint4 *>(words_ptr(src)), src->rows, src->cols, vec_per_poly);
     HIP_TRY(hipGetLastError());
     return 0;
     ABI_GUARD_END
@@ -421,7 +432,7 @@ static int column_blocks(GpuMatrix *whole, GpuMatrix *const *blocks, size_t n, b
         while (j < n && cb.count < COLUMN_BLOCKS_MAX) {
             if (blocks[j]->cols) {
                 cb.start[cb.count] = static_cast<uint32_t>(at);
-                cb.ptr[cb.count] = blocks[j]->data;
+                cb.ptr[cb.count] = words_ptr(blocks[j]);
                 ++cb.count;
                 at += blocks[j]->cols;
             }
@@ -436,10 +447,10 @@ static int column_blocks(GpuMatrix *whole, GpuMatrix *const *blocks, size_t n, b
         MXX_TRACE_BYTES(2.0 * static_cast<double>(entries) * poly_bytes);
         if (split)
             MXX_LAUNCH(column_blocks_kernel<true>, dim3(gx, static_cast<unsigned>(gy), static_cast<unsigned>(gz)), dim3(256), 0, ctx->stream,
-                       static_cast<uint4 *>(whole->data), cb, whole->rows, whole->cols, vec_per_poly);
+                       static_cast<uint4 *>(words_ptr(whole)), cb, whole->rows, whole->cols, vec_per_poly);
         else
             MXX_LAUNCH(column_blocks_kernel<false>, dim3(gx, static_cast<unsigned>(gy), static_cast<unsigned>(gz)), dim3(256), 0, ctx->stream,
-                       static_cast<uint4 *>(whole->data), cb, whole->rows, whole->cols, vec_per_poly);
+                       static_cast<uint4 *>(words_ptr(whole)), cb, whole->rows, whole->cols, vec_per_poly);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -468,7 +479,7 @@ extern "C" int gpupoly_matrix_fill_zero(GpuMatrix *out) {
     if (!out) return set_error("gpupoly_matrix_fill_zero: null matrix");
     if (out->bytes == 0) return 0;
     if (ctx_activate(out->ctx)) return 1;
-    HIP_TRY(hipMemsetAsync(out->data, 0, out->bytes, out->ctx->stream));
+    HIP_TRY(hipMemsetAsync(words_ptr(out), 0, out->bytes, out->ctx->stream));
     return 0;
     ABI_GUARD_END
 }
@@ -498,24 +509,32 @@ extern "C" int gpupoly_matrix_fill_identity(GpuMatrix *out, const GpuMatrix *sca
     GpuContext *ctx = out->ctx;
     if (ctx_activate(ctx)) return 1;
     if (out->rows > 65535) return set_error("gpupoly_matrix_fill_identity: matrix too large");
-    HIP_TRY(hipMemsetAsync(out->data, 0, out->bytes, ctx->stream));
+    HIP_TRY(hipMemsetAsync(words_ptr(out), 0, out->bytes, ctx->stream));
     const size_t words = matrix_limbs(out) * static_cast<size_t>(ctx->N);
     const dim3 grid(static_cast<unsigned>(std::min<size_t>((words + 255) / 256, 256)), static_cast<unsigned>(out->rows));
     if (ctx->wide)
-        MXX_LAUNCH(fill_diagonal_kernel<uint64_t>, grid, dim3(256), 0, ctx->stream, static_cast<uint64_t *>(out->data),
-                           scalar ? static_cast<const uint64_t *>(scalar->data) : nullptr, out->rows, words);
+        MXX_LAUNCH(fill_diagonal_kernel<uint64_t>, grid, dim3(256), 0, ctx->stream, static_cast<uint64_t *>(words_ptr(out)),
+                           scalar ? static_cast<const uint64_t *>(words_ptr(scalar)) : nullptr, out->rows, words);
     else
-        MXX_LAUNCH(fill_diagonal_kernel<uint32_t>, grid, dim3(256), 0, ctx->stream, static_cast<uint32_t *>(out->data),
-                           scalar ? static_cast<const uint32_t *>(scalar->data) : nullptr, out->rows, words);
+        MXX_LAUNCH(fill_diagonal_kernel<uint32_t>, grid, dim3(256), 0, ctx->stream, static_cast<uint32_t *>(words_ptr(out)),
+                           scalar ? static_cast<const uint32_t *>(words_ptr(scalar)) : nullptr, out->rows, words);
     HIP_TRY(hipGetLastError());
     return 0;
     ABI_GUARD_END
 }
 
 extern "C" int gpupoly_matrix_device_ptr(const GpuMatrix *mat, void **out_ptr, size_t *out_bytes) {
+    ABI_GUARD_BEGIN
     if (!mat || !out_ptr || !out_bytes) return set_error("gpupoly_matrix_device_ptr: null argument");
-    *out_ptr = mat->data;
+    *out_ptr = words_ptr(mat);
     *out_bytes = mat->bytes;
+    return 0;
+    ABI_GUARD_END
+}
+
+extern "C" int gpupoly_matrix_layout(const GpuMatrix *mat, int *out) {
+    if (!mat || !out) return set_error("gpupoly_matrix_layout: null argument");
+    *out = mat->layout.v.load(std::memory_order_acquire);
     return 0;
 }
 
@@ -542,6 +561,7 @@ extern "C" int gpupoly_matrix_copy_to_context(GpuContext *dst_ctx, const GpuMatr
         *out = dst;
         return 0;
     }
+    const void *src_words = words_ptr(src);  // a packed source is unpacked on its stream before `ready` is recorded
     hipEvent_t ready = nullptr, done = nullptr;
     auto fail = [&](hipError_t e, const char *what) {
         if (ready) (void)hipEventDestroy(ready);
@@ -571,8 +591,8 @@ extern "C" int gpupoly_matrix_copy_to_context(GpuContext *dst_ctx, const GpuMatr
     e = hipStreamWaitEvent(dst_ctx->stream, ready, 0);
     if (e == hipSuccess) {
         e = dst_ctx->device == sctx->device
-                ? hipMemcpyAsync(dst->data, src->data, src->bytes, hipMemcpyDeviceToDevice, dst_ctx->stream)
-                : hipMemcpyPeerAsync(dst->data, dst_ctx->device, src->data, sctx->device, src->bytes, dst_ctx->stream);
+                ? hipMemcpyAsync(words_ptr(dst), src_words, src->bytes, hipMemcpyDeviceToDevice, dst_ctx->stream)
+                : hipMemcpyPeerAsync(words_ptr(dst), dst_ctx->device, src_words, sctx->device, src->bytes, dst_ctx->stream);
     }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventRecord(done, dst_ctx->stream);
@@ -650,11 +670,11 @@ extern "C" int gpu_matrix_load_rns_batch(GpuMatrix *mat, const uint8_t *bytes, s
         unsigned blocks = grid_for(total, 256);
         if (ctx->wide)
             MXX_LAUNCH(unpack_rns_kernel<uint64_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                               static_cast<const uint64_t *>(stage), static_cast<uint64_t *>(mat->data) + p0 * wpp,
+                               static_cast<const uint64_t *>(stage), static_cast<uint64_t *>(words_ptr(mat)) + p0 * wpp,
                                wpp, src_wpp, total);
         else
             MXX_LAUNCH(unpack_rns_kernel<uint32_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                               static_cast<const uint64_t *>(stage), static_cast<uint32_t *>(mat->data) + p0 * wpp,
+                               static_cast<const uint64_t *>(stage), static_cast<uint32_t *>(words_ptr(mat)) + p0 * wpp,
                                wpp, src_wpp, total);
         HIP_TRY(hipGetLastError());
     }
@@ -693,11 +713,11 @@ extern "C" int gpu_matrix_store_rns_batch(const GpuMatrix *mat, uint8_t *bytes_o
         unsigned blocks = grid_for(total, 256);
         if (ctx->wide)
             MXX_LAUNCH(pack_rns_kernel<uint64_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                               static_cast<const uint64_t *>(mat->data) + p0 * wpp, static_cast<uint64_t *>(stage), wpp,
+                               static_cast<const uint64_t *>(words_ptr(mat)) + p0 * wpp, static_cast<uint64_t *>(stage), wpp,
                                wpp, total);
         else
             MXX_LAUNCH(pack_rns_kernel<uint32_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                               static_cast<const uint32_t *>(mat->data) + p0 * wpp, static_cast<uint64_t *>(stage), wpp,
+                               static_cast<const uint32_t *>(words_ptr(mat)) + p0 * wpp, static_cast<uint64_t *>(stage), wpp,
                                wpp, total);
         HIP_TRY(hipGetLastError());
         if (bytes_per_poly == tight)
@@ -733,11 +753,11 @@ extern "C" int gpu_matrix_store_const_coeff_batch(const GpuMatrix *mat, uint64_t
     const dim3 blocks = item_grid(polys * L, 256);
     if (ctx->wide)
         MXX_LAUNCH(const_coeff_kernel<uint64_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                           static_cast<const uint64_t *>(mat->data), static_cast<uint64_t *>(stage), polys, L,
+                           static_cast<const uint64_t *>(words_ptr(mat)), static_cast<uint64_t *>(stage), polys, L,
                            (size_t)ctx->N, L);
     else
         MXX_LAUNCH(const_coeff_kernel<uint32_t>, dim3(blocks), dim3(256), 0, ctx->stream,
-                           static_cast<const uint32_t *>(mat->data), static_cast<uint64_t *>(stage), polys, L,
+                           static_cast<const uint32_t *>(words_ptr(mat)), static_cast<uint64_t *>(stage), polys, L,
                            (size_t)ctx->N, L);
     HIP_TRY(hipGetLastError());
     if (words_per_poly == L) HIP_TRY(hipMemcpyAsync(words_out, stage, bytes, hipMemcpyDeviceToHost, ctx->stream));

@@ -198,7 +198,7 @@ extern "C" int gpu_matrix_ntt_all(GpuMatrix *mat) {
     if (!mat) return set_error("gpu_matrix_ntt_all: null matrix");
     if (mat->format == GPU_POLY_FORMAT_EVAL) return 0;
     if (ctx_activate(mat->ctx)) return 1;
-    int rc = launch_ntt(mat->ctx, mat->data, matrix_polys(mat) * matrix_limbs(mat), mat->level + 1, false);
+    int rc = launch_ntt(mat->ctx, words_ptr(mat), matrix_polys(mat) * matrix_limbs(mat), mat->level + 1, false);
     if (rc) return rc;
     mat->format = GPU_POLY_FORMAT_EVAL;
     return 0;
@@ -210,7 +210,7 @@ extern "C" int gpu_matrix_intt_all(GpuMatrix *mat) {
     if (!mat) return set_error("gpu_matrix_intt_all: null matrix");
     if (mat->format == GPU_POLY_FORMAT_COEFF) return 0;
     if (ctx_activate(mat->ctx)) return 1;
-    int rc = launch_ntt(mat->ctx, mat->data, matrix_polys(mat) * matrix_limbs(mat), mat->level + 1, true);
+    int rc = launch_ntt(mat->ctx, words_ptr(mat), matrix_polys(mat) * matrix_limbs(mat), mat->level + 1, true);
     if (rc) return rc;
     mat->format = GPU_POLY_FORMAT_COEFF;
     return 0;
@@ -237,8 +237,8 @@ extern "C" int gpupoly_matrix_mul_scalar_intt(GpuMatrix *out, const GpuMatrix *l
     if (ctx_activate(ctx)) return 1;
     int rc = -1;
     if (!ctx->wide)
-        rc = launch_mul_intt_u32(ctx, static_cast<uint32_t *>(out->data), static_cast<const uint32_t *>(lhs->data),
-                                 static_cast<const uint32_t *>(scalar->data), matrix_polys(out) * matrix_limbs(out),
+        rc = launch_mul_intt_u32(ctx, static_cast<uint32_t *>(words_ptr(out)), static_cast<const uint32_t *>(words_ptr(lhs)),
+                                 static_cast<const uint32_t *>(words_ptr(scalar)), matrix_polys(out) * matrix_limbs(out),
                                  static_cast<uint32_t>(matrix_limbs(out)));
     if (rc < 0) {
         rc = gpu_matrix_mul_scalar(out, lhs, scalar);

@@ -64,11 +64,29 @@ __device__ __forceinline__ void wave_sync() {
 // stores sit 32 bytes apart: each instruction half-fills 64 lines, and the two halves of a line reach the memory side as
 // separate partial writes when the store is non-temporal (streams of 1 GiB and more, the digit transforms of a
 // decomposition): "stores only" ran at 1.7 TB/s there (tools/ab_ntt_phases.sh).
-template <typename W, bool TIGHT, bool NTS, typename Load, bool ADD = false, bool COAL = false, bool NOTW = false>
+// PK: g is a PACKED24 row (layout.hip) instead of a vector of words: every 4 finished residues go out as 3 words at
+// word 3 e / 4 of the row (fwd_pack24_kernel)
+template <bool NTS>
+__device__ __forceinline__ void store_packed4(uint32_t *row, uint32_t e, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3) {
+    uint32_t *p = row + (e >> 2) * 3;
+    const uint32_t w0 = r0 | (r1 << 24), w1 = (r1 >> 8) | (r2 << 16), w2 = (r2 >> 16) | (r3 << 8);
+    if constexpr (NTS) {
+        __builtin_nontemporal_store(w0, p);
+        __builtin_nontemporal_store(w1, p + 1);
+        __builtin_nontemporal_store(w2, p + 2);
+    } else {
+        p[0] = w0;
+        p[1] = w1;
+        p[2] = w2;
+    }
+}
+
+template <typename W, bool TIGHT, bool NTS, typename Load, bool ADD = false, bool COAL = false, bool NOTW = false, bool PK = false>
 __device__ __forceinline__ void fwd_body(W *g, const Load load, const TwPair<W> *__restrict__ tw_all,
                                          const LimbConst &lc, uint32_t limb, const W *__restrict__ addv = nullptr,
                                          uint32_t phase = 0) {
     (void)phase;
+    static_assert(!PK || (sizeof(W) == 4 && !ADD), "packed rows hold 32-bit residues");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     W *xs = reinterpret_cast<W *>(smem);  // [2][8][BLK_PAD]
     constexpr int VN = 16 / sizeof(W);
@@ -155,6 +173,10 @@ __device__ __forceinline__ void fwd_body(W *g, const Load load, const TwPair<W> 
                 for (int c = 0; c < CH; ++c) {
                     const uint32_t pos = c * 64 * VN + VN * lane;  // VN consecutive words never straddle a padding step (32 words)
                     wx t = *reinterpret_cast<const wx *>(&xb[pad64(pos)]);
+                    if constexpr (PK) {
+                        store_packed4<NTS>(reinterpret_cast<uint32_t *>(g), B * BLK + pos, t[0], t[1], t[2], t[3]);
+                        continue;
+                    }
                     W *dstc = g + B * BLK + pos;
                     if constexpr (ADD) {
                         const wx a = __builtin_nontemporal_load(reinterpret_cast<const wx *>(addv + B * BLK + pos));
@@ -175,6 +197,10 @@ __device__ __forceinline__ void fwd_body(W *g, const Load load, const TwPair<W> 
                 wx t;
 #pragma unroll
                 for (int e = 0; e < VN; ++e) t[e] = v[m + e];
+                if constexpr (PK) {
+                    store_packed4<NTS>(reinterpret_cast<uint32_t *>(g), B * BLK + 8 * lane + m, t[0], t[1], t[2], t[3]);
+                    continue;
+                }
                 if constexpr (ADD) {
                     const wx a = __builtin_nontemporal_load(reinterpret_cast<const wx *>(addv + B * BLK + 8 * lane + m));
 #pragma unroll
@@ -225,6 +251,19 @@ __global__ void __launch_bounds__(512, 8 / (sizeof(W) / 4))
     // non-temporal streams (1 GiB and more) store through the coalescing LDS trip: see COAL
     fwd_body<W, TIGHT, NT, LoadVector<W, NT>, false, NT>(g, LoadVector<W, NT>{g}, tw_all, lc, limb);
 #endif
+}
+
+// out = NTT(in) as PACKED24 rows (layout.hip), out of place: a uniform sample's transform writes 3 bytes per residue
+// (3N / 4 words per vector).  Moduli below 2^24, so never TIGHT.  NT as fwd_kernel (COAL with it).
+template <bool NT = false>
+__global__ void __launch_bounds__(512, 8)
+    fwd_pack24_kernel(uint32_t *__restrict__ out, const uint32_t *__restrict__ in, const TwPair<uint32_t> *__restrict__ tw_all,
+                      const LimbConst *__restrict__ limbs, uint32_t L) {
+    const uint32_t limb = blockIdx.x;
+    const size_t vec = (static_cast<size_t>(blockIdx.z) * gridDim.y + blockIdx.y) * L + limb;
+    const LimbConst lc = limbs[limb];
+    fwd_body<uint32_t, false, NT, LoadVector<uint32_t, NT>, false, NT, false, true>(
+        out + vec * (N / 4 * 3), LoadVector<uint32_t, NT>{in + vec * N}, tw_all, lc, limb);
 }
 
 // out = NTT(src) + add, out of place: the preimage's x = [.. ; p2 + z] takes the G-sampler's coefficient digits, the

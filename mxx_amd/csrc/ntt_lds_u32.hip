@@ -29,6 +29,23 @@ int launch_intt_oop_u32(GpuContext *ctx, uint32_t *out, const uint32_t *in, size
     return ctx->lazy_ok ? launch_ntt14<false>(ctx, out, vectors, L, true, in) : launch_ntt14<true>(ctx, out, vectors, L, true, in);
 }
 
+// out = NTT(in) as PACKED24 rows in one pass (ntt14.h, fwd_pack24_kernel; layout.hip); -1: no fused kernel for this
+// context / path override, the caller then transforms in place and packs
+int launch_ntt_fwd_pack24_u32(GpuContext *ctx, uint32_t *out, const uint32_t *in, size_t vectors, uint32_t L) {
+    const EnvSwitches &env = ctx->env;
+    if (ctx->logN != 14 || !ctx->lazy_ok || env.ntt14 == 1 || env.ntt_path > 1 || env.ntt_phase) return -1;
+    dim3 grid, block(ntt14::T);
+    if (vectors == 0 || vectors > 0x7fffffffull || !ntt14_grid(vectors, L, grid)) return -1;
+    const size_t lds = ntt14::lds_bytes(sizeof(W));
+    const TwPair<W> *tw = static_cast<const TwPair<W> *>(ctx->d_tw2_fwd);
+    const bool nt = (vectors << 14) * sizeof(W) >= (size_t(1) << 30);  // as launch_ntt14
+    MXX_TRACE_BYTES(1.75 * vectors * ntt14::N * sizeof(W));  // words read, 3 bytes per residue written
+    if (nt) MXX_LAUNCH((ntt14::fwd_pack24_kernel<true>), grid, block, lds, ctx->stream, out, in, tw, ctx->d_limbs, L);
+    else MXX_LAUNCH((ntt14::fwd_pack24_kernel<false>), grid, block, lds, ctx->stream, out, in, tw, ctx->d_limbs, L);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // out = NTT(src) + add in one pass (ntt14.h, fwd_add_kernel); -1: no fused kernel for this context / path override,
 // the caller then copies, transforms in place and adds
 int launch_ntt_add_u32(GpuContext *ctx, uint32_t *out, const uint32_t *src, const uint32_t *add, size_t vectors, uint32_t L) {

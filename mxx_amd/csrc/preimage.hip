@@ -129,11 +129,11 @@ static int launch_gather_sub(GpuContext *ctx, GpuMatrix *out, const GpuMatrix *a
     if (!poly_grid(entries, wpp, vn, grid)) return set_error("gpupoly_trapdoor_preimage_many: matrix too large");
     MXX_TRACE_BYTES(3.0 * entries * wpp * sizeof(W));
     if (vn == 1)
-        MXX_LAUNCH((preimage_gather_sub_kernel<W, 1>), grid, dim3(256), 0, ctx->stream, static_cast<W *>(out->data),
-                   static_cast<const W *>(ap->data), req, ctx->d_limbs, out->rows, ap->cols, ctx->logN, wpp);
+        MXX_LAUNCH((preimage_gather_sub_kernel<W, 1>), grid, dim3(256), 0, ctx->stream, static_cast<W *>(words_ptr(out)),
+                   static_cast<const W *>(words_ptr(ap)), req, ctx->d_limbs, out->rows, ap->cols, ctx->logN, wpp);
     else
-        MXX_LAUNCH((preimage_gather_sub_kernel<W, 16 / sizeof(W)>), grid, dim3(256), 0, ctx->stream, static_cast<W *>(out->data),
-                   static_cast<const W *>(ap->data), req, ctx->d_limbs, out->rows, ap->cols, ctx->logN, wpp);
+        MXX_LAUNCH((preimage_gather_sub_kernel<W, 16 / sizeof(W)>), grid, dim3(256), 0, ctx->stream, static_cast<W *>(words_ptr(out)),
+                   static_cast<const W *>(words_ptr(ap)), req, ctx->d_limbs, out->rows, ap->cols, ctx->logN, wpp);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -146,12 +146,12 @@ static int launch_scatter(GpuContext *ctx, const RequestTable &req, const GpuMat
     if (!poly_grid(entries, wpp, vn, grid)) return set_error("gpupoly_trapdoor_preimage_many: matrix too large");
     MXX_TRACE_BYTES(3.0 * entries * wpp * sizeof(W));
     if (vn == 1)
-        MXX_LAUNCH((preimage_scatter_kernel<W, 1>), grid, dim3(256), 0, ctx->stream, req, static_cast<const W *>(p->data),
-                   static_cast<const W *>(rez->data), static_cast<const W *>(z->data), ctx->d_limbs, rez->rows, p->rows,
+        MXX_LAUNCH((preimage_scatter_kernel<W, 1>), grid, dim3(256), 0, ctx->stream, req, static_cast<const W *>(words_ptr(p)),
+                   static_cast<const W *>(words_ptr(rez)), static_cast<const W *>(words_ptr(z)), ctx->d_limbs, rez->rows, p->rows,
                    p->cols, ctx->logN, wpp);
     else
         MXX_LAUNCH((preimage_scatter_kernel<W, 16 / sizeof(W)>), grid, dim3(256), 0, ctx->stream, req,
-                   static_cast<const W *>(p->data), static_cast<const W *>(rez->data), static_cast<const W *>(z->data),
+                   static_cast<const W *>(words_ptr(p)), static_cast<const W *>(words_ptr(rez)), static_cast<const W *>(words_ptr(z)),
                    ctx->d_limbs, rez->rows, p->rows, p->cols, ctx->logN, wpp);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -176,17 +176,19 @@ struct TempMatrix {
 // rows [row, row + rows) of m as a matrix that shares its storage (gpupoly_matrix_row_view without the allocation)
 static GpuMatrix row_block(const GpuMatrix *m, size_t row, size_t rows) {
     const size_t poly_bytes = matrix_limbs(m) * static_cast<size_t>(m->ctx->N) * m->ctx->word_bytes;
+    char *base = static_cast<char *>(words_ptr(m));
     GpuMatrix v = *m;
     v.rows = rows;
-    v.data = rows && m->cols ? static_cast<char *>(m->data) + row * m->cols * poly_bytes : nullptr;
+    v.storage = rows && m->cols ? base + row * m->cols * poly_bytes : nullptr;
     v.bytes = rows * m->cols * poly_bytes;
     v.borrowed = true;
     return v;
 }
 
 static bool storage_overlaps(const GpuMatrix *a, const GpuMatrix *b) {
-    if (!a->data || !b->data || !a->bytes || !b->bytes) return false;
-    const char *a0 = static_cast<const char *>(a->data), *b0 = static_cast<const char *>(b->data);
+    if (!a->bytes || !b->bytes) return false;
+    const char *a0 = static_cast<const char *>(words_ptr(a)), *b0 = static_cast<const char *>(words_ptr(b));
+    if (!a0 || !b0) return false;
     return a0 < b0 + b->bytes && b0 < a0 + a->bytes;
 }
 
@@ -221,8 +223,8 @@ static int preimage_group(const PreimageCall &call, const GpuMatrix *const *targ
         seed_z[g] = seeds[3 * j + 2];
         gather.start[g] = scatter.start[g] = static_cast<uint32_t>(at);
         gather.pad_start[g] = scatter.pad_start[g] = static_cast<uint32_t>(pad_at);
-        gather.ptr[g] = targets[j]->data;
-        scatter.ptr[g] = outs[j]->data;
+        gather.ptr[g] = words_ptr(targets[j]);
+        scatter.ptr[g] = words_ptr(outs[j]);
         at += cols[g];
         pad_at += pads[g];
     }

@@ -284,6 +284,7 @@ void EnvSwitches::load() {
     if (const char *e = std::getenv("MXX_HIP_NTT64")) ntt64_int = e[0] == 'i';
     if (const char *e = std::getenv("MXX_HIP_RNG_COMPAT")) rng_compat = e[0] == 'r';
     if (const char *e = std::getenv("MXX_HIP_SERDE")) serde_general = e[0] == 'g';
+    if (const char *e = std::getenv("MXX_HIP_PACK24")) pack24 = !(std::strcmp(e, "0") == 0 || std::strcmp(e, "off") == 0);
     if (const char *e = std::getenv("MXX_HIP_SAMPLER_PER_LANE")) {
         const int v = std::atoi(e);
         if (v >= 1 && v <= 4096) sampler_per_lane = v;
@@ -620,6 +621,7 @@ extern "C" int gpu_context_create(uint32_t logN, uint32_t L, uint32_t dnum, cons
     ctx->lazy_ok = crt_bits + 7 <= (wide ? 64u : 32u);
     ctx->tight_ok = !wide && !ctx->lazy_ok && crt_bits + 4 <= 32u;
     ctx->signed_ok = !wide && crt_bits <= 24;  // signed lazy inverse butterflies: 2^6 q < 2^30 (ntt_lds.h)
+    ctx->pack24_ok = !wide && crt_bits <= 24 && ctx->N % 4 == 0;  // every residue fits 3 bytes (layout.hip)
 
     // Garner table: garner_inv[i*L + j] = (q_j)^-1 mod q_i for j < i
     // (mixed-radix CRT as the reference builds it, Runtime.cu:77-96)

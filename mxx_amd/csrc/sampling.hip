@@ -401,14 +401,15 @@ int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t 
         const dim3 blocks = item_grid(total, 128);
         MXX_TRACE_BYTES(static_cast<double>(out->bytes));
         if (ctx->wide)
-            MXX_LAUNCH(sample_compat_kernel<uint64_t>, blocks, dim3(128), 0, ctx->stream, static_cast<uint64_t *>(out->data), ctx->d_limbs,
+            MXX_LAUNCH(sample_compat_kernel<uint64_t>, blocks, dim3(128), 0, ctx->stream, static_cast<uint64_t *>(words_ptr(out)), ctx->d_limbs,
                        polys, out->cols, full_ncol, col_offset, L, ctx->logN, dist, sigma, seed);
         else
-            MXX_LAUNCH(sample_compat_kernel<uint32_t>, blocks, dim3(128), 0, ctx->stream, static_cast<uint32_t *>(out->data), ctx->d_limbs,
+            MXX_LAUNCH(sample_compat_kernel<uint32_t>, blocks, dim3(128), 0, ctx->stream, static_cast<uint32_t *>(words_ptr(out)), ctx->d_limbs,
                        polys, out->cols, full_ncol, col_offset, L, ctx->logN, dist, sigma, seed);
         HIP_TRY(hipGetLastError());
         if (keep_coeff) return 0;
-        return launch_ntt(ctx, out->data, polys * L, static_cast<int>(L), false);
+        if (dist == GPU_MATRIX_DIST_UNIFORM && pack24_eligible(out)) return pack24_store(out, true);
+        return launch_ntt(ctx, words_ptr(out), polys * L, static_cast<int>(L), false);
     }
     if (dist == GPU_MATRIX_DIST_GAUSS) {
         // enough lanes to fill the chip first, then up to 16 coefficients per lane
@@ -457,7 +458,7 @@ int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t 
         const size_t threads = polys * (uniform ? L : 1u) * groups;
         const dim3 blocks = item_grid(threads, 256);
 #define MXX_SAMPLE(KERNEL, WORD, ...)                                                                                     \
-    MXX_LAUNCH(KERNEL<WORD>, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<WORD *>(out->data), ctx->d_limbs, \
+    MXX_LAUNCH(KERNEL<WORD>, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<WORD *>(words_ptr(out)), ctx->d_limbs, \
                        d_keys, polys, out->cols, full_ncol, col_offset, L, N, groups, ##__VA_ARGS__)
         MXX_TRACE_BYTES(static_cast<double>(out->bytes));  // no input: the residues written once
         if (uniform) {
@@ -471,8 +472,10 @@ int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t 
     }
     HIP_TRY(hipGetLastError());
     if (keep_coeff) return 0;
-    // samples are coefficients; callers always get EVAL (MatrixSampling.cu:463-469)
-    return launch_ntt(ctx, out->data, polys * L, static_cast<int>(L), false);
+    // samples are coefficients; callers always get EVAL (MatrixSampling.cu:463-469).  Uniform samples of a context whose
+    // moduli fit 3 bytes are stored packed, the transform writing the packed rows (layout.hip)
+    if (dist == GPU_MATRIX_DIST_UNIFORM && pack24_eligible(out)) return pack24_store(out, true);
+    return launch_ntt(ctx, words_ptr(out), polys * L, static_cast<int>(L), false);
 }
 
 // ---- several independently seeded requests in one launch (rng.h, RngSegments) ---------------------------------------
@@ -525,7 +528,7 @@ extern "C" int gpupoly_matrix_sample_distribution_segments(GpuMatrix *out, int d
     ctx_free(ctx, stage);
     HIP_TRY(err);
     if (rc) return rc;
-    return launch_ntt(ctx, out->data, polys * L, static_cast<int>(L), false);
+    return launch_ntt(ctx, words_ptr(out), polys * L, static_cast<int>(L), false);
     ABI_GUARD_END
 }
 

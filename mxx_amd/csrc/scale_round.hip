@@ -225,26 +225,26 @@ extern "C" int gpupoly_matrix_scale_round(GpuMatrix *out, const GpuMatrix *in, u
 
     const size_t words = matrix_words(in);
     const size_t word_bytes = static_cast<size_t>(ctx->word_bytes);
-    const void *src = in->data;
+    const void *src = words_ptr(in);
     if (in->format == GPU_POLY_FORMAT_EVAL) {
         // inverse transform in `out` (a copy of `in` first when they differ): `in` is left as it was
         if (out != in)
             MXX_TRACED_COPY("copy (device to device)", ctx->stream, 2.0 * in->bytes,
-                            HIP_TRY(hipMemcpyAsync(out->data, in->data, in->bytes, hipMemcpyDeviceToDevice, ctx->stream)));
-        const int rc = launch_ntt(ctx, out->data, polys * static_cast<size_t>(L), L, true);
+                            HIP_TRY(hipMemcpyAsync(words_ptr(out), words_ptr(in), in->bytes, hipMemcpyDeviceToDevice, ctx->stream)));
+        const int rc = launch_ntt(ctx, words_ptr(out), polys * static_cast<size_t>(L), L, true);
         if (rc) return rc;
         out->format = GPU_POLY_FORMAT_COEFF;
-        src = out->data;
+        src = words_ptr(out);
     }
     const uint32_t N = static_cast<uint32_t>(ctx->N);
     const dim3 grid = item_grid(polys * N, 256);
     const size_t gstride = static_cast<size_t>(ctx->limb_count);
     MXX_TRACE_BYTES(2.0 * static_cast<double>(words * word_bytes));
     if (ctx->wide)
-        BY_LIMBS(scale_round_kernel, uint64_t, L, static_cast<const uint64_t *>(src), static_cast<uint64_t *>(out->data), polys, N,
+        BY_LIMBS(scale_round_kernel, uint64_t, L, static_cast<const uint64_t *>(src), static_cast<uint64_t *>(words_ptr(out)), polys, N,
                  sc, ctx->d_garner, gstride, ctx->d_limbs);
     else
-        BY_LIMBS(scale_round_kernel, uint32_t, L, static_cast<const uint32_t *>(src), static_cast<uint32_t *>(out->data), polys, N,
+        BY_LIMBS(scale_round_kernel, uint32_t, L, static_cast<const uint32_t *>(src), static_cast<uint32_t *>(words_ptr(out)), polys, N,
                  sc, ctx->d_garner, gstride, ctx->d_limbs);
     HIP_TRY(hipGetLastError());
     out->format = GPU_POLY_FORMAT_COEFF;
@@ -270,12 +270,12 @@ extern "C" int gpupoly_matrix_store_coeff_words(const GpuMatrix *mat, uint64_t *
     wc.words = static_cast<int>(Q.size());
     for (int k = 0; k < static_cast<int>(GPUPOLY_MAX_LIMBS); ++k) wc.q[k] = k < L ? ctx->moduli[k] : 0;
 
-    const void *src = mat->data;
+    const void *src = words_ptr(mat);
     CtxBlock scratch(ctx);
     if (mat->format == GPU_POLY_FORMAT_EVAL) {  // scratch inverse transform: `mat` is left as it was
         if (scratch.alloc(mat->bytes)) return 1;
         MXX_TRACED_COPY("copy (device to device)", ctx->stream, 2.0 * mat->bytes,
-                        HIP_TRY(hipMemcpyAsync(scratch.ptr, mat->data, mat->bytes, hipMemcpyDeviceToDevice, ctx->stream)));
+                        HIP_TRY(hipMemcpyAsync(scratch.ptr, words_ptr(mat), mat->bytes, hipMemcpyDeviceToDevice, ctx->stream)));
         const int rc = launch_ntt(ctx, scratch.ptr, polys * static_cast<size_t>(L), L, true);
         if (rc) return rc;
         src = scratch.ptr;

@@ -456,7 +456,7 @@ extern "C" int gpu_matrix_store_compact_bytes(GpuMatrix *mat, uint8_t *payload_o
     if (fast) {
         const dim3 fast_blocks(static_cast<unsigned>(std::min<size_t>((coeffs + 255) / 256, 8192)));
 #define FAST_MAXBITS(WT, ML)                                                                                             \
-    MXX_LAUNCH((compact_maxbits_fast_kernel<WT, ML>), fast_blocks, dim3(256), 0, ctx->stream, static_cast<const WT *>(mat->data), polys, N, sc, \
+    MXX_LAUNCH((compact_maxbits_fast_kernel<WT, ML>), fast_blocks, dim3(256), 0, ctx->stream, static_cast<const WT *>(words_ptr(mat)), polys, N, sc, \
                ctx->d_garner, gstride, ctx->d_limbs, static_cast<unsigned int *>(d_max))
         if (ctx->wide) {
             if (sc.limbs <= 8) FAST_MAXBITS(uint64_t, 8);
@@ -483,10 +483,10 @@ extern "C" int gpu_matrix_store_compact_bytes(GpuMatrix *mat, uint8_t *payload_o
     unsigned int h_max = h_mf[0];
     if (!fast) {
         if (ctx->wide)
-            SERDE_LAUNCH(compact_maxbits_kernel, uint64_t, static_cast<const uint64_t *>(mat->data), polys, N, sc, ctx->d_garner,
+            SERDE_LAUNCH(compact_maxbits_kernel, uint64_t, static_cast<const uint64_t *>(words_ptr(mat)), polys, N, sc, ctx->d_garner,
                          gstride, ctx->d_limbs, static_cast<unsigned int *>(d_max));
         else
-            SERDE_LAUNCH(compact_maxbits_kernel, uint32_t, static_cast<const uint32_t *>(mat->data), polys, N, sc, ctx->d_garner,
+            SERDE_LAUNCH(compact_maxbits_kernel, uint32_t, static_cast<const uint32_t *>(words_ptr(mat)), polys, N, sc, ctx->d_garner,
                          gstride, ctx->d_limbs, static_cast<unsigned int *>(d_max));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&h_max, d_max, sizeof(h_max), hipMemcpyDeviceToHost, ctx->stream));
@@ -517,7 +517,7 @@ extern "C" int gpu_matrix_store_compact_bytes(GpuMatrix *mat, uint8_t *payload_o
         const size_t word_count = padded / 4;
 #undef SERDE_LAUNCH
 #define PACK_LAUNCH(WT, ML, LDSF)                                                                                       \
-    MXX_LAUNCH((compact_pack_kernel<WT, ML, LDSF>), blocks, dim3(256), pack_lds, ctx->stream, static_cast<const WT *>(mat->data), polys, N, sc, \
+    MXX_LAUNCH((compact_pack_kernel<WT, ML, LDSF>), blocks, dim3(256), pack_lds, ctx->stream, static_cast<const WT *>(words_ptr(mat)), polys, N, sc, \
                ctx->d_garner, gstride, ctx->d_limbs, width, static_cast<uint32_t *>(d_payload), word_count)
 #define PACK_BY_LIMBS(WT, LDSF)                       \
     do {                                              \
@@ -526,7 +526,7 @@ extern "C" int gpu_matrix_store_compact_bytes(GpuMatrix *mat, uint8_t *payload_o
         else PACK_LAUNCH(WT, 64, LDSF);               \
     } while (0)
 #define FAST_PACK(WT, ML)                                                                                                \
-    MXX_LAUNCH((compact_pack_fast_kernel<WT, ML>), blocks, dim3(256), pack_lds, ctx->stream, static_cast<const WT *>(mat->data), polys, N, sc, \
+    MXX_LAUNCH((compact_pack_fast_kernel<WT, ML>), blocks, dim3(256), pack_lds, ctx->stream, static_cast<const WT *>(words_ptr(mat)), polys, N, sc, \
                ctx->d_garner, gstride, ctx->d_limbs, width, static_cast<uint32_t *>(d_payload), word_count)
         if (fast && in_lds) {
             if (ctx->wide) {
@@ -587,11 +587,11 @@ extern "C" int gpu_matrix_load_compact_bytes(GpuMatrix *mat, const uint8_t *payl
     const dim3 blocks = item_grid(coeffs, 256);
     if (ctx->wide)
         MXX_LAUNCH(compact_unpack_kernel<uint64_t>, blocks, dim3(256), 0, ctx->stream,
-                           static_cast<uint64_t *>(mat->data), static_cast<const uint8_t *>(d_payload), polys, N, sc,
+                           static_cast<uint64_t *>(words_ptr(mat)), static_cast<const uint8_t *>(d_payload), polys, N, sc,
                            ctx->d_limbs, static_cast<uint32_t>(max_coeff_bits));
     else
         MXX_LAUNCH(compact_unpack_kernel<uint32_t>, blocks, dim3(256), 0, ctx->stream,
-                           static_cast<uint32_t *>(mat->data), static_cast<const uint8_t *>(d_payload), polys, N, sc,
+                           static_cast<uint32_t *>(words_ptr(mat)), static_cast<const uint8_t *>(d_payload), polys, N, sc,
                            ctx->d_limbs, static_cast<uint32_t>(max_coeff_bits));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // synchronous, like the reference; payload may be freed by the caller

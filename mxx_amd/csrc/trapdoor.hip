@@ -602,16 +602,16 @@ static int gauss_samp_impl(GpuMatrix *src, uint32_t base_bits, double c, GpuRngS
         int rc = gpu_matrix_intt_all(src);
         if (rc) return rc;
     }
-    int rc = ctx->wide ? launch_gauss_samp<uint64_t>(ctx, static_cast<uint64_t *>(out->data),
-                                                     static_cast<const uint64_t *>(src->data), polys,
+    int rc = ctx->wide ? launch_gauss_samp<uint64_t>(ctx, static_cast<uint64_t *>(words_ptr(out)),
+                                                     static_cast<const uint64_t *>(words_ptr(src)), polys,
                                                      (uint32_t)src->cols, (uint32_t)L, dpt, base_bits, c, k, seed, segs)
-                       : launch_gauss_samp<uint32_t>(ctx, static_cast<uint32_t *>(out->data),
-                                                     static_cast<const uint32_t *>(src->data), polys,
+                       : launch_gauss_samp<uint32_t>(ctx, static_cast<uint32_t *>(words_ptr(out)),
+                                                     static_cast<const uint32_t *>(words_ptr(src)), polys,
                                                      (uint32_t)src->cols, (uint32_t)L, dpt, base_bits, c, k, seed, segs);
     if (rc) return rc;
     out->format = GPU_POLY_FORMAT_COEFF;
     if (requested == GPU_POLY_FORMAT_EVAL) {
-        rc = launch_ntt(ctx, out->data, matrix_polys(out) * L, static_cast<int>(L), false);
+        rc = launch_ntt(ctx, words_ptr(out), matrix_polys(out) * L, static_cast<int>(L), false);
         if (rc) return rc;
         out->format = GPU_POLY_FORMAT_EVAL;
     }
@@ -886,13 +886,13 @@ extern "C" int gpu_matrix_create_p1_covariance_cache(const GpuMatrix *a_mat, con
     const unsigned blocks = static_cast<unsigned>((n + 127) / 128);
     if (ctx->wide)
         MXX_LAUNCH(p1_covariance_kernel<uint64_t>, dim3(blocks), dim3(128), 0, ctx->stream,
-                           static_cast<const uint64_t *>(a_mat->data), static_cast<const uint64_t *>(b_mat->data),
-                           static_cast<const uint64_t *>(d_mat->data), (uint32_t)d, L, (uint32_t)n, ctx->moduli[0],
+                           static_cast<const uint64_t *>(words_ptr(a_mat)), static_cast<const uint64_t *>(words_ptr(b_mat)),
+                           static_cast<const uint64_t *>(words_ptr(d_mat)), (uint32_t)d, L, (uint32_t)n, ctx->moduli[0],
                            sigma, s, dgg_stddev, static_cast<double *>(cov_ws), cache->sqrt_var, cache->update_coeff);
     else
         MXX_LAUNCH(p1_covariance_kernel<uint32_t>, dim3(blocks), dim3(128), 0, ctx->stream,
-                           static_cast<const uint32_t *>(a_mat->data), static_cast<const uint32_t *>(b_mat->data),
-                           static_cast<const uint32_t *>(d_mat->data), (uint32_t)d, L, (uint32_t)n, ctx->moduli[0],
+                           static_cast<const uint32_t *>(words_ptr(a_mat)), static_cast<const uint32_t *>(words_ptr(b_mat)),
+                           static_cast<const uint32_t *>(words_ptr(d_mat)), (uint32_t)d, L, (uint32_t)n, ctx->moduli[0],
                            sigma, s, dgg_stddev, static_cast<double *>(cov_ws), cache->sqrt_var, cache->update_coeff);
     MXX_LAUNCH(p1_divisor_kernel, dim3(static_cast<unsigned>((n * m + 255) / 256)), dim3(256), 0, ctx->stream,
                        static_cast<KarneyDivisor *>(kd), cache->sqrt_var, n * m);
@@ -979,7 +979,7 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
                         static_cast<double>(N) * m * (8.0 + sizeof(KarneyDivisor) + 8.0 * m));
 #define LAUNCH_P1K(WT, MAXM, SV, SEG, SEGARG)                                                                     \
     MXX_LAUNCH((p1_sample_lanes_kernel<WT, MAXM, SV, SEG>), dim3(lblocks), dim3(SAMPLER_THREADS), 0, ctx->stream, \
-               static_cast<int64_t *>(stage), static_cast<const WT *>(tp2->data), cache->sqrt_var,                \
+               static_cast<int64_t *>(stage), static_cast<const WT *>(words_ptr(tp2)), cache->sqrt_var,                \
                cache->update_coeff, static_cast<const KarneyDivisor *>(cache->karney_div), (uint32_t)m,           \
                (uint32_t)cols, L, ctx->logN, ctx->moduli[0], c_scale, key, total, per_lane,                       \
                static_cast<uint32_t>(ctx->env.sampler_fill_every ? ctx->env.sampler_fill_every : 2), SEGARG)
@@ -1013,7 +1013,7 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
         ctx_free(ctx, stage);
         if (le != hipSuccess) return set_error(le, "p1_sample_lanes_kernel");
         if (lrc) return lrc;
-        lrc = launch_ntt(ctx, out->data, matrix_polys(out) * L, static_cast<int>(L), false);
+        lrc = launch_ntt(ctx, words_ptr(out), matrix_polys(out) * L, static_cast<int>(L), false);
         if (lrc) return lrc;
         out->format = GPU_POLY_FORMAT_EVAL;
         return 0;
@@ -1023,7 +1023,7 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
     if (m > 8 && ctx_alloc(ctx, total * m * sizeof(double), &mean_ws)) return 1;
 #define LAUNCH_P1(WT, MAXM)                                                                                       \
     MXX_LAUNCH((p1_sample_kernel<WT, MAXM>), dim3(blocks), dim3(128), 0, ctx->stream,                      \
-                       static_cast<WT *>(out->data), static_cast<const WT *>(tp2->data), ctx->d_limbs,             \
+                       static_cast<WT *>(words_ptr(out)), static_cast<const WT *>(words_ptr(tp2)), ctx->d_limbs,             \
                        cache->sqrt_var, cache->update_coeff, (uint32_t)m, (uint32_t)cols, L, N, ctx->moduli[0],    \
                        c_scale, seed, static_cast<double *>(mean_ws))
     if (ctx->wide) {
@@ -1042,7 +1042,7 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
     if (mean_ws) ctx_free(ctx, mean_ws);
     if (e != hipSuccess) return set_error(e, "p1_sample_kernel");
     // always finishes in EVAL
-    int rc = launch_ntt(ctx, out->data, matrix_polys(out) * L, static_cast<int>(L), false);
+    int rc = launch_ntt(ctx, words_ptr(out), matrix_polys(out) * L, static_cast<int>(L), false);
     if (rc) return rc;
     out->format = GPU_POLY_FORMAT_EVAL;
     return 0;

@@ -223,6 +223,15 @@ class GpuDCRTPolyMatrix:
         self._version = 0  # bumped by every in-place write (and on the parent of a view): keys caches derived from the contents
         self._finalizer = weakref.finalize(self, _ffi.lib().gpu_matrix_destroy, raw)
 
+    @property
+    def layout(self) -> str:
+        """How the device stores the residues now (gpupoly_matrix_layout): "words", or "packed24" - 3 bytes per residue,
+        what a uniform sample of a context whose moduli are all below 2^24 starts as until an operation without a
+        packed path unpacks it (once).  Results never depend on it."""
+        out = C.c_int(-1)
+        check_status(_ffi.lib().gpupoly_matrix_layout(self.raw, C.byref(out)), "gpupoly_matrix_layout")
+        return "packed24" if out.value == 1 else "words"
+
     @classmethod
     def new_empty(cls, params, nrow, ncol) -> "GpuDCRTPolyMatrix":
         return cls(params, nrow, ncol, params.crt_depth() - 1, True)
