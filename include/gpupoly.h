@@ -335,6 +335,15 @@ int gpupoly_matrix_scale_round(GpuMatrix *out, const GpuMatrix *in, uint64_t t, 
  * coeffs() / coeffs_biguints() (src/poly/dcrt/gpu.rs:959-994).  A words_per_coeff below what Q_level needs is
  * refused with nothing launched.                                                                                  */
 int gpupoly_matrix_store_coeff_words(const GpuMatrix *mat, uint64_t *out, size_t words_per_coeff);
+/* Exact centred infinity norm of every entry: max_i |x_i| with x_i coefficient i of entry (row, col) taken in
+ * (-Q_level/2, Q_level/2] - min(v, Q_level - v) for v in [0, Q_level) - as little-endian 64-bit words, words_per_value
+ * words each (zero above the words Q_level needs), order [row][col], into host memory `out` (synchronous).  COEFF or EVAL
+ * input (an EVAL input is inverse-transformed in scratch; `mat`'s residues and format are left as they were); 0 rows or
+ * 0 columns succeed with nothing launched.  Replaces the host loops over coeffs() with min(v, Q - v) and a max: the
+ * preimage predicate (src/sampler/trapdoor/gpu.rs:690-752, the p-hat form :756-812) and matrix_centered_max_abs
+ * (tests/test_gpu_diamond_injector_q_bits_vs_max_error_plot_generates_svg.rs:145-163).  A null argument or a
+ * words_per_value below what Q_level needs is refused with nothing launched and nothing written.                  */
+int gpupoly_matrix_centered_max_abs(const GpuMatrix *mat, uint64_t *out, size_t words_per_value);
 /* kernel launches issued by the library since it was loaded (every context; copies / memsets not counted): bench.py
  * reports launches per step for the launch-bound small-ring chain                                              */
 uint64_t gpupoly_launch_count(void);

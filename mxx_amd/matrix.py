@@ -201,6 +201,21 @@ class GpuP1CovarianceCache:
         self._finalizer = weakref.finalize(self, _ffi.lib().gpu_matrix_destroy_p1_covariance_cache, raw)
 
 
+def _max_along(entries, axis, nrow, ncol):
+    """[row][col] values -> the whole-matrix max (axis=None), per row (1), per column (0) or as they are ("entries")"""
+    if isinstance(axis, str):
+        if axis != "entries":
+            raise ValueError(f"axis must be None, 0, 1 or 'entries' (got {axis!r})")
+        return entries
+    if axis is None:
+        return max((v for row in entries for v in row), default=0)
+    if axis == 1:
+        return [max(row, default=0) for row in entries]
+    if axis == 0:
+        return [max((entries[r][c] for r in range(nrow)), default=0) for c in range(ncol)]
+    raise ValueError(f"axis must be None, 0, 1 or 'entries' (got {axis!r})")
+
+
 class GpuDCRTPolyMatrix:
     __slots__ = ("params", "nrow", "ncol", "level", "is_ntt", "raw", "_finalizer", "_parent", "_version", "__weakref__")
 
@@ -501,6 +516,39 @@ class GpuDCRTPolyMatrix:
                 row.append([v % Q for v in vals])
             out.append(row)
         return out
+
+    def centered_max_abs(self, axis=None):
+        """Exact centred infinity norm: max |x| over the coefficients x of an entry, each taken in
+        (-Q_level/2, Q_level/2] (= min(v, Q_level - v) for v in [0, Q_level)), Q_level the product of the matrix's own
+        limbs.  One device call (gpupoly_matrix_centered_max_abs, the matrix left as it is) replaces coeffs() and a host
+        pass.  axis=None: an int over the whole matrix; axis=1: a list per row; axis=0: a list per column;
+        axis="entries": the [row][col] nested list.  Empty rows / columns contribute 0."""
+        return _max_along(self._centered_max_abs_entries(), axis, self.nrow, self.ncol)
+
+    def _centered_max_abs_entries(self) -> list:
+        if self.nrow == 0 or self.ncol == 0:
+            return [[] for _ in range(self.nrow)]
+        Q = 1
+        for q in self.params.moduli()[: self.level + 1]:
+            Q *= q
+        wpv = -(-Q.bit_length() // 64)
+        words = np.empty((self.nrow, self.ncol, wpv), dtype=np.uint64)
+        st = _ffi.lib().gpupoly_matrix_centered_max_abs(self.raw, words.ctypes.data_as(C.POINTER(C.c_uint64)), wpv)
+        check_status(st, "gpupoly_matrix_centered_max_abs")
+        if wpv == 1:
+            return words[..., 0].tolist()
+        mv, step = memoryview(words).cast("B"), 8 * wpv
+        flat = [int.from_bytes(mv[i : i + step], "little") for i in range(0, len(mv), step)]
+        return [flat[r * self.ncol : (r + 1) * self.ncol] for r in range(self.nrow)]
+
+    def _centered_max_abs_host(self, axis=None):
+        """centered_max_abs as the callers run it on the host: coeffs(), then min(v, Q - v) and a max (kept for
+        comparison)."""
+        Q = 1
+        for q in self.params.moduli()[: self.level + 1]:
+            Q *= q
+        entries = [[max((min(v, Q - v) for v in poly), default=0) for poly in row] for row in self.coeffs()]
+        return _max_along(entries, axis, self.nrow, self.ncol)
 
     # ------------------------------------------------------------------ compact wire format
     def to_compact_bytes(self) -> bytes:

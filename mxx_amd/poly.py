@@ -130,6 +130,10 @@ class GpuDCRTPoly:
     def coeffs(self) -> list[int]:
         return self.inner.coeffs()[0][0]
 
+    def centered_max_abs(self) -> int:
+        """max |x| over the coefficients x in (-Q_level/2, Q_level/2] (GpuDCRTPolyMatrix.centered_max_abs)"""
+        return self.inner.centered_max_abs()
+
     def ensure_coeff_domain(self) -> "GpuDCRTPoly":
         return GpuDCRTPoly(self.inner.ensure_coeff())
 
