@@ -335,6 +335,20 @@ int gpupoly_matrix_scale_round(GpuMatrix *out, const GpuMatrix *in, uint64_t t, 
  * coeffs() / coeffs_biguints() (src/poly/dcrt/gpu.rs:959-994).  A words_per_coeff below what Q_level needs is
  * refused with nothing launched.                                                                                  */
 int gpupoly_matrix_store_coeff_words(const GpuMatrix *mat, uint64_t *out, size_t words_per_coeff);
+/* The way in (extension): coefficient k of entry (row, col) of `mat` becomes x mod q_l for every limb
+ * l <= mat->level, x the integer that words_per_coeff little-endian 64-bit words spell; `words` is host memory in the
+ * order [row][col][k][w], k < coeffs_per_poly, w < words_per_coeff - the mirror image of what
+ * gpupoly_matrix_store_coeff_words writes.  x need not be below Q_level: every limb reduces the whole value, like the
+ * BigUint % q of residues_from_biguints (src/poly/dcrt/gpu.rs:841-857), which this replaces together with the upload
+ * and transform of from_biguints / from_coeffs (:903-939).  words_per_coeff may be smaller or larger than the words of
+ * Q_level.  coeffs_per_poly <= N; coefficients at or above it are written as 0, so every word of `mat` is written
+ * whatever it held (coeffs_per_poly = 0: the zero matrix, `words` may be null).  out_format GPU_POLY_FORMAT_COEFF leaves
+ * the residues as loaded, GPU_POLY_FORMAT_EVAL runs the forward transform in place afterwards; `mat` is tagged with it on
+ * success.  Synchronous: `words` may be reused on return.  0 rows or 0 columns succeed with nothing launched.
+ * Refused, with nothing launched and `mat` (contents and tag) untouched: a null `mat`, null `words` with
+ * coeffs_per_poly > 0, words_per_coeff = 0 or above 2^32 - 1, coeffs_per_poly > N, an out_format that is neither.    */
+int gpupoly_matrix_load_coeff_words(GpuMatrix *mat, const uint64_t *words, size_t words_per_coeff, size_t coeffs_per_poly,
+                                    int out_format);
 /* Exact centred infinity norm of every entry: max_i |x_i| with x_i coefficient i of entry (row, col) taken in
  * (-Q_level/2, Q_level/2] - min(v, Q_level - v) for v in [0, Q_level) - as little-endian 64-bit words, words_per_value
  * words each (zero above the words Q_level needs), order [row][col], into host memory `out` (synchronous).  COEFF or EVAL

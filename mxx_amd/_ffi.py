@@ -143,6 +143,7 @@ SIGNATURES = {
     "gpupoly_launch_count": (C.c_uint64, []),
     "gpupoly_matrix_scale_round": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int]),
     "gpupoly_matrix_store_coeff_words": (C.c_int, [_vp, C.POINTER(C.c_uint64), _sz]),
+    "gpupoly_matrix_load_coeff_words": (C.c_int, [_vp, C.POINTER(C.c_uint64), _sz, _sz, C.c_int]),
     "gpupoly_matrix_centered_max_abs": (C.c_int, [_vp, C.POINTER(C.c_uint64), _sz]),
     "gpupoly_detmath_eval": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _sz]),
     "gpupoly_device_can_access_peer": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),

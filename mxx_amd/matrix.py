@@ -278,6 +278,50 @@ class GpuDCRTPolyMatrix:
         return out
 
     @classmethod
+    def from_coeff_words(cls, params, words: np.ndarray, eval_format: bool = True, level=None) -> "GpuDCRTPolyMatrix":
+        """Extension: big-integer coefficients as little-endian 64-bit words, shape (nrow, ncol, k, wpc) with
+        k <= ring dimension (missing coefficients are 0), reduced mod every limb on the device
+        (gpupoly_matrix_load_coeff_words; any value of wpc words, not only those below Q).  EVAL unless eval_format is
+        false; at `level` (full level by default)."""
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        if words.ndim != 4:
+            raise ValueError("from_coeff_words: words must have shape (nrow, ncol, k, words_per_coeff)")
+        nrow, ncol = words.shape[:2]
+        out = cls(params, nrow, ncol, params.crt_depth() - 1 if level is None else level, eval_format)
+        out.load_coeff_words(words, eval_format)
+        return out
+
+    @classmethod
+    def from_coeffs(cls, params, rows, eval_format: bool = True) -> "GpuDCRTPolyMatrix":
+        """The inverse of coeffs(): rows[r][c] is a sequence of at most ring-dimension non-negative python ints (shorter
+        ones are padded with zeros; values at or above Q are reduced), the result is at full level, EVAL unless
+        eval_format is false.  The ints become 64-bit words in one pass over a bytes buffer and the device reduces them
+        mod every limb (from_coeff_words): no big-integer arithmetic on the host."""
+        nrow = len(rows)
+        ncol = len(rows[0]) if nrow else 0
+        if nrow == 0 or ncol == 0:
+            return cls.new_empty(params, nrow, ncol)
+        polys = []
+        for row in rows:
+            assert len(row) == ncol, "row length mismatch in from_coeffs"
+            polys.extend(row)
+        k = max(len(poly) for poly in polys)
+        assert k <= params.ring_dimension(), "more coefficients than the ring dimension"
+        flat = []
+        for poly in polys:
+            flat.extend(map(int, poly))
+            flat.extend([0] * (k - len(poly)))
+        if flat and min(flat) < 0:
+            raise ValueError("from_coeffs: negative coefficient (coefficients are unsigned)")
+        wpc = max(1, -(-max(flat, default=0).bit_length() // 64))
+        if wpc == 1:
+            words = np.array(flat, dtype=np.uint64)
+        else:
+            step = 8 * wpc
+            words = np.frombuffer(b"".join([c.to_bytes(step, "little") for c in flat]), dtype=np.uint64)
+        return cls.from_coeff_words(params, words.reshape(nrow, ncol, k, wpc), eval_format)
+
+    @classmethod
     def from_cpu_matrix(cls, params, coeff_residues: np.ndarray) -> "GpuDCRTPolyMatrix":
         """`from_cpu_matrix` (gpu_dcrt_poly.rs:769-817): CPU matrices travel as EVAL residues."""
         return cls.from_rns(params, coeff_residues, True)
@@ -345,6 +389,20 @@ class GpuDCRTPolyMatrix:
         st = _ffi.lib().gpu_matrix_load_rns_batch(self.raw, data.ctypes.data, self._bytes_per_poly(), fmt, C.byref(events))
         check_status(st, "gpu_matrix_load_rns_batch")
         _ffi.wait_and_destroy_events(events)
+        self.is_ntt = eval_format
+
+    def load_coeff_words(self, words: np.ndarray, eval_format: bool = True) -> None:
+        """Overwrite this matrix with the coefficients `words` spells, shape (nrow, ncol, k, wpc) (from_coeff_words):
+        one call of gpupoly_matrix_load_coeff_words at this matrix's level."""
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        if words.ndim != 4 or words.shape[:2] != (self.nrow, self.ncol):
+            raise ValueError("load_coeff_words: words must have shape (nrow, ncol, k, words_per_coeff)")
+        k, wpc = words.shape[2:]
+        fmt = GPU_POLY_FORMAT_EVAL if eval_format else GPU_POLY_FORMAT_COEFF
+        self._touch()
+        ptr = words.ctypes.data_as(C.POINTER(C.c_uint64)) if words.size else None
+        st = _ffi.lib().gpupoly_matrix_load_coeff_words(self.raw, ptr, wpc, k, fmt)
+        check_status(st, "gpupoly_matrix_load_coeff_words")
         self.is_ntt = eval_format
 
     def to_rns(self) -> np.ndarray:
@@ -646,14 +704,11 @@ class GpuDCRTPolyMatrix:
         return out if out is not None else self._modulus_switch_host(new_modulus)
 
     def _modulus_switch_host(self, new_modulus: int) -> "GpuDCRTPolyMatrix":
-        """modulus_switch as the reference runs it: coeffs() -> big-integer rescale -> from_coeffs -> from_poly_vec."""
-        from .poly import GpuDCRTPoly
-
+        """modulus_switch as the reference runs it, coeffs() -> big-integer rescale -> from_coeffs -> from_poly_vec, the
+        last two as one from_coeffs of the whole matrix."""
         Q = self.params.modulus()
-        rows = []
-        for row in self.coeffs():
-            rows.append([GpuDCRTPoly.from_coeffs(self.params, [(c * new_modulus // Q) % new_modulus for c in poly]) for poly in row])
-        return GpuDCRTPolyMatrix.from_poly_vec(self.params, rows)
+        rows = [[[(c * new_modulus // Q) % new_modulus for c in poly] for poly in row] for row in self.coeffs()]
+        return GpuDCRTPolyMatrix.from_coeffs(self.params, rows)
 
     def decode_centered(self, plaintext_modulus: int) -> "GpuDCRTPolyMatrix":
         """Extension: `decode_centered_masked_matrix` (src/decoder/masked_high_bit.rs:39-70) on the device - every
@@ -665,17 +720,12 @@ class GpuDCRTPolyMatrix:
         return out if out is not None else self._decode_centered_host(plaintext_modulus)
 
     def _decode_centered_host(self, plaintext_modulus: int) -> "GpuDCRTPolyMatrix":
-        """decode_centered as the reference runs it: coeffs -> big-integer rounding -> from_biguints -> set_entry."""
-        from .poly import GpuDCRTPoly
-
+        """decode_centered as the reference runs it, coeffs -> big-integer rounding -> from_biguints -> set_entry, the
+        last two as one from_coeffs of the whole matrix."""
         Q = self.params.modulus()
         half = Q // 2
-        out = GpuDCRTPolyMatrix.zero(self.params, self.nrow, self.ncol)
-        for i, row in enumerate(self.coeffs()):
-            for j, poly in enumerate(row):
-                vals = [((plaintext_modulus * c + half) // Q) % plaintext_modulus for c in poly]
-                out.set_entry(i, j, GpuDCRTPoly.from_biguints(self.params, vals))
-        return out
+        rows = [[[((plaintext_modulus * c + half) // Q) % plaintext_modulus for c in poly] for poly in row] for row in self.coeffs()]
+        return GpuDCRTPolyMatrix.from_coeffs(self.params, rows)
 
     def _scale_round(self, t: int, round_half: bool):
         """gpupoly_matrix_scale_round into a new full-level matrix, brought to EVAL; None where the host path applies."""

@@ -26,7 +26,15 @@ class GpuDCRTPoly:
 
     @classmethod
     def from_biguints(cls, params, coeffs) -> "GpuDCRTPoly":
-        """Coefficients (python ints) -> COEFF residues -> NTT (gpu.rs:930-933,841-857)."""
+        """Coefficients (python ints) -> COEFF residues -> NTT (gpu.rs:930-933,841-857): the residues are taken on the
+        device (GpuDCRTPolyMatrix.from_coeffs, gpupoly_matrix_load_coeff_words)."""
+        assert len(coeffs) <= params.ring_dimension()
+        return cls(GpuDCRTPolyMatrix.from_coeffs(params, [[coeffs]], True))
+
+    @classmethod
+    def _from_biguints_host(cls, params, coeffs) -> "GpuDCRTPoly":
+        """from_biguints with `int % q` per coefficient and limb on the host: the form before the device load (kept for
+        comparison)."""
         n = params.ring_dimension()
         assert len(coeffs) <= n
         moduli = params.moduli()
