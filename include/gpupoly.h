@@ -358,6 +358,35 @@ int gpupoly_matrix_load_coeff_words(GpuMatrix *mat, const uint64_t *words, size_
  * (tests/test_gpu_diamond_injector_q_bits_vs_max_error_plot_generates_svg.rs:145-163).  A null argument or a
  * words_per_value below what Q_level needs is refused with nothing launched and nothing written.                  */
 int gpupoly_matrix_centered_max_abs(const GpuMatrix *mat, uint64_t *out, size_t words_per_value);
+/* The compact wire format for MANY matrices in one call (extension): what a loop over
+ * gpu_matrix_store_compact_bytes / gpu_matrix_load_compact_bytes gives, with one width launch, one pack launch, one copy
+ * of the widths, one copy of the payloads and two synchronises per CALL (up to 32 matrices of a level per launch)
+ * instead of per matrix.  Replaces the per-matrix to_compact_bytes of get_lookup_buffer (src/storage/write.rs:724-793)
+ * and the per-slot from_compact_bytes of the reading side (src/storage/read.rs:129-149).
+ * Store: for every j < n the triple (out_max_coeff_bits[j], out_bytes_per_coeff[j], the out_payload_lens[j] bytes at
+ * payload_out + out_payload_offsets[j]) is exactly what gpu_matrix_store_compact_bytes(mats[j], ...) reports and writes
+ * for that matrix alone: every matrix keeps its OWN matrix-wide width.  out_payload_offsets[0] = 0, offsets are multiples
+ * of 8 and do not decrease with j, the bytes between a payload's end and the next offset (at most 7) are zero,
+ * *out_total_len = the last offset + the last length.  Like the one-matrix entry, an EVAL matrix is taken to the
+ * coefficient domain in place (the caller records the tag beforehand); zero matrices and matrices without entries give
+ * width 0 and length 0.  Synchronous: the bytes are in payload_out on return.  When payload_capacity < *out_total_len the
+ * call fails with "payload buffer too small ..." AND fills all five out arrays / values, payload_out untouched, so that
+ * the caller retries once with the exact size (the matrices are in COEFF form by then, as after the one-matrix entry).
+ * Load: mats[j] receives what gpu_matrix_load_compact_bytes(mats[j], payloads[j], payload_lens[j], max_coeff_bits[j])
+ * gives it, tagged COEFF.  The payloads are separate host pointers (in a lookup buffer a header sits in front of each).
+ * Synchronous: the payloads may be freed on return.
+ * One context per call; levels and shapes may differ from matrix to matrix; n = 0 does nothing.  Matrices whose
+ * coefficients leave the two fast CRT forms, contexts above 16 limbs and MXX_HIP_SERDE=general go through the general
+ * kernels one by one inside the same call (at most one further synchronise).
+ * Refused, with nothing launched and every matrix (contents and tag) and every out value untouched: a null array with
+ * n > 0, a null matrix, matrices of different contexts, the same matrix twice; for the load additionally everything the
+ * one-matrix load refuses (length mismatch, non-zero length at width 0, null payload), checked for ALL j before the
+ * first copy.                                                                                                      */
+int gpupoly_matrix_store_compact_bytes_many(GpuMatrix *const *mats, size_t n, uint8_t *payload_out, size_t payload_capacity,
+                                            uint16_t *out_max_coeff_bits, uint16_t *out_bytes_per_coeff,
+                                            size_t *out_payload_offsets, size_t *out_payload_lens, size_t *out_total_len);
+int gpupoly_matrix_load_compact_bytes_many(GpuMatrix *const *mats, size_t n, const uint8_t *const *payloads,
+                                           const size_t *payload_lens, const uint16_t *max_coeff_bits);
 /* kernel launches issued by the library since it was loaded (every context; copies / memsets not counted): bench.py
  * reports launches per step for the launch-bound small-ring chain                                              */
 uint64_t gpupoly_launch_count(void);

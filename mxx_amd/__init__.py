@@ -29,6 +29,7 @@ from .matrix import (  # noqa: F401
 )
 from .params import DCRTPolyParams, GpuContext, GpuDCRTPolyParams, gen_crt_basis  # noqa: F401
 from .poly import GpuDCRTPoly  # noqa: F401
+from . import storage  # noqa: F401
 from .sampler import (  # noqa: F401
     DistType,
     GpuDCRTPolyHashSampler,

@@ -663,6 +663,93 @@ class GpuDCRTPolyMatrix:
         total = len(header) + plen.value
         return memoryview((C.c_ubyte * total).from_address(base + start)).cast("B")
 
+    def _compact_header(self, fmt, max_bits, bpc, plen) -> bytes:
+        return b"".join([bytes([1, fmt]), _bincode_varint(self.level), _bincode_varint(self.nrow), _bincode_varint(self.ncol),
+                         _bincode_varint(max_bits), _bincode_varint(bpc), _bincode_varint(plen)])
+
+    @staticmethod
+    def to_compact_bytes_many(mats) -> list:
+        """`to_compact_bytes` of every matrix (the operands stay as they are), through ONE batched store per context."""
+        return GpuDCRTPolyMatrix.into_compact_bytes_many([m.clone() for m in mats])
+
+    @staticmethod
+    def into_compact_bytes_many(mats) -> list:
+        """[m.into_compact_bytes() for m in mats] - the same framed bytes per matrix - with the device work of all
+        matrices of a context in ONE gpupoly_matrix_store_compact_bytes_many call (what `get_lookup_buffer`,
+        src/storage/write.rs:724-793, does with a to_compact_bytes per matrix).  Every matrix ends in the coefficient
+        domain, like after `into_compact_bytes`.  The payloads land in this thread's pinned staging buffer; a buffer
+        that is too small is retried once with the total the first call reported."""
+        mats = list(mats)
+        out = [None] * len(mats)
+        by_ctx = {}
+        for j, m in enumerate(mats):
+            by_ctx.setdefault(m.params.ctx_raw().value, []).append(j)
+        for idx in by_ctx.values():
+            n = len(idx)
+            fmts = [GPU_POLY_FORMAT_EVAL if mats[j].is_ntt else GPU_POLY_FORMAT_COEFF for j in idx]
+            cap = 0
+            for j in idx:
+                m = mats[j]
+                bits_upper = sum(q.bit_length() for q in m.params.moduli()[: m.level + 1])
+                cap += ((m.nrow * m.ncol * m.params.ring_dimension() * bits_upper + 7) // 8 + 7) // 8 * 8
+                m._touch()  # an EVAL matrix is taken to the coefficient domain in place
+            raws = (C.c_void_p * n)(*[mats[j].raw for j in idx])
+            bits, bpcs = (C.c_uint16 * n)(), (C.c_uint16 * n)()
+            offs, lens, total = (C.c_size_t * n)(), (C.c_size_t * n)(), C.c_size_t(0)
+            want = min(max(cap, 1), max(_pinned_capacity(), (cap + 7) // 8, 1 << 16))
+            for attempt in range(2):
+                base = _pinned_buffer(want)
+                st = _ffi.lib().gpupoly_matrix_store_compact_bytes_many(raws, n, C.c_void_p(base), want, bits, bpcs, offs, lens, C.byref(total))
+                if st != 0 and attempt == 0 and want < cap and "payload buffer too small" in _ffi.last_error_string():
+                    want = min(cap, total.value if total.value > want else cap)
+                    continue
+                break
+            check_status(st, "gpupoly_matrix_store_compact_bytes_many")
+            for k, j in enumerate(idx):
+                mats[j].is_ntt = False
+                out[j] = mats[j]._compact_header(fmts[k], bits[k], bpcs[k], lens[k]) + C.string_at(base + offs[k], lens[k])
+        return out
+
+    @classmethod
+    def from_compact_bytes_many(cls, params, blobs) -> list:
+        """[from_compact_bytes(params, b) for b in blobs] with the device work in ONE
+        gpupoly_matrix_load_compact_bytes_many call.  Bytes after a frame are ignored, as `bincode::decode_from_slice`
+        ignores them (gpu_dcrt_poly.rs:1004-1017): a slot of a lookup buffer is padded to the longest matrix."""
+        blobs = list(blobs)
+        n = len(blobs)
+        if n == 0:
+            return []
+        outs, fmts, keep = [], [], []
+        ptrs, lens, widths = (C.c_void_p * n)(), (C.c_size_t * n)(), (C.c_uint16 * n)()
+        for j, data in enumerate(blobs):
+            version, fmt = data[0], data[1]
+            assert version == 1, f"Unsupported compact matrix version: {version}"
+            assert fmt in (GPU_POLY_FORMAT_COEFF, GPU_POLY_FORMAT_EVAL), f"Invalid compact matrix format tag: {fmt}"
+            pos = 2
+            level, pos = _bincode_read_varint(data, pos)
+            nrow, pos = _bincode_read_varint(data, pos)
+            ncol, pos = _bincode_read_varint(data, pos)
+            max_bits, pos = _bincode_read_varint(data, pos)
+            bpc, pos = _bincode_read_varint(data, pos)
+            plen, pos = _bincode_read_varint(data, pos)
+            assert pos + plen <= len(data), "truncated compact bytes"
+            assert level < params.crt_depth(), f"invalid compact matrix level: {level}"
+            assert bpc == (max_bits + 7) // 8, "compact bytes_per_coeff mismatch"
+            payload = bytes(data[pos : pos + plen]) if plen else b"\0"
+            keep.append(payload)  # the pointers below must outlive the call
+            ptrs[j] = C.cast(C.c_char_p(payload), C.c_void_p)
+            lens[j], widths[j] = plen, max_bits
+            outs.append(cls(params, nrow, ncol, level, False))
+            fmts.append(fmt)
+        raws = (C.c_void_p * n)(*[m.raw for m in outs])
+        st = _ffi.lib().gpupoly_matrix_load_compact_bytes_many(raws, n, ptrs, lens, widths)
+        check_status(st, "gpupoly_matrix_load_compact_bytes_many")
+        for m, fmt in zip(outs, fmts):
+            m.is_ntt = False
+            if fmt == GPU_POLY_FORMAT_EVAL:
+                m.ntt_all_in_place()
+        return outs
+
     @classmethod
     def zero_compact_bytes(cls, params, nrow, ncol, level, is_ntt, max_coeff_bits) -> bytes:
         """Compact bytes of a zero matrix without touching the device (gpu_dcrt_poly.rs:1681-1710)."""
