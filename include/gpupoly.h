@@ -157,6 +157,36 @@ int gpu_poly_load_compact_bytes(GpuMatrix *poly, const uint8_t *payload, size_t 
  * memory allows, then one product into `out`.  The EVAL-form digit matrix IS written once and read once (a full
  * fusion would need 8 x 16384 accumulators per workgroup).                          */
 int gpupoly_matrix_mul_decompose(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs, uint32_t base_bits);
+/* Several left operands against ONE G^-1(rhs), each with its addend (extension):
+ *   outs[j] = lhss[j] * G^-1(rhs) + addends[j] o scalars[j]        for all j < n
+ * - for every j the residues, bit for bit, of gpupoly_matrix_mul_decompose(tmp, lhss[j], rhs, base_bits),
+ * gpu_matrix_mul_scalar(tmp2, addends[j], scalars[j]), gpu_matrix_add(outs[j], tmp, tmp2).  Replaces the repeated
+ * decompositions of one matrix in the BGG multiplication gates: BggEncoding::mul (src/bgg/encoding.rs:125-145: vector and
+ * public-key matrix against one other.pubkey.matrix, then + other.vector * plaintext), large_scalar_mul / matrix_mul
+ * (:191-219), BggPolyEncoding::mul (src/bgg/poly_encoding.rs:327-357: one mul_decompose per slot, each followed by
+ * + rhs_vector * lhs_plaintext, and one more for the keys at :341), src/io/diamond_io.rs:1924-1926 and
+ * src/we/diamond_we.rs:456,538.  G^-1(rhs) is built ONCE per call with the fused digit transform - in as few column chunks
+ * as the memory budget allows (the rule of gpupoly_matrix_mul_decompose; MXX_HIP_MUL_DECOMPOSE_MANY_BUDGET=<bytes>
+ * overrides it for this entry) - and read by one grouped product per 64 operands and chunk, whose epilogue adds
+ * addend o scalar and stores into each operand's own output: no stacking or splitting copies, no mul_scalar or add launch.
+ *   rhs         r x c, COEFF or EVAL, left untouched (as with gpu_matrix_decompose_base); k = ceil(crt_bits/base_bits) * limbs
+ *   lhss[j]     rows_j x (r*k), EVAL; rows_j may differ from operand to operand and may be 0
+ *   outs[j]     rows_j x c, made by the caller, tagged EVAL on success
+ *   addends     NULL, or addends[j] NULL: no addend; else rows_j x c, EVAL
+ *   scalars     NULL, or scalars[j] NULL: the addend is added as it is; else 1 x 1, EVAL, multiplies every entry of
+ *               addends[j] point-wise before the sum
+ * One context and one level per call; n = 0 does nothing; r*k = 0 gives the addend term alone.  Enqueued on the context's
+ * stream, the host does not block; temporaries come from the context's allocator and are released stream-ordered.
+ * PACKED24 operands are unpacked first.  Every operand height goes through the grouped kernel in tiles of at most 8
+ * stacked rows: it is built for few-row operands (encodings, key matrices of small d); operands of 24 rows and more are
+ * better served by one gpupoly_matrix_mul_decompose each.
+ * Refused, with nothing launched and every outs[j] (contents AND tag) untouched, all checked for every j before the first
+ * launch: a null outs, lhss or rhs with n > 0, a null outs[j] or lhss[j]; a context or level mismatch or a shape mismatch
+ * in any j; an lhss[j], addends[j] or scalars[j] not in EVAL form; a scalars[j] without an addends[j]; an output that
+ * aliases any input or another output; base_bits of 0 or >= 63.                                                      */
+int gpupoly_matrix_mul_decompose_many(GpuMatrix *const *outs, const GpuMatrix *const *lhss,
+                                      const GpuMatrix *const *addends, const GpuMatrix *const *scalars, size_t n,
+                                      const GpuMatrix *rhs, uint32_t base_bits);
 /* outs[i] = lhss[i] * rhss[i], i < count: independent products of one context and level (all EVAL) in one call.  Small
  * products - a level of circuit gates on a small ring, where every product is a launch-latency-bound kernel - go out
  * up to 64 per launch; large ones run one by one through the tuned kernels.  No output may be another product's

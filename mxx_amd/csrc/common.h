@@ -52,6 +52,8 @@ struct EnvSwitches {
     bool serde_general = false;   // MXX_HIP_SERDE=general: compact store always through the kernels that carry the general Garner path (tests, A/B)
     bool rng_compat = false;      // MXX_HIP_RNG_COMPAT=reference: sample_distribution* keyed exactly as the reference's device RNG (sampling.hip)
     bool pack24 = true;           // MXX_HIP_PACK24=0|off: uniform samples stay in 4-byte words (layout.hip)
+    size_t mul_decompose_many_budget = 0;  // MXX_HIP_MUL_DECOMPOSE_MANY_BUDGET=<bytes>: digit-matrix budget of gpupoly_matrix_mul_decompose_many
+                                           // alone (0 = a third of the free memory, at least 8 GiB; tests reach its column chunks with it)
     void load();
 };
 

@@ -1420,6 +1420,44 @@ class GpuDCRTPolyMatrix:
             out.copy_block_from(prod, 0, c0, 0, 0, self.nrow, c1 - c0)
         return out
 
+    @staticmethod
+    def mul_decompose_many(lhss, rhs, addends=None, scalars=None) -> list:
+        """[l.mul_decompose(rhs) + a.mul_scalar(s) for l, a, s in zip(lhss, addends, scalars)] through
+        `gpupoly_matrix_mul_decompose_many`: G^-1(rhs) is built once for all operands and the addend term rides in the
+        product's epilogue (the BGG multiplication gates: src/bgg/encoding.rs:125-145,191-219,
+        src/bgg/poly_encoding.rs:327-357).  `addends` / `scalars` may be None or hold None entries: no addend / the
+        addend as it is.  The reference's per-operand sequence runs when its chunk switch is set."""
+        n = len(lhss)
+        addends = [None] * n if addends is None else list(addends)
+        scalars = [None] * n if scalars is None else list(scalars)
+        assert len(addends) == n and len(scalars) == n, "mul_decompose_many: one addend / scalar slot per operand"
+        if n == 0:
+            return []
+        scalars = [s.inner if hasattr(s, "inner") else s for s in scalars]
+        k = rhs.params.modulus_digits()
+        for l_, a_, s_ in zip(lhss, addends, scalars):
+            assert l_.params == rhs.params and l_.ncol == rhs.nrow * k, "mul_decompose_many: operand mismatch"
+            assert a_ is None or (a_.nrow, a_.ncol) == (l_.nrow, rhs.ncol), "mul_decompose_many: addend shape"
+            assert s_ is None or a_ is not None, "mul_decompose_many: a scalar needs an addend"
+        if mul_decompose_column_chunk_width_is_set():
+            outs = []
+            for l_, a_, s_ in zip(lhss, addends, scalars):
+                out = l_.mul_decompose(rhs)
+                if a_ is not None:
+                    out = out + (a_.mul_scalar(s_) if s_ is not None else a_.ensure_eval())
+                outs.append(out)
+            return outs
+        # converted copies stay referenced until the call returns
+        ls = [m.ensure_eval() for m in lhss]
+        ads = [None if m is None else m.ensure_eval() for m in addends]
+        scs = [None if m is None else m.ensure_eval() for m in scalars]
+        outs = [GpuDCRTPolyMatrix(rhs.params, l_.nrow, rhs.ncol, l_.level, True) for l_ in ls]
+        raw = lambda m: None if m is None else (m.raw.value if hasattr(m.raw, "value") else m.raw)
+        arr = lambda ms: (C.c_void_p * n)(*[raw(m) for m in ms])
+        st = _ffi.lib().gpupoly_matrix_mul_decompose_many(arr(outs), arr(ls), arr(ads), arr(scs), n, rhs.raw, rhs.params.base_bits())
+        check_status(st, "gpupoly_matrix_mul_decompose_many")
+        return outs
+
     def mul_decompose_small(self, other) -> "GpuDCRTPolyMatrix":
         k = -(-self.params.crt_bits() // self.params.base_bits())
         assert self.ncol == other.nrow * k
