@@ -417,6 +417,47 @@ int gpupoly_matrix_store_compact_bytes_many(GpuMatrix *const *mats, size_t n, ui
                                             size_t *out_payload_offsets, size_t *out_payload_lens, size_t *out_total_len);
 int gpupoly_matrix_load_compact_bytes_many(GpuMatrix *const *mats, size_t n, const uint8_t *const *payloads,
                                            const size_t *payload_lens, const uint16_t *max_coeff_bits);
+/* Products by monomials on the device (extension).  Shifts are any uint64_t, taken as shift & (2N - 1):
+ * x^N = -1 in Z_q[x] / (x^N + 1).  Every slot-packing step of the reference's callers is such a sum, one host loop
+ * iteration per term: collapse_slot_matrices (src/noise_refresh/naive_vec.rs:1983-1998: sum_slot M_slot *
+ * const_rotate_poly(slot), num_slots == ring_dim terms), the slot-transfer reduce step
+ * (src/slot_transfer/bgg_poly_encoding.rs:362-380: c_gate + sum_src pre_slot_src * x^src), the target of slot_reduce on the
+ * GPU path (src/slot_transfer/bgg_pubkey_gpu.rs:448-464: lhs_chunk - sum_src (...) * x^src) and rotate_gate /
+ * monomial_scalar (src/circuit/poly_circuit/construction.rs:352-357, src/slot_transfer/bgg_poly_encoding.rs:706,942).  Per
+ * term that loop builds a one-hot vector on the host, uploads and transforms it (from_u32s / from_coeffs;
+ * const_rotate_poly, src/poly/mod.rs:151-156, goes through coeffs() - a host CRT of N big integers - first), then
+ * gpu_matrix_mul_scalar and gpu_matrix_add: three launches, one upload, five passes over a matrix.
+ *
+ * gpupoly_matrix_fill_monomial: every entry of `out` becomes x^shift, written directly in `format` - COEFF: the one-hot
+ * vector with +1 at coefficient shift mod N, or -1 (as q - 1 in every limb) when shift mod 2N >= N; EVAL: slot k of limb l
+ * is psi_l^(shift (2 bitrev(k) + 1)), read from the context's forward twiddle table.  `out` is tagged with `format`.
+ * Replaces const_rotate_poly and the from_u32s(one-hot) idiom.  Enqueued on the context's stream; 0 rows or 0 columns
+ * succeed with nothing launched.  Refused, with nothing launched and `out` untouched: a null `out`, a `format` that is
+ * neither GPU_POLY_FORMAT_COEFF nor GPU_POLY_FORMAT_EVAL.                                                              */
+int gpupoly_matrix_fill_monomial(GpuMatrix *out, uint64_t shift, int format);
+/* out = in * x^shift: gpupoly_matrix_monomial_sum with n = 1, no addend and negate = 0 - its semantics and refusals
+ * (`out` must not overlap `in`; a null `out` or `in` is refused).                                                      */
+int gpupoly_matrix_mul_monomial(GpuMatrix *out, const GpuMatrix *in, uint64_t shift);
+/* out = addend + sgn * sum_{j<n} mats[j] * x^shifts[j],  sgn = negate ? -1 : +1.
+ * One context, one level (it may be below the context's top level) and one shape for `out`, `addend` and every mats[j];
+ * all of mats[j] and `addend` share one format, COEFF or EVAL, and `out` is tagged with it on success.  `addend` may be
+ * NULL; out == addend accumulates in place (every word is read and written by the same thread).  The residues are, bit
+ * for bit, those of the existing sequence - in EVAL gpupoly_matrix_fill_monomial, gpu_matrix_mul_scalar and gpu_matrix_add
+ * / gpu_matrix_sub per term, in COEFF the inverse transform of that sequence on the transformed operands: everything is
+ * exact modular arithmetic on canonical residues.  In EVAL each term is a point-wise product by the twiddle-table entry
+ * psi^(shift (2 bitrev(k) + 1)), accumulated lazily; in COEFF a signed rotation: coefficient i receives +a[m] for
+ * m = (i - shift) mod 2N < N and -a[m - N] otherwise.  Up to 64 terms go into one launch: a call on words-layout operands
+ * issues ceil(n / 64) kernel launches, later groups reading `out` as their addend.  PACKED24 operands are unpacked first.
+ * Enqueued on the context's stream, the host does not block; no temporaries are allocated.
+ * n = 0 with an addend copies the addend (residues and tag); n = 0 without an addend gives zeros and leaves `out`'s tag as
+ * it was.  0 rows or 0 columns succeed with nothing launched.
+ * Refused, with nothing launched and `out` (contents AND tag) untouched, every condition checked for every j before the
+ * first launch: a null `out`; a null `mats` or `shifts` with n > 0; a null mats[j]; a context, level or shape mismatch of
+ * `addend` or any mats[j] with `out`; mixed formats among mats and addend; `out` overlapping any mats[j] (row views share
+ * their parent's storage: gpupoly_matrix_row_view); an `addend` that overlaps `out` without being the very same block; a
+ * matrix of more than 2^31 (polynomial, 64-slot block) pairs.                                                          */
+int gpupoly_matrix_monomial_sum(GpuMatrix *out, const GpuMatrix *addend, const GpuMatrix *const *mats,
+                                const uint64_t *shifts, size_t n, int negate);
 /* kernel launches issued by the library since it was loaded (every context; copies / memsets not counted): bench.py
  * reports launches per step for the launch-bound small-ring chain                                              */
 uint64_t gpupoly_launch_count(void);

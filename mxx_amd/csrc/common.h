@@ -253,6 +253,15 @@ void *words_ptr(const GpuMatrix *m);
 // holds ctx->layout_mutex from this call until its launch is enqueued (words_ptr must not be called meanwhile).
 const void *packed24_ptr(const GpuMatrix *m, bool *packed);
 inline size_t packed24_bytes(const GpuMatrix *m) { return m->bytes / 4 * 3; }
+// [storage, storage + bytes held now) of two matrices overlap (row views share their parent's storage)
+inline bool storage_overlaps(const GpuMatrix *x, const GpuMatrix *y) {
+    if (x == y) return true;
+    if (!x->storage || !y->storage || x->bytes == 0 || y->bytes == 0) return false;
+    const size_t xb = x->layout.v.load(std::memory_order_acquire) == GPU_MATRIX_LAYOUT_PACKED24 ? packed24_bytes(x) : x->bytes;
+    const size_t yb = y->layout.v.load(std::memory_order_acquire) == GPU_MATRIX_LAYOUT_PACKED24 ? packed24_bytes(y) : y->bytes;
+    const char *xs = static_cast<const char *>(x->storage), *ys = static_cast<const char *>(y->storage);
+    return xs < ys + yb && ys < xs + xb;
+}
 // whether a fresh uniform sample into m may be stored PACKED24
 bool pack24_eligible(const GpuMatrix *m);
 // m's words (EVAL after the caller's transform) -> PACKED24 storage in a new block; the words block is freed on the stream.

@@ -228,16 +228,6 @@ static int launch_group(GpuContext *ctx, const MulGroupArgs &args, uint32_t item
 #undef MXX_GROUP
 }
 
-// [storage, storage + bytes held now) of two matrices overlap (row views share their parent's storage)
-static bool storage_overlaps(const GpuMatrix *x, const GpuMatrix *y) {
-    if (x == y) return true;
-    if (!x->storage || !y->storage || x->bytes == 0 || y->bytes == 0) return false;
-    const size_t xb = x->layout.v.load(std::memory_order_acquire) == GPU_MATRIX_LAYOUT_PACKED24 ? packed24_bytes(x) : x->bytes;
-    const size_t yb = y->layout.v.load(std::memory_order_acquire) == GPU_MATRIX_LAYOUT_PACKED24 ? packed24_bytes(y) : y->bytes;
-    const char *xs = static_cast<const char *>(x->storage), *ys = static_cast<const char *>(y->storage);
-    return xs < ys + yb && ys < xs + xb;
-}
-
 extern "C" int gpupoly_matrix_mul_decompose_many(GpuMatrix *const *outs, const GpuMatrix *const *lhss,
                                                  const GpuMatrix *const *addends, const GpuMatrix *const *scalars, size_t n,
                                                  const GpuMatrix *rhs, uint32_t base_bits) {

@@ -185,7 +185,7 @@ static GpuMatrix row_block(const GpuMatrix *m, size_t row, size_t rows) {
     return v;
 }
 
-static bool storage_overlaps(const GpuMatrix *a, const GpuMatrix *b) {
+static bool words_overlap(const GpuMatrix *a, const GpuMatrix *b) {
     if (!a->bytes || !b->bytes) return false;
     const char *a0 = static_cast<const char *>(words_ptr(a)), *b0 = static_cast<const char *>(words_ptr(b));
     if (!a0 || !b0) return false;
@@ -300,8 +300,8 @@ extern "C" int gpupoly_trapdoor_preimage_many(const GpuMatrix *re, const GpuP1Co
     }
     for (size_t j = 0; j < n; ++j) {
         const GpuMatrix *o = outs[j];
-        bool alias = storage_overlaps(o, re) || storage_overlaps(o, public_matrix);
-        for (size_t i = 0; i < n && !alias; ++i) alias = storage_overlaps(o, targets[i]) || (i != j && storage_overlaps(o, outs[i]));
+        bool alias = words_overlap(o, re) || words_overlap(o, public_matrix);
+        for (size_t i = 0; i < n && !alias; ++i) alias = words_overlap(o, targets[i]) || (i != j && words_overlap(o, outs[i]));
         if (alias) return fail("output " + std::to_string(j) + " aliases an input or another output");
     }
     // what the segmented samplers cover (include/gpupoly.h); the caller issues such requests one by one

@@ -1159,6 +1159,53 @@ class GpuDCRTPolyMatrix:
         check_status(_ffi.lib().gpu_matrix_mul_scalar(out.raw, lhs.raw, s.raw), "gpu_matrix_mul_scalar")
         return out
 
+    @classmethod
+    def monomial(cls, params, nrow, ncol, shift, eval_format: bool = True, level=None) -> "GpuDCRTPolyMatrix":
+        """Extension: every entry x^shift (shift mod 2N, x^N = -1), written on the device directly in the wanted form
+        (gpupoly_matrix_fill_monomial): no one-hot host vector, no upload, no transform."""
+        out = cls(params, nrow, ncol, params.crt_depth() - 1 if level is None else level, eval_format)
+        fmt = GPU_POLY_FORMAT_EVAL if eval_format else GPU_POLY_FORMAT_COEFF
+        shift = int(shift) % (2 * params.ring_dimension())
+        check_status(_ffi.lib().gpupoly_matrix_fill_monomial(out.raw, shift, fmt), "gpupoly_matrix_fill_monomial")
+        return out
+
+    def mul_monomial(self, shift) -> "GpuDCRTPolyMatrix":
+        """self * x^shift in one pass, in the domain self is in (gpupoly_matrix_mul_monomial): a twiddle-table look-up per
+        slot in EVAL, a signed rotation in COEFF.  rotate_gate / monomial_scalar of the reference
+        (src/circuit/poly_circuit/construction.rs:352-357) build the monomial on the host and multiply."""
+        out = GpuDCRTPolyMatrix(self.params, self.nrow, self.ncol, self.level, self.is_ntt)
+        shift = int(shift) % (2 * self.params.ring_dimension())
+        check_status(_ffi.lib().gpupoly_matrix_mul_monomial(out.raw, self.raw, shift), "gpupoly_matrix_mul_monomial")
+        return out
+
+    @staticmethod
+    def monomial_sum(mats, shifts, addend=None, negate: bool = False, out=None) -> "GpuDCRTPolyMatrix":
+        """addend +- sum_j mats[j] * x^shifts[j] in ceil(n / 64) launches (gpupoly_matrix_monomial_sum): the slot-packing
+        sums of collapse_slot_matrices (src/noise_refresh/naive_vec.rs:1983-1998) and the slot-transfer reduce steps
+        (src/slot_transfer/bgg_poly_encoding.rs:362-380, src/slot_transfer/bgg_pubkey_gpu.rs:448-464).  All operands share
+        one shape, level and domain, which the result takes.  `out`: write there (it may be `addend`: accumulate in place;
+        never one of `mats`); a fresh matrix otherwise."""
+        mats, shifts = list(mats), list(shifts)
+        n = len(mats)
+        assert len(shifts) == n, "monomial_sum: one shift per matrix"
+        first = addend if addend is not None else (mats[0] if n else out)
+        if first is None:
+            raise ValueError("monomial_sum: no operand to take the shape from")
+        for m in mats + ([addend] if addend is not None else []):
+            first._check_binop(m, "monomial_sum")
+        if out is None:
+            out = GpuDCRTPolyMatrix(first.params, first.nrow, first.ncol, first.level, first.is_ntt)
+        else:
+            out._touch()
+        two_n = 2 * first.params.ring_dimension()
+        marr = (C.c_void_p * max(n, 1))(*[m.raw.value for m in mats])
+        sarr = (C.c_uint64 * max(n, 1))(*[int(s) % two_n for s in shifts])
+        st = _ffi.lib().gpupoly_matrix_monomial_sum(out.raw, None if addend is None else addend.raw, marr, sarr, n, 1 if negate else 0)
+        check_status(st, "gpupoly_matrix_monomial_sum")
+        if n or addend is not None:
+            out.is_ntt = first.is_ntt
+        return out
+
     def mul_scalar_intt(self, scalar) -> "GpuDCRTPolyMatrix":
         """INTT(self o scalar) in one kernel (extension: the product rides in the inverse transform's load)."""
         s = scalar.inner if hasattr(scalar, "inner") else scalar

@@ -81,6 +81,12 @@ class GpuDCRTPoly:
         return cls.from_biguints(params, [params.modulus() - 1])
 
     @classmethod
+    def const_rotate_poly(cls, params, shift: int) -> "GpuDCRTPoly":
+        """x^shift in EVAL form (src/poly/mod.rs:151-156, which goes through coeffs() and from_coeffs): written on the
+        device from the twiddle table (gpupoly_matrix_fill_monomial).  The shift is taken mod 2N, x^N = -1."""
+        return cls(GpuDCRTPolyMatrix.monomial(params, 1, 1, shift, True))
+
+    @classmethod
     def const_max(cls, params):
         return cls.from_biguints(params, [params.modulus() - 1] * params.ring_dimension())
 
