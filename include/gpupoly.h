@@ -30,6 +30,29 @@
  *   - EVAL format is OpenFHE's: slot k of limb i holds a(psi_i^(2*bitrev(k)+1))
  *     with psi_i the minimum primitive 2N-th root mod q_i (the reference CPU
  *     path's convention), so EVAL bytes are interchangeable with the CPU side.
+ *   - operands that share memory.  "Overlap" always means byte ranges of device storage, never object identity: a
+ *     row view (gpupoly_matrix_row_view) is another object over its parent's bytes and overlaps it.  "The same block"
+ *     means the same object, or a view with the same start and the same byte length.
+ *       1. Point-wise entries - gpu_matrix_add, gpu_matrix_sub, gpupoly_matrix_neg, gpu_matrix_mul_scalar,
+ *          gpupoly_matrix_mul_scalar_intt (its lhs), gpupoly_matrix_scale_round, the ADD / SUB / NEG / MUL_SCALAR
+ *          gates of gpupoly_batch and the addend of gpupoly_matrix_monomial_sum: an operand may be the same block as
+ *          the output, and the result is the out-of-place one (for mul_scalar also the 1x1 out == lhs == scalar).
+ *       2. Any other overlap of their output with an operand is refused.
+ *       3. Every other entry that reads matrices and writes one refuses any overlap between what it writes and what
+ *          it reads, the same block included (gpu_matrix_gauss_samp_gq_arb_base before its source is transformed).
+ *          gpupoly_matrix_add_rows / _ntt_add_rows are judged on the destination row block: an operand may be a view
+ *          of other rows of `out`.
+ *       4. Several outputs: the blocks of gpupoly_matrix_split_columns are pairwise disjoint and disjoint from the
+ *          source (the blocks of a concat may repeat, its output is disjoint from all of them); in
+ *          gpupoly_matrix_mul_batch and gpupoly_batch no output overlaps another product's / gate's output or
+ *          operand; gpupoly_matrix_all_gather_columns wants full[r] disjoint from local_blocks[r].
+ *       5. gpu_matrix_copy_block / gpu_matrix_add_block give the result of reading the whole source block before the
+ *          first write whenever `out` and `src` share storage (they stage it).  gpu_matrix_copy does nothing on the
+ *          same block and refuses a partial overlap.
+ *       6. Disjoint views of one parent are ordinary operands everywhere.
+ *     A call refused under this rule launches nothing and leaves the residues and the format tag of every matrix
+ *     passed to it as they were; its message names the entry point and contains "alias" or "overlap".
+ *     INTEGRATION.md lists every entry point that takes two or more matrices with its case.
  */
 #ifndef GPUPOLY_H
 #define GPUPOLY_H

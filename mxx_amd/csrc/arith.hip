@@ -691,7 +691,9 @@ extern "C" int gpupoly_matrix_add_rows(GpuMatrix *out, size_t dst_row, const Gpu
     if (out->cols != lhs->cols || dst_row > out->rows || lhs->rows > out->rows - dst_row)
         return set_error("gpupoly_matrix_add_rows: row block out of range");
     if (lhs->format != rhs->format) return set_error("gpupoly_matrix_add_rows: operands must share a format");
-    if (out == lhs || out == rhs) return set_error("gpupoly_matrix_add_rows: output must not alias an input");
+    // judged on the destination row block: an operand may be a view of other rows of `out`
+    if (row_block_overlaps(out, dst_row, lhs->rows, lhs) || row_block_overlaps(out, dst_row, lhs->rows, rhs))
+        return set_error("gpupoly_matrix_add_rows: output must not alias an input");
     const size_t poly_bytes = matrix_limbs(out) * static_cast<size_t>(out->ctx->N) * out->ctx->word_bytes;
     GpuMatrix view = matrix_view(out, dst_row * out->cols, lhs->rows, lhs->cols, poly_bytes);
     int rc = launch_elementwise<OP_ADD, false>(&view, lhs, rhs);
@@ -718,7 +720,8 @@ extern "C" int gpupoly_matrix_ntt_add_rows(GpuMatrix *out, size_t dst_row, GpuMa
         return set_error("gpupoly_matrix_ntt_add_rows: row block out of range");
     if (coeff->format != GPU_POLY_FORMAT_COEFF || addend->format != GPU_POLY_FORMAT_EVAL)
         return set_error("gpupoly_matrix_ntt_add_rows: expects a COEFF matrix and an EVAL addend");
-    if (out == coeff || out == addend) return set_error("gpupoly_matrix_ntt_add_rows: output must not alias an input");
+    if (row_block_overlaps(out, dst_row, coeff->rows, coeff) || row_block_overlaps(out, dst_row, coeff->rows, addend))
+        return set_error("gpupoly_matrix_ntt_add_rows: output must not alias an input");
     GpuContext *ctx = out->ctx;
     out->format = GPU_POLY_FORMAT_EVAL;  // the whole destination, as add_rows / copy_block do
     const size_t polys = matrix_polys(coeff);
@@ -751,6 +754,8 @@ extern "C" int gpu_matrix_add(GpuMatrix *out, const GpuMatrix *lhs, const GpuMat
     ABI_GUARD_BEGIN
     if (matrix_check_same_shape(out, lhs, "gpu_matrix_add") || matrix_check_same_shape(lhs, rhs, "gpu_matrix_add"))
         return 1;
+    if (partial_overlap(out, lhs) || partial_overlap(out, rhs))
+        return set_error("gpu_matrix_add: the output overlaps an operand without being the same block");
     int rc = launch_elementwise<OP_ADD, false>(out, lhs, rhs);
     if (rc) return rc;
     // The reference tags the result EVAL unconditionally (MatrixArith.cu:2694), which makes a later
@@ -765,6 +770,8 @@ extern "C" int gpu_matrix_sub(GpuMatrix *out, const GpuMatrix *lhs, const GpuMat
     ABI_GUARD_BEGIN
     if (matrix_check_same_shape(out, lhs, "gpu_matrix_sub") || matrix_check_same_shape(lhs, rhs, "gpu_matrix_sub"))
         return 1;
+    if (partial_overlap(out, lhs) || partial_overlap(out, rhs))
+        return set_error("gpu_matrix_sub: the output overlaps an operand without being the same block");
     int rc = launch_elementwise<OP_SUB, false>(out, lhs, rhs);
     if (rc) return rc;
     out->format = rhs->format;  // see gpu_matrix_add
@@ -777,6 +784,8 @@ extern "C" int gpu_matrix_sub(GpuMatrix *out, const GpuMatrix *lhs, const GpuMat
 extern "C" int gpupoly_matrix_neg(GpuMatrix *out, const GpuMatrix *src) {
     ABI_GUARD_BEGIN
     if (matrix_check_same_shape(out, src, "gpupoly_matrix_neg")) return 1;
+    if (partial_overlap(out, src))
+        return set_error("gpupoly_matrix_neg: the output overlaps the source without being the same block");
     int rc = launch_elementwise<OP_NEG, false>(out, src, src);
     if (rc) return rc;
     out->format = src->format;
@@ -793,6 +802,9 @@ extern "C" int gpu_matrix_mul_scalar(GpuMatrix *out, const GpuMatrix *lhs, const
     if (scalar->rows != 1 || scalar->cols != 1) return set_error("gpu_matrix_mul_scalar: scalar must be 1x1");
     if (lhs->format != GPU_POLY_FORMAT_EVAL || scalar->format != GPU_POLY_FORMAT_EVAL)
         return set_error("gpu_matrix_mul_scalar requires Eval format");
+    // the scalar is read by every entry: it may only share storage with `out` as the very block (a 1x1 out == lhs == scalar)
+    if (partial_overlap(out, lhs) || partial_overlap(out, scalar))
+        return set_error("gpu_matrix_mul_scalar: the output overlaps an operand without being the same block");
     int rc = launch_elementwise<OP_MUL, true>(out, lhs, scalar);
     if (rc) return rc;
     out->format = GPU_POLY_FORMAT_EVAL;
@@ -834,7 +846,7 @@ extern "C" int gpupoly_matrix_tensor(GpuMatrix *out, const GpuMatrix *lhs, const
         return set_error("gpupoly_matrix_tensor: shape mismatch");
     if (lhs->format != GPU_POLY_FORMAT_EVAL || rhs->format != GPU_POLY_FORMAT_EVAL)
         return set_error("gpupoly_matrix_tensor requires Eval format");
-    if (out == lhs || out == rhs) return set_error("gpupoly_matrix_tensor: output must not alias an input");
+    if (storage_overlaps(out, lhs) || storage_overlaps(out, rhs)) return set_error("gpupoly_matrix_tensor: output must not alias an input");
     out->format = GPU_POLY_FORMAT_EVAL;
     if (matrix_polys(out) == 0) return 0;
     if (ctx_activate(out->ctx)) return 1;
@@ -851,7 +863,7 @@ extern "C" int gpu_matrix_mul(GpuMatrix *out, const GpuMatrix *lhs, const GpuMat
         return set_error("gpu_matrix_mul: shape mismatch");
     if (lhs->format != GPU_POLY_FORMAT_EVAL || rhs->format != GPU_POLY_FORMAT_EVAL)
         return set_error("gpu_matrix_mul requires Eval format");
-    if (out == lhs || out == rhs) return set_error("gpu_matrix_mul: output must not alias an input");
+    if (storage_overlaps(out, lhs) || storage_overlaps(out, rhs)) return set_error("gpu_matrix_mul: output must not alias an input");
     out->format = GPU_POLY_FORMAT_EVAL;
     if (matrix_polys(out) == 0) return 0;
     if (ctx_activate(out->ctx)) return 1;
@@ -875,7 +887,7 @@ static int mul_tensor_identity_impl(GpuMatrix *out, const GpuMatrix *lhs, const 
     if (out->level != lhs->level || out->level != rhs->level) return set_error(std::string(who) + ": level mismatch");
     if (mode != 0 && (base_bits == 0 || base_bits >= 63)) return set_error(std::string(who) + ": invalid base_bits");
     if (identity_size == 0) return set_error(std::string(who) + ": identity_size must be positive");
-    if (out == lhs || out == rhs) return set_error(std::string(who) + ": output must not alias an input");
+    if (storage_overlaps(out, lhs) || storage_overlaps(out, rhs)) return set_error(std::string(who) + ": output must not alias an input");
     GpuContext *ctx = out->ctx;
     const size_t L = matrix_limbs(out);
     const size_t dpt = mode == 0 ? 1 : (ctx->crt_bits + base_bits - 1) / base_bits;
@@ -1076,13 +1088,14 @@ extern "C" int gpupoly_matrix_mul_batch(GpuMatrix *const *outs, const GpuMatrix 
             return set_error("gpupoly_matrix_mul_batch: shape mismatch");
         if (lhs->format != GPU_POLY_FORMAT_EVAL || rhs->format != GPU_POLY_FORMAT_EVAL)
             return set_error("gpupoly_matrix_mul_batch requires Eval format");
-        if (out == lhs || out == rhs) return set_error("gpupoly_matrix_mul_batch: output must not alias an input");
-        for (size_t o = 0; o < count; ++o)  // an output another product reads or writes: the products are unordered
-            if (o != p && (outs[o] == out || lhss[o] == out || rhss[o] == out))
-                return set_error("gpupoly_matrix_mul_batch: an output aliases another product's operand");
+        if (storage_overlaps(out, lhs) || storage_overlaps(out, rhs)) return set_error("gpupoly_matrix_mul_batch: output must not alias an input");
         max_work = std::max<uint64_t>(max_work, static_cast<uint64_t>(lhs->rows) * lhs->cols * rhs->cols * matrix_limbs(out) *
                                                     static_cast<uint64_t>(ctx->N));
     }
+    for (size_t p = 0; p < count; ++p)  // an output another product reads or writes, by bytes: the products are unordered
+        for (size_t o = 0; o < count; ++o)
+            if (o != p && (storage_overlaps(outs[p], outs[o]) || storage_overlaps(outs[p], lhss[o]) || storage_overlaps(outs[p], rhss[o])))
+                return set_error("gpupoly_matrix_mul_batch: an output aliases another product's operand");
     if (ctx_activate(ctx)) return 1;
     // large products fill the chip by themselves: one by one through the tuned kernels
     if (max_work > (1ull << 24)) {
@@ -1178,9 +1191,21 @@ extern "C" int gpupoly_batch(const GpuBatchOp *ops, size_t count, uint32_t base_
         if (!unary && !o.rhs) return set_error("gpupoly_batch: null right operand");
         if (!ctx) ctx = o.out->ctx;
         if (o.out->ctx != ctx || o.lhs->ctx != ctx || (!unary && o.rhs->ctx != ctx)) return set_error("gpupoly_batch: context mismatch");
+    }
+    // every overlap refusal before the first launch (bytes, not objects: row views share their parent's storage)
+    for (size_t i = 0; i < count; ++i) {
+        const GpuBatchOp &o = ops[i];
+        const bool unary = o.kind == GPUPOLY_OP_NEG || o.kind == GPUPOLY_OP_DECOMPOSE;
+        const bool pointwise = o.kind == GPUPOLY_OP_ADD || o.kind == GPUPOLY_OP_SUB || o.kind == GPUPOLY_OP_NEG || o.kind == GPUPOLY_OP_MUL_SCALAR;
+        // a gate's own operands: the point-wise gates may run in place on the very block, the others on disjoint storage
+        if (pointwise ? (partial_overlap(o.out, o.lhs) || (!unary && partial_overlap(o.out, o.rhs)))
+                      : (storage_overlaps(o.out, o.lhs) || (!unary && storage_overlaps(o.out, o.rhs))))
+            return set_error(pointwise ? "gpupoly_batch: an output overlaps its gate's operand without being the same block"
+                                       : "gpupoly_batch: an output aliases its gate's input");
         // the gates of a level are unordered: no output may be read or written by another gate
         for (size_t j = 0; j < count; ++j)
-            if (j != i && (ops[j].out == o.out || ops[j].lhs == o.out || ops[j].rhs == o.out))
+            if (j != i && (storage_overlaps(o.out, ops[j].out) || storage_overlaps(o.out, ops[j].lhs) ||
+                           (ops[j].kind != GPUPOLY_OP_NEG && ops[j].kind != GPUPOLY_OP_DECOMPOSE && storage_overlaps(o.out, ops[j].rhs))))  // unary: rhs is ignored
                 return set_error("gpupoly_batch: an output aliases another gate's operand");
     }
     if (ctx_activate(ctx)) return 1;

@@ -252,7 +252,7 @@ extern "C" int gpupoly_matrix_all_gather_columns(GpuComm *comm, const GpuMatrix 
             return set_error("gpupoly_matrix_all_gather_columns: row count mismatch");
         if (b->format != local_blocks[0]->format)
             return set_error("gpupoly_matrix_all_gather_columns: the blocks are in different formats");
-        if (b == f) return set_error("gpupoly_matrix_all_gather_columns: a block must not alias its output");
+        if (storage_overlaps(b, f)) return set_error("gpupoly_matrix_all_gather_columns: a block must not alias its output");
         col_start[r] = cols_total;
         cols_total += b->cols;
         max_cols = std::max(max_cols, b->cols);

@@ -262,6 +262,28 @@ inline bool storage_overlaps(const GpuMatrix *x, const GpuMatrix *y) {
     const char *xs = static_cast<const char *>(x->storage), *ys = static_cast<const char *>(y->storage);
     return xs < ys + yb && ys < xs + xb;
 }
+// ---- the operand overlap rule (include/gpupoly.h, conventions) -------------------------------------------------------
+// x and y are the very same block: the same object, or a view with the same start and byte length
+inline bool same_block(const GpuMatrix *x, const GpuMatrix *y) {
+    return x == y || (x->storage == y->storage && x->bytes == y->bytes);
+}
+// the point-wise entries: an operand may be out's very block (every word is read and written by the same thread); any
+// other overlap would be read after it is written
+inline bool partial_overlap(const GpuMatrix *out, const GpuMatrix *operand) {
+    return storage_overlaps(out, operand) && !same_block(out, operand);
+}
+// rows [row, row + rows) of m - the block a row-block writer fills - overlap y.  Nothing is unpacked: a PACKED24 matrix
+// has no views (gpupoly_matrix_row_view unpacks its parent, and a viewed matrix is never packed), so only m itself
+// shares its storage and the whole of it stands for the block
+inline bool row_block_overlaps(const GpuMatrix *m, size_t row, size_t rows, const GpuMatrix *y) {
+    if (m->layout.v.load(std::memory_order_acquire) == GPU_MATRIX_LAYOUT_PACKED24) return rows && m->cols && storage_overlaps(m, y);
+    if (!m->storage) return false;
+    const size_t poly_bytes = matrix_limbs(m) * static_cast<size_t>(m->ctx->N) * m->ctx->word_bytes;
+    GpuMatrix block;
+    block.storage = static_cast<char *>(m->storage) + row * m->cols * poly_bytes;
+    block.bytes = rows * m->cols * poly_bytes;
+    return storage_overlaps(&block, y);
+}
 // whether a fresh uniform sample into m may be stored PACKED24
 bool pack24_eligible(const GpuMatrix *m);
 // m's words (EVAL after the caller's transform) -> PACKED24 storage in a new block; the words block is freed on the stream.

@@ -127,7 +127,7 @@ static int decompose_impl(const GpuMatrix *src, uint32_t base_bits, GpuMatrix *o
     if (base_bits == 0) return set_error("base_bits must be non-zero in gpu_matrix_decompose_base");
     if (src->ctx != out->ctx || src->level != out->level)
         return set_error("context mismatch in gpu_matrix_decompose_base");
-    if (src == out) return set_error("gpu_matrix_decompose_base: output must not alias the source");
+    if (storage_overlaps(src, out)) return set_error("gpu_matrix_decompose_base: output must not alias the source");
     GpuContext *ctx = src->ctx;
     const int requested = out->format;
     const size_t L = matrix_limbs(src);
@@ -230,6 +230,8 @@ extern "C" int gpu_matrix_fill_small_decomposed_identity_chunk(GpuMatrix *out, c
     const size_t size = out->rows, chunk_count = scalar_by_digit->cols;
     if (chunk_idx >= chunk_count)
         return set_error("chunk_idx out of range in gpu_matrix_fill_small_decomposed_identity_chunk");
+    if (storage_overlaps(out, scalar_by_digit))
+        return set_error("gpu_matrix_fill_small_decomposed_identity_chunk: output must not alias scalar_by_digit");
     if (size == 0) return 0;
     if (size > 65535) return set_error("gpu_matrix_fill_small_decomposed_identity_chunk: size too large");
     GpuContext *ctx = out->ctx;

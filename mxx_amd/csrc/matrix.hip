@@ -166,6 +166,7 @@ int launch_copy_block(GpuMatrix *out, const GpuMatrix *src, size_t dst_row, size
         return set_error(std::string(who) + ": destination block out of bounds");
     // quirk kept from the reference: the whole destination is retagged with the
     // source's format even for a partial block (MatrixData.cu:519,531,558)
+    const bool shared = storage_overlaps(out, src);  // judged before anything is unpacked
     out->format = src->format;
     if (rows == 0 || cols == 0) return 0;
     GpuContext *ctx = out->ctx;
@@ -175,9 +176,9 @@ int launch_copy_block(GpuMatrix *out, const GpuMatrix *src, size_t dst_row, size
         size_t wb = static_cast<size_t>(ctx->word_bytes);
         const char *s = static_cast<const char *>(words_ptr(src)) + (src_row * src->cols + src_col) * wpp * wb;
         char *d = static_cast<char *>(words_ptr(out)) + (dst_row * out->cols + dst_col) * wpp * wb;
-        if (out == src) {
-            // overlapping self-copy: go through the kernel only when disjoint is not guaranteed
-            // (hipMemcpy2D has undefined overlap semantics); use a temp
+        if (shared) {
+            // the blocks may overlap (the same matrix, or row views of one parent): the source block is read in full
+            // before the first write (hipMemcpy2D has undefined overlap semantics); use a temp
             CtxBlock tmp(ctx);  // back to the cache at scope exit, error paths included
             size_t row_bytes = cols * wpp * wb;
             if (tmp.alloc(rows * row_bytes)) return 1;
@@ -205,19 +206,35 @@ int launch_copy_block(GpuMatrix *out, const GpuMatrix *src, size_t dst_row, size
     if (cols > 65535) return set_error(std::string(who) + ": block too wide");
     (void)entries;
     unsigned gx = grid_for(wpp, 256, 64);
+    // shared storage: the kernel's blocks would read source words that other blocks have already accumulated into, so the
+    // source block is staged first (tightly, rows x cols) and the kernel reads the copy
+    CtxBlock staged(ctx);
+    const void *src_words = words_ptr(src);
+    size_t from_cols = src->cols, from_row = src_row, from_col = src_col;
+    if (shared) {
+        const size_t wb = static_cast<size_t>(ctx->word_bytes), row_bytes = cols * wpp * wb;
+        if (staged.alloc(rows * row_bytes)) return 1;
+        const char *s = static_cast<const char *>(src_words) + (src_row * src->cols + src_col) * wpp * wb;
+        MXX_TRACED_COPY("copy_block (2-D runtime copy)", ctx->stream, 2.0 * rows * row_bytes,
+                        HIP_TRY(hipMemcpy2DAsync(staged.ptr, row_bytes, s, src->cols * wpp * wb, row_bytes, rows,
+                                                 hipMemcpyDeviceToDevice, ctx->stream)));
+        src_words = staged.ptr;
+        from_cols = cols;
+        from_row = from_col = 0;
+    }
     for (size_t r0 = 0; r0 < rows; r0 += rows_per_launch) {
         size_t rr = std::min(rows_per_launch, rows - r0);
         dim3 grid(gx, static_cast<unsigned>(rr * cols));
         MXX_TRACE_BYTES(3.0 * rr * cols * wpp * ctx->word_bytes);  // destination block read + written, source block read
         if (ctx->wide)
             MXX_LAUNCH((block_rect_kernel<uint64_t, true>), grid, dim3(256), 0, ctx->stream,
-                               static_cast<uint64_t *>(words_ptr(out)), static_cast<const uint64_t *>(words_ptr(src)),
-                               ctx->d_limbs, out->cols, src->cols, dst_row + r0, dst_col, src_row + r0, src_col, cols,
+                               static_cast<uint64_t *>(words_ptr(out)), static_cast<const uint64_t *>(src_words),
+                               ctx->d_limbs, out->cols, from_cols, dst_row + r0, dst_col, from_row + r0, from_col, cols,
                                wpp, (uint32_t)ctx->N);
         else
             MXX_LAUNCH((block_rect_kernel<uint32_t, true>), grid, dim3(256), 0, ctx->stream,
-                               static_cast<uint32_t *>(words_ptr(out)), static_cast<const uint32_t *>(words_ptr(src)),
-                               ctx->d_limbs, out->cols, src->cols, dst_row + r0, dst_col, src_row + r0, src_col, cols,
+                               static_cast<uint32_t *>(words_ptr(out)), static_cast<const uint32_t *>(src_words),
+                               ctx->d_limbs, out->cols, from_cols, dst_row + r0, dst_col, from_row + r0, from_col, cols,
                                wpp, (uint32_t)ctx->N);
         HIP_TRY(hipGetLastError());
     }
@@ -293,8 +310,9 @@ extern "C" void gpu_matrix_destroy(GpuMatrix *mat) {
 extern "C" int gpu_matrix_copy(GpuMatrix *dst, const GpuMatrix *src) {
     ABI_GUARD_BEGIN
     if (matrix_check_same_shape(dst, src, "gpu_matrix_copy")) return 1;
+    if (partial_overlap(dst, src)) return set_error("gpu_matrix_copy: the destination overlaps the source without being the same block");
     dst->format = src->format;
-    if (dst->bytes == 0 || dst == src) return 0;
+    if (dst->bytes == 0 || same_block(dst, src)) return 0;
     if (ctx_activate(dst->ctx)) return 1;
     MXX_TRACED_COPY("copy (device to device)", dst->ctx->stream, 2.0 * dst->bytes,
                     HIP_TRY(hipMemcpyAsync(words_ptr(dst), words_ptr(src), dst->bytes, hipMemcpyDeviceToDevice, dst->ctx->stream)));
@@ -321,7 +339,7 @@ extern "C" int gpu_matrix_add_block(GpuMatrix *out, const GpuMatrix *src, size_t
 extern "C" int gpupoly_matrix_transpose(GpuMatrix *out, const GpuMatrix *src) {
     ABI_GUARD_BEGIN
     if (!out || !src) return set_error("gpupoly_matrix_transpose: null matrix");
-    if (out == src) return set_error("gpupoly_matrix_transpose: output must not alias the source");
+    if (storage_overlaps(out, src)) return set_error("gpupoly_matrix_transpose: output must not alias the source");
     if (out->ctx != src->ctx || out->level != src->level) return set_error("gpupoly_matrix_transpose: context / level mismatch");
     if (out->rows != src->cols || out->cols != src->rows) return set_error("gpupoly_matrix_transpose: shape mismatch");
     out->format = src->format;
@@ -394,13 +412,17 @@ static int column_blocks(GpuMatrix *whole, GpuMatrix *const *blocks, size_t n, b
     for (size_t j = 0; j < n; ++j) {
         const GpuMatrix *b = blocks[j];
         if (!b) return set_error(std::string(who) + ": null block");
-        if (b == whole) return set_error(std::string(who) + ": a block must not alias the wide matrix");
+        if (storage_overlaps(b, whole)) return set_error(std::string(who) + ": a block must not alias the wide matrix");
         if (b->ctx != whole->ctx || b->level != whole->level) return set_error(std::string(who) + ": context / level mismatch");
         if (b->rows != whole->rows) return set_error(std::string(who) + ": blocks must have the wide matrix's row count");
         if (split ? false : b->format != blocks[0]->format) return set_error(std::string(who) + ": blocks must share one format");
         total += b->cols;
     }
     if (total != whole->cols) return set_error(std::string(who) + ": the blocks' columns must add up to the wide matrix's");
+    if (split)  // every block is written: two that share storage would have two writers (blocks of a concat may repeat)
+        for (size_t j = 0; j < n; ++j)
+            for (size_t i = 0; i < j; ++i)
+                if (blocks[i]->bytes && storage_overlaps(blocks[i], blocks[j])) return set_error(std::string(who) + ": two blocks overlap");
     if (split) {
         for (size_t j = 0; j < n; ++j) blocks[j]->format = whole->format;
     } else if (n) {
@@ -502,7 +524,7 @@ extern "C" int gpupoly_matrix_fill_identity(GpuMatrix *out, const GpuMatrix *sca
             return set_error("gpupoly_matrix_fill_identity: context/level mismatch");
         if (scalar->rows != 1 || scalar->cols != 1) return set_error("gpupoly_matrix_fill_identity: scalar must be 1x1");
         if (scalar->format != GPU_POLY_FORMAT_EVAL) return set_error("gpupoly_matrix_fill_identity requires an Eval scalar");
-        if (scalar == out) return set_error("gpupoly_matrix_fill_identity: output must not alias the scalar");
+        if (storage_overlaps(scalar, out)) return set_error("gpupoly_matrix_fill_identity: output must not alias the scalar");
     }
     out->format = GPU_POLY_FORMAT_EVAL;
     if (out->bytes == 0) return 0;

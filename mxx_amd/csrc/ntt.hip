@@ -229,6 +229,9 @@ extern "C" int gpupoly_matrix_mul_scalar_intt(GpuMatrix *out, const GpuMatrix *l
     if (scalar->rows != 1 || scalar->cols != 1) return set_error("gpupoly_matrix_mul_scalar_intt: scalar must be 1x1");
     if (lhs->format != GPU_POLY_FORMAT_EVAL || scalar->format != GPU_POLY_FORMAT_EVAL)
         return set_error("gpupoly_matrix_mul_scalar_intt requires Eval format");
+    // out may be lhs's very block (the transform is in place then); the scalar is read while `out` is written
+    if (partial_overlap(out, lhs) || storage_overlaps(out, scalar))
+        return set_error("gpupoly_matrix_mul_scalar_intt: the output overlaps lhs without being the same block, or the scalar");
     GpuContext *ctx = out->ctx;
     if (matrix_polys(out) == 0) {
         out->format = GPU_POLY_FORMAT_COEFF;

@@ -185,12 +185,8 @@ static GpuMatrix row_block(const GpuMatrix *m, size_t row, size_t rows) {
     return v;
 }
 
-static bool words_overlap(const GpuMatrix *a, const GpuMatrix *b) {
-    if (!a->bytes || !b->bytes) return false;
-    const char *a0 = static_cast<const char *>(words_ptr(a)), *b0 = static_cast<const char *>(words_ptr(b));
-    if (!a0 || !b0) return false;
-    return a0 < b0 + b->bytes && b0 < a0 + a->bytes;
-}
+// the shared byte-range test (common.h: nothing is unpacked for it); a matrix without entries overlaps nothing, itself included
+static bool words_overlap(const GpuMatrix *a, const GpuMatrix *b) { return a->bytes && b->bytes && storage_overlaps(a, b); }
 
 static int fail(const std::string &msg) { return set_error("gpupoly_trapdoor_preimage_many: " + msg); }
 

@@ -196,6 +196,8 @@ extern "C" int gpupoly_matrix_scale_round(GpuMatrix *out, const GpuMatrix *in, u
     if (out->level != L - 1) return set_error("gpupoly_matrix_scale_round: level mismatch (out must be at full level)");
     if (t >= kAuxM) return set_error("gpupoly_matrix_scale_round: unsupported t (t >= 2^64 - 59): use the host path");
     if (in->level != L - 1) return set_error("gpupoly_matrix_scale_round: unsupported input below full level: use the host path");
+    if (partial_overlap(out, in))
+        return set_error("gpupoly_matrix_scale_round: the output overlaps the input without being the same block");
     const size_t polys = matrix_polys(in);
     if (polys == 0) {
         out->format = GPU_POLY_FORMAT_COEFF;
@@ -228,7 +230,7 @@ extern "C" int gpupoly_matrix_scale_round(GpuMatrix *out, const GpuMatrix *in, u
     const void *src = words_ptr(in);
     if (in->format == GPU_POLY_FORMAT_EVAL) {
         // inverse transform in `out` (a copy of `in` first when they differ): `in` is left as it was
-        if (out != in)
+        if (!same_block(out, in))
             MXX_TRACED_COPY("copy (device to device)", ctx->stream, 2.0 * in->bytes,
                             HIP_TRY(hipMemcpyAsync(words_ptr(out), words_ptr(in), in->bytes, hipMemcpyDeviceToDevice, ctx->stream)));
         const int rc = launch_ntt(ctx, words_ptr(out), polys * static_cast<size_t>(L), L, true);

@@ -592,6 +592,8 @@ static int gauss_samp_impl(GpuMatrix *src, uint32_t base_bits, double c, GpuRngS
     const size_t k = static_cast<size_t>(dpt) * L;
     if (out->rows != src->rows * k || out->cols != src->cols)
         return set_error("output size mismatch in gpu_matrix_gauss_samp_gq_arb_base");
+    // before `src` is taken to the coefficient domain: a refused call leaves it as it was
+    if (storage_overlaps(src, out)) return set_error("gpu_matrix_gauss_samp_gq_arb_base: output must not alias the source");
     const size_t polys = matrix_polys(src);
     if (polys == 0) {
         out->format = GPU_POLY_FORMAT_EVAL;
@@ -956,6 +958,7 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
     const size_t m = cache->m, cols = tp2->cols;
     if (tp2->rows != m || out->rows != m || out->cols != cols)
         return set_error("tp2/out shape mismatch in gpu_matrix_sample_p1_full_cached");
+    if (storage_overlaps(tp2, out)) return set_error("gpu_matrix_sample_p1_full_cached: output must not alias tp2");
     if (cols == 0 || m == 0) {
         out->format = GPU_POLY_FORMAT_EVAL;
         return 0;
@@ -1053,6 +1056,10 @@ extern "C" int gpu_matrix_sample_p1_full(const GpuMatrix *a_mat, const GpuMatrix
                                          const GpuMatrix *tp2, double sigma, double s, double dgg_stddev,
                                          GpuRngSeed seed, GpuMatrix *out) {
     ABI_GUARD_BEGIN
+    // before the covariance kernels: `out` must not share storage with anything the call reads
+    if (out && ((tp2 && storage_overlaps(tp2, out)) || (a_mat && storage_overlaps(a_mat, out)) ||
+                (b_mat && storage_overlaps(b_mat, out)) || (d_mat && storage_overlaps(d_mat, out))))
+        return set_error("gpu_matrix_sample_p1_full: output must not alias an input");
     GpuP1CovarianceCache *cache = nullptr;
     int rc = gpu_matrix_create_p1_covariance_cache(a_mat, b_mat, d_mat, sigma, s, dgg_stddev, &cache);
     if (rc) return rc;
