@@ -37,6 +37,8 @@
  *          gpupoly_matrix_mul_scalar_intt (its lhs), gpupoly_matrix_scale_round, the ADD / SUB / NEG / MUL_SCALAR
  *          gates of gpupoly_batch and the addend of gpupoly_matrix_monomial_sum: an operand may be the same block as
  *          the output, and the result is the out-of-place one (for mul_scalar also the 1x1 out == lhs == scalar).
+ *          Likewise the addend of gpupoly_matrix_mul_sum (gpupoly_matrix_mul_acc: `out` is its own addend); their
+ *          lhss[t] / rhss[t] fall under 3.
  *       2. Any other overlap of their output with an operand is refused.
  *       3. Every other entry that reads matrices and writes one refuses any overlap between what it writes and what
  *          it reads, the same block included (gpu_matrix_gauss_samp_gq_arb_base before its source is transformed).
@@ -481,6 +483,47 @@ int gpupoly_matrix_mul_monomial(GpuMatrix *out, const GpuMatrix *in, uint64_t sh
  * matrix of more than 2^31 (polynomial, 64-slot block) pairs.                                                          */
 int gpupoly_matrix_monomial_sum(GpuMatrix *out, const GpuMatrix *addend, const GpuMatrix *const *mats,
                                 const uint64_t *shifts, size_t n, int negate);
+/* Fused multiply-accumulate (extension):
+ *   out[:, dst_col .. dst_col + cols) = addend[:, dst_col .. dst_col + cols) + sgn * sum_{t<n} lhss[t] * rhss[t],
+ *   sgn = negate ? -1 : +1.
+ * The reference's callers almost never use a product by itself, they add it into something: one output chunk of
+ * src/lookup/ggh15/encoding.rs:205-298 is c_b0 M + c_b0 gy_mid + c_b0 v_mid + c_b0 vx_mid - c_b0 pre + sum_inner (input
+ * U_inner) v_rhs, written as five add_in_place(&(a * &b)) / x - (a * &b) steps (:224, :244, :255, :273) and an accumulation
+ * loop (:275-298); src/lookup/ggh15/pubkey_gpu.rs:408 (target_chunk.add_in_place(&(w_block_v * &v_idx_chunk))) and :494-505;
+ * src/lookup/lwe/encoding_gpu.rs:142-223 (two product families per column chunk, summed with add_in_place);
+ * src/sampler/trapdoor/gpu.rs:212 (g - (a_bar r + e)) and :286 (public_left p1 + public_right p2);
+ * src/gadgets/fhe/ring_gsw_montgomery_gpu.rs:80 (public_matrix randomizer + gadget plaintext); the per-chunk results are
+ * then glued with concat_columns_owned (src/slot_transfer/bgg_poly_encoding_gpu.rs:320-335,
+ * src/input_injector/diamond_gpu.rs:104-118).  Through gpu_matrix_mul each term is a product launch, an add or sub launch
+ * (three more passes over the output), a temporary, a neg launch for a negated term and a copy_block per chunk.
+ *   lhss[t]   r x k_t, EVAL;  rhss[t]  k_t x cols, EVAL.  k_t may differ from term to term and may be 0 (adds nothing)
+ *   out       r x C with dst_col + cols <= C; columns outside the block are not touched.  Tagged EVAL on success; when the
+ *             block is not the whole of `out`, `out` must already be tagged EVAL
+ *   addend    NULL, or r x C, EVAL; only its block is read.  With addend == NULL and negate the result is -sum
+ * One context and one level (it may be below the context's top level).  The residues are, bit for bit, those of the
+ * existing sequence - gpu_matrix_mul per term, gpu_matrix_add / gpu_matrix_sub (or gpupoly_matrix_neg), gpu_matrix_copy_block
+ * into place: everything is modular arithmetic on canonical residues, the order of accumulation cannot show.
+ * Up to 8 rows: one term-table kernel walks up to 64 terms per launch with lazy accumulators that carry across term
+ * boundaries, and its epilogue negates, adds the addend block and stores at dst_col - a call on words-layout operands
+ * issues ceil(n / 64) launches (one for n = 0 unless nothing is to be done), later launches reading out's block as their
+ * addend.  Above 8 rows every term runs gpu_matrix_mul's tuned kernels into one scratch matrix of the context's allocator
+ * (released stream-ordered) followed by one combine pass into the block.  PACKED24 operands are unpacked first.  Enqueued
+ * on the context's stream; the host does not block.
+ * Overlap: `addend` may be the same block as `out` (accumulate in place: every word is read and written by the same
+ * thread), any other overlap of `addend` with `out` is refused; `out` must not overlap any lhss[t] or rhss[t], row views
+ * included; operands may repeat and may overlap each other.
+ * n = 0 with an addend copies the addend's block into out's block, n = 0 without one writes zeros there; r = 0 or
+ * cols = 0 succeed with nothing launched.
+ * Refused, with nothing launched and `out` (residues AND tag) untouched, every condition checked for every t before the
+ * first launch: a null `out`; null lhss / rhss with n > 0; a null lhss[t] / rhss[t]; a context or level mismatch;
+ * lhss[t]->cols != rhss[t]->rows, lhss[t]->rows != out->rows or rhss[t]->cols != cols; dst_col + cols > out->cols; an
+ * addend whose shape is not out's; an operand or addend not in EVAL form; a partial block into an `out` not tagged EVAL; the
+ * overlaps above (the message contains "overlaps").                                                                   */
+int gpupoly_matrix_mul_sum(GpuMatrix *out, size_t dst_col, size_t cols, const GpuMatrix *addend,
+                           const GpuMatrix *const *lhss, const GpuMatrix *const *rhss, size_t n, int negate);
+/* out += lhs * rhs (negate: out -= lhs * rhs): gpupoly_matrix_mul_sum(out, 0, out->cols, out, &lhs, &rhs, 1, negate), its
+ * semantics and refusals (a null matrix is refused; `out` is the addend and must be in EVAL form).                     */
+int gpupoly_matrix_mul_acc(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs, int negate);
 /* kernel launches issued by the library since it was loaded (every context; copies / memsets not counted): bench.py
  * reports launches per step for the launch-bound small-ring chain                                              */
 uint64_t gpupoly_launch_count(void);

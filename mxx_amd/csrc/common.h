@@ -54,6 +54,8 @@ struct EnvSwitches {
     bool pack24 = true;           // MXX_HIP_PACK24=0|off: uniform samples stay in 4-byte words (layout.hip)
     size_t mul_decompose_many_budget = 0;  // MXX_HIP_MUL_DECOMPOSE_MANY_BUDGET=<bytes>: digit-matrix budget of gpupoly_matrix_mul_decompose_many
                                            // alone (0 = a third of the free memory, at least 8 GiB; tests reach its column chunks with it)
+    char mul_sum_path = 0;        // MXX_HIP_MUL_SUM_PATH: 0 auto, 't' the term-table tile kernel at every height, 's' products into
+                                  // scratch + one combine pass per term above 8 rows (matmul_sum.hip; A/B, tests)
     void load();
 };
 

@@ -1206,6 +1206,56 @@ class GpuDCRTPolyMatrix:
             out.is_ntt = first.is_ntt
         return out
 
+    @staticmethod
+    def mul_sum(lhss, rhss, addend=None, negate: bool = False, out=None, dst_col: int = 0) -> "GpuDCRTPolyMatrix":
+        """addend +- sum_t lhss[t] * rhss[t] in one call (gpupoly_matrix_mul_sum), written into columns
+        [dst_col, dst_col + cols) of `out`: the `add_in_place(&(a * &b))` / `x - (a * &b)` chains and the chunk-by-chunk
+        concatenation of src/lookup/ggh15/encoding.rs:205-298, src/lookup/ggh15/pubkey_gpu.rs:408,494-505 and
+        src/lookup/lwe/encoding_gpu.rs:142-223.  All operands are in the NTT domain; lhss[t] is r x k_t, rhss[t] k_t x cols.
+        `out` None: a fresh r x cols matrix (`addend`, if any, has that shape; dst_col = 0).  Otherwise `out` is r x C,
+        `addend` None or r x C (it may be `out`: accumulate in place), and columns outside the block keep their contents."""
+        lhss, rhss = list(lhss), list(rhss)
+        n = len(lhss)
+        assert len(rhss) == n, "mul_sum: one right operand per left operand"
+        first = out if out is not None else (addend if addend is not None else (lhss[0] if n else None))
+        if first is None:
+            raise ValueError("mul_sum: no operand to take the shape from")
+        cols = rhss[0].ncol if n else first.ncol - dst_col
+        for l_, r_ in zip(lhss, rhss):
+            assert l_.params == first.params and r_.params == first.params, "mul_sum requires same params"
+            assert l_.level == first.level and r_.level == first.level, "mul_sum requires same level"
+            assert l_.is_ntt and r_.is_ntt, "mul_sum requires NTT domain"
+            assert l_.ncol == r_.nrow and l_.nrow == first.nrow and r_.ncol == cols, "mul_sum: term shape mismatch"
+        if out is None:
+            assert dst_col == 0, "mul_sum: dst_col needs an `out` to place the block in"
+            out = GpuDCRTPolyMatrix(first.params, first.nrow, cols, first.level, True)
+        else:
+            out._touch()
+        if addend is not None:
+            assert addend.is_ntt and (addend.nrow, addend.ncol) == (out.nrow, out.ncol), "mul_sum: the addend has out's shape, NTT domain"
+        larr = (C.c_void_p * max(n, 1))(*[m.raw.value for m in lhss])
+        rarr = (C.c_void_p * max(n, 1))(*[m.raw.value for m in rhss])
+        st = _ffi.lib().gpupoly_matrix_mul_sum(out.raw, dst_col, cols, None if addend is None else addend.raw, larr, rarr, n, 1 if negate else 0)
+        check_status(st, "gpupoly_matrix_mul_sum")
+        out.is_ntt = True
+        return out
+
+    def _mul_acc(self, lhs, rhs, negate: bool) -> None:
+        assert self.params == lhs.params == rhs.params, "mul_acc requires same params"
+        assert self.level == lhs.level == rhs.level, "mul_acc requires same level"
+        assert self.is_ntt and lhs.is_ntt and rhs.is_ntt, "mul_acc requires NTT domain"
+        assert lhs.ncol == rhs.nrow and (lhs.nrow, rhs.ncol) == (self.nrow, self.ncol), "mul_acc: shape mismatch"
+        self._touch()
+        check_status(_ffi.lib().gpupoly_matrix_mul_acc(self.raw, lhs.raw, rhs.raw, 1 if negate else 0), "gpupoly_matrix_mul_acc")
+
+    def mul_add_in_place(self, lhs, rhs) -> None:
+        """self += lhs * rhs in one call (gpupoly_matrix_mul_acc): `x.add_in_place(&(a * &b))` without the temporary."""
+        self._mul_acc(lhs, rhs, False)
+
+    def mul_sub_in_place(self, lhs, rhs) -> None:
+        """self -= lhs * rhs in one call (gpupoly_matrix_mul_acc)."""
+        self._mul_acc(lhs, rhs, True)
+
     def mul_scalar_intt(self, scalar) -> "GpuDCRTPolyMatrix":
         """INTT(self o scalar) in one kernel (extension: the product rides in the inverse transform's load)."""
         s = scalar.inner if hasattr(scalar, "inner") else scalar
