@@ -38,7 +38,8 @@
  *          gates of gpupoly_batch and the addend of gpupoly_matrix_monomial_sum: an operand may be the same block as
  *          the output, and the result is the out-of-place one (for mul_scalar also the 1x1 out == lhs == scalar).
  *          Likewise the addend of gpupoly_matrix_mul_sum (gpupoly_matrix_mul_acc: `out` is its own addend); their
- *          lhss[t] / rhss[t] fall under 3.
+ *          lhss[t] / rhss[t] fall under 3.  Likewise the addend of gpupoly_matrix_mul_gadget and of
+ *          gpupoly_matrix_gadget_mul; their lhs, scalar_1x1 and rhs fall under 3.
  *       2. Any other overlap of their output with an operand is refused.
  *       3. Every other entry that reads matrices and writes one refuses any overlap between what it writes and what
  *          it reads, the same block included (gpu_matrix_gauss_samp_gq_arb_base before its source is transformed).
@@ -524,6 +525,72 @@ int gpupoly_matrix_mul_sum(GpuMatrix *out, size_t dst_col, size_t cols, const Gp
 /* out += lhs * rhs (negate: out -= lhs * rhs): gpupoly_matrix_mul_sum(out, 0, out->cols, out, &lhs, &rhs, 1, negate), its
  * semantics and refusals (a null matrix is refused; `out` is the addend and must be in EVAL form).                     */
 int gpupoly_matrix_mul_acc(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs, int negate);
+/* Products with the gadget matrix without the matrix (extension).  G_d = I_d (x) g is d x d*k with
+ * dpt = ceil(crt_bits / base_bits), k = small ? dpt : dpt * (level + 1); its column gc = j*k + t*dpt + e (small: j*dpt + e)
+ * holds, in row j alone, the constant whose residue in limb l is (2^base_bits mod q_l)^e mod q_l when small || t == l and 0
+ * otherwise - exactly what gpu_matrix_fill_gadget / gpu_matrix_fill_small_gadget write.  Of its d * d*k polynomials of L*N
+ * words only d*k limb vectors of N words are non-zero, and every BGG+ relation of the reference's callers multiplies by it:
+ *   A - G x, A_chunk - G[:, chunk] y, -G[:, chunk], G x: src/lookup/lwe/pubkey_gpu.rs:205-210, src/lookup/lwe/pubkey.rs:449-471,520,
+ *     src/lookup/ggh15/pubkey_gpu.rs:393-395,474, src/io/diamond_io/utils.rs:612-616,1664, src/io/diamond_io.rs:684,702,1133,1704,1909,
+ *     src/we/diamond_we.rs:223-227, src/lookup/commit_eval.rs:510, src/lookup/debug.rs:290-291,500,
+ *     src/gadgets/fhe/ring_gsw_montgomery_gpu.rs:80, src/sampler/trapdoor/gpu.rs:212 (G - (A R + E)),
+ *     src/slot_transfer/bgg_poly_encoding.rs:874,1021,1166;
+ *   s G and s (G y): src/bgg/sampler_gpu.rs:149, src/bgg/sampler.rs:165,322,524, src/lookup/ggh15/mod.rs:438,
+ *     src/lookup/lwe/naive_vec.rs:340, src/slot_transfer/bgg_pubkey.rs:1904, src/slot_transfer/bgg_pubkey_gpu.rs:1607;
+ *   G D: src/lookup/ggh15/pubkey_gpu.rs:505 with :1264, src/commit/wee25.rs:718, src/matrix/gpu_dcrt_poly.rs:2114,2159,2406-2479,
+ *     src/sampler/trapdoor/sampler.rs:302,315;
+ *   a column chunk of G itself: gadget_matrix.slice(0, d, col_start, col_end).
+ * Through the existing entries each of these fills the whole of G, runs gpu_matrix_mul_scalar or gpu_matrix_mul over it, then
+ * gpu_matrix_add / _sub / gpupoly_matrix_neg and a gpu_matrix_copy_block: d*L times the bytes and, for s G, d times the ring
+ * multiplications.
+ *
+ * gpupoly_matrix_mul_gadget:
+ *   out[:, dst_col .. dst_col + cols) = addend[:, dst_col .. dst_col + cols) + sgn * (lhs * G_d[:, gadget_col .. gadget_col + cols)) o scalar,
+ *   sgn = negate ? -1 : +1.
+ *   lhs         r x d, EVAL; NULL: the identity I_d with d = out->rows
+ *   scalar_1x1  NULL: 1; else 1 x 1, EVAL, multiplies every entry point-wise
+ *   addend      NULL: 0; else out's shape, EVAL, only its block is read
+ *   out         r x C with dst_col + cols <= C; columns outside the block are not touched.  Tagged EVAL on success; when the
+ *               block is not the whole of `out`, `out` must already be tagged EVAL
+ * Word by word, for entry (i, c), limb l, slot s, with gadget_col + c = (j, t, e): addend +- lhs[i, j][l][s] * w(l, t, e) *
+ * scalar[l][s] mod q_l where small || t == l, addend +- 0 elsewhere.  With everything defaulted and cols = d*k the result is
+ * gpu_matrix_fill_gadget's, bit for bit; any window of it is the corresponding slice.
+ * When `addend` is the same block as `out` (A -= G x) the launch visits only the limb vectors G makes non-zero - r*cols of
+ * them (cols with lhs NULL; times L with `small`) - and the others are neither read nor written.  Otherwise one pass writes
+ * every limb vector of the block once: a hit reads its lhs vector and the scalar's and addend's, a miss copies the addend's
+ * vector or writes zeros.
+ *
+ * gpupoly_matrix_gadget_mul:  out = addend + sgn * G_d * rhs.
+ *   rhs     (d*k) x c, COEFF or EVAL (a constant scales whole limb vectors, so the domain does not matter)
+ *   addend  NULL, or d x c in rhs's format
+ *   out     d x c, tagged with rhs's format on success
+ * Limb l of entry (j, c) is sum_{e<dpt} w(l, l, e) * rhs[j*k + l*dpt + e, c][l] (small: row j*dpt + e): it reads limb l of dpt
+ * rows and nothing else - d*k*c*N words of rhs against d*k*c*L*N for the generic product - by Horner with the Shoup constant
+ * of 2^base_bits mod q_l.
+ *
+ * Both: one context and one level (it may be below the context's top level; k follows the level).  The residues are
+ * canonical and equal, bit for bit, to those of the existing sequence named above.  Enqueued on the context's stream, the
+ * host does not block; no temporaries are allocated (the first call for a base_bits builds a table of dpt weights per limb
+ * that the context keeps).  A call on words-layout operands issues exactly one kernel launch; PACKED24 operands are unpacked
+ * first.  r = 0, cols = 0, d = 0 or c = 0 succeed with nothing launched.
+ * Overlap: `addend` may be the same block as `out` (every word is read and written by the same thread), any other overlap
+ * of `addend` with `out` is refused; `out` must not overlap lhs, scalar_1x1 or rhs, row views included (the message contains
+ * "overlaps").
+ * Refused, with nothing launched and `out` (residues AND tag) untouched, everything checked before the launch, the message
+ * naming the entry: a null `out`, a null `rhs`; base_bits of 0 or >= 63; a context or level mismatch; lhs->rows != out->rows;
+ * dst_col + cols > out->cols; gadget_col + cols > d*k; rhs->rows != out->rows * k or rhs->cols != out->cols; an addend whose
+ * shape is not out's; an lhs, scalar or (mul_gadget) addend not in EVAL form; a scalar that is not 1 x 1; rhs and addend of
+ * different formats; a partial block into an `out` not tagged EVAL; the overlaps above.                                   */
+int gpupoly_matrix_mul_gadget(GpuMatrix *out, size_t dst_col, const GpuMatrix *lhs, const GpuMatrix *scalar_1x1,
+                              size_t gadget_col, size_t cols, const GpuMatrix *addend, int negate, uint32_t base_bits,
+                              int small);
+/* out = addend + sgn * G_d * rhs: the recomposition half of the pair above - its description, overlap rule (an addend that
+ * is `out` is allowed, any other overlap of `out` with addend or rhs is refused) and what is Refused are stated there.  The
+ * reference's callers: src/lookup/ggh15/pubkey_gpu.rs:505 with :1264, src/commit/wee25.rs:718 and the relation
+ * G * decompose(M) == M of src/matrix/gpu_dcrt_poly.rs:2114,2159; s G of src/bgg/sampler_gpu.rs:149 and A - G x of
+ * src/lookup/lwe/pubkey_gpu.rs:205-210 are gpupoly_matrix_mul_gadget's.                                              */
+int gpupoly_matrix_gadget_mul(GpuMatrix *out, const GpuMatrix *rhs, const GpuMatrix *addend, int negate,
+                              uint32_t base_bits, int small);
 /* kernel launches issued by the library since it was loaded (every context; copies / memsets not counted): bench.py
  * reports launches per step for the launch-bound small-ring chain                                              */
 uint64_t gpupoly_launch_count(void);

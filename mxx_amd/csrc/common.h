@@ -110,6 +110,9 @@ struct GpuContext {
     // guards every matrix's layout tag and storage swap (layout.hip) and the launches that read packed storage, so that
     // no thread frees packed bytes another thread is about to hand to a kernel
     std::mutex layout_mutex;
+    // base_bits -> device table [limb_count][dpt] of {(2^base_bits mod q_l)^e, its Shoup companion}: built on the first
+    // gadget product for that base (gadget_products.hip), under `mutex`, freed with the context
+    std::map<uint32_t, void *> gadget_weights;
 };
 
 // the layout tag of a matrix's storage, copyable (local views copy a GpuMatrix) and read without the lock on the fast path

@@ -506,6 +506,7 @@ static void context_release(GpuContext *ctx) {
     if (ctx->d_tw2_fwd) (void)hipFree(ctx->d_tw2_fwd);
     if (ctx->d_tw2_inv) (void)hipFree(ctx->d_tw2_inv);
     if (ctx->d_tw2s_inv) (void)hipFree(ctx->d_tw2s_inv);
+    for (auto &kv : ctx->gadget_weights) (void)hipFree(kv.second);
     if (ctx->timer_start) (void)hipEventDestroy(ctx->timer_start);
     if (ctx->timer_stop) (void)hipEventDestroy(ctx->timer_stop);
     for (hipEvent_t ev : ctx->marks)

@@ -1256,6 +1256,85 @@ class GpuDCRTPolyMatrix:
         """self -= lhs * rhs in one call (gpupoly_matrix_mul_acc)."""
         self._mul_acc(lhs, rhs, True)
 
+    # ---- products with the gadget matrix that never build it (gpupoly_matrix_mul_gadget / _gadget_mul) ----
+    @staticmethod
+    def _gadget_digits(params, level, small: bool) -> int:
+        """columns of g at `level`: digits per tower, times the towers unless `small`"""
+        dpt = -(-params.crt_bits() // params.base_bits())
+        return dpt if small else dpt * (level + 1)
+
+    @staticmethod
+    def _scalar_raw(scalar):
+        if scalar is None:
+            return None, None
+        s = scalar.inner if hasattr(scalar, "inner") else scalar
+        s = s.ensure_eval()
+        return s, s.raw
+
+    def mul_gadget(self, scalar=None, col_start: int = 0, col_end=None, addend=None, negate: bool = False, out=None, dst_col: int = 0,
+                   small: bool = False) -> "GpuDCRTPolyMatrix":
+        """addend +- (self * G[:, col_start:col_end]) o scalar in one launch, G = I_d (x) g with d = self.ncol, never built
+        (gpupoly_matrix_mul_gadget): `s * G` and `s * (G * y)` of src/bgg/sampler_gpu.rs:149 and src/bgg/sampler.rs:165.
+        `out` None: a fresh r x (col_end - col_start) matrix (`addend`, if any, has that shape; dst_col = 0).  Otherwise the
+        block goes to columns [dst_col, dst_col + col_end - col_start) of `out`, `addend` is None or has out's shape (it may
+        be `out`), and the other columns keep their contents."""
+        assert self.is_ntt, "mul_gadget requires NTT domain"
+        k = self._gadget_digits(self.params, self.level, small)
+        col_end = self.ncol * k if col_end is None else col_end
+        cols = col_end - col_start
+        assert 0 <= col_start <= col_end <= self.ncol * k, "mul_gadget: gadget window out of range"
+        s, s_raw = self._scalar_raw(scalar)
+        if out is None:
+            assert dst_col == 0, "mul_gadget: dst_col needs an `out` to place the block in"
+            out = GpuDCRTPolyMatrix(self.params, self.nrow, cols, self.level, True)
+        else:
+            out._touch()
+        if addend is not None:
+            assert addend.is_ntt and (addend.nrow, addend.ncol) == (out.nrow, out.ncol), "mul_gadget: the addend has out's shape, NTT domain"
+        st = _ffi.lib().gpupoly_matrix_mul_gadget(out.raw, dst_col, self.raw, s_raw, col_start, cols, None if addend is None else addend.raw,
+                                                  1 if negate else 0, self.params.base_bits(), 1 if small else 0)
+        check_status(st, "gpupoly_matrix_mul_gadget")
+        out.is_ntt = True
+        return out
+
+    def add_scaled_gadget(self, scalar=None, negate: bool = False, gadget_col: int = 0, small: bool = False) -> None:
+        """self +- G[:, gadget_col : gadget_col + self.ncol] o scalar in place, G = I_d (x) g with d = self.nrow: the
+        `A - G * x` idiom (src/lookup/lwe/pubkey_gpu.rs:205-210, src/io/diamond_io/utils.rs:612-616).  Only the limb
+        vectors G makes non-zero are read and written."""
+        assert self.is_ntt, "add_scaled_gadget requires NTT domain"
+        s, s_raw = self._scalar_raw(scalar)
+        self._touch()
+        st = _ffi.lib().gpupoly_matrix_mul_gadget(self.raw, 0, None, s_raw, gadget_col, self.ncol, self.raw, 1 if negate else 0,
+                                                  self.params.base_bits(), 1 if small else 0)
+        check_status(st, "gpupoly_matrix_mul_gadget")
+
+    @classmethod
+    def gadget_block(cls, params, size, col_start, col_end, scalar=None, negate: bool = False, small: bool = False, level=None) -> "GpuDCRTPolyMatrix":
+        """+-G[:, col_start:col_end] o scalar for G = I_size (x) g without the full matrix (gpupoly_matrix_mul_gadget):
+        `gadget_matrix.slice(0, d, col_start, col_end)` and `-G[:, chunk]` of the reference's callers."""
+        level = params.crt_depth() - 1 if level is None else level
+        out = cls(params, size, col_end - col_start, level, True)
+        s, s_raw = cls._scalar_raw(scalar)
+        st = _ffi.lib().gpupoly_matrix_mul_gadget(out.raw, 0, None, s_raw, col_start, col_end - col_start, None, 1 if negate else 0,
+                                                  params.base_bits(), 1 if small else 0)
+        check_status(st, "gpupoly_matrix_mul_gadget")
+        return out
+
+    @staticmethod
+    def gadget_mul(rhs, addend=None, negate: bool = False, small: bool = False) -> "GpuDCRTPolyMatrix":
+        """addend +- G * rhs in one launch, G = I_d (x) g with d = rhs.nrow / k, never built (gpupoly_matrix_gadget_mul): the
+        recomposition of digit rows (src/lookup/ggh15/pubkey_gpu.rs:505, src/commit/wee25.rs:718).  rhs and addend share one
+        domain, which the result takes."""
+        k = GpuDCRTPolyMatrix._gadget_digits(rhs.params, rhs.level, small)
+        assert rhs.nrow % k == 0, "gadget_mul: rhs rows must be a multiple of the digit count"
+        out = GpuDCRTPolyMatrix(rhs.params, rhs.nrow // k, rhs.ncol, rhs.level, rhs.is_ntt)
+        if addend is not None:
+            assert addend.is_ntt == rhs.is_ntt and (addend.nrow, addend.ncol) == (out.nrow, out.ncol), "gadget_mul: addend shape / domain mismatch"
+        st = _ffi.lib().gpupoly_matrix_gadget_mul(out.raw, rhs.raw, None if addend is None else addend.raw, 1 if negate else 0,
+                                                  rhs.params.base_bits(), 1 if small else 0)
+        check_status(st, "gpupoly_matrix_gadget_mul")
+        return out
+
     def mul_scalar_intt(self, scalar) -> "GpuDCRTPolyMatrix":
         """INTT(self o scalar) in one kernel (extension: the product rides in the inverse transform's load)."""
         s = scalar.inner if hasattr(scalar, "inner") else scalar
