@@ -39,12 +39,14 @@
  *          the output, and the result is the out-of-place one (for mul_scalar also the 1x1 out == lhs == scalar).
  *          Likewise the addend of gpupoly_matrix_mul_sum (gpupoly_matrix_mul_acc: `out` is its own addend); their
  *          lhss[t] / rhss[t] fall under 3.  Likewise the addend of gpupoly_matrix_mul_gadget and of
- *          gpupoly_matrix_gadget_mul; their lhs, scalar_1x1 and rhs fall under 3.
+ *          gpupoly_matrix_gadget_mul; their lhs, scalar_1x1 and rhs fall under 3.  Likewise addends[j] against outs[j]
+ *          in gpupoly_matrix_mul_decompose_gadget_scalar_many and gpupoly_matrix_mul_decompose_gadget_const_many.
  *       2. Any other overlap of their output with an operand is refused.
  *       3. Every other entry that reads matrices and writes one refuses any overlap between what it writes and what
  *          it reads, the same block included (gpu_matrix_gauss_samp_gq_arb_base before its source is transformed).
  *          gpupoly_matrix_add_rows / _ntt_add_rows are judged on the destination row block: an operand may be a view
- *          of other rows of `out`.
+ *          of other rows of `out`.  In gpupoly_matrix_mul_decompose_gadget_scalar_many / _const_many no outs[j] overlaps
+ *          any lhss[o], scalar_1x1, another output or another operand's addend.
  *       4. Several outputs: the blocks of gpupoly_matrix_split_columns are pairwise disjoint and disjoint from the
  *          source (the blocks of a concat may repeat, its output is disjoint from all of them); in
  *          gpupoly_matrix_mul_batch and gpupoly_batch no output overlaps another product's / gate's output or
@@ -591,6 +593,53 @@ int gpupoly_matrix_mul_gadget(GpuMatrix *out, size_t dst_col, const GpuMatrix *l
  * src/lookup/lwe/pubkey_gpu.rs:205-210 are gpupoly_matrix_mul_gadget's.                                              */
 int gpupoly_matrix_gadget_mul(GpuMatrix *out, const GpuMatrix *rhs, const GpuMatrix *addend, int negate,
                               uint32_t base_bits, int small);
+/* Extension: the LargeScalarMul gate, lhs * G^-1(G_d o c), without G or its digit matrix.
+ *   outs[j] = addends[j] + sgn * lhss[j] * G^-1(G_dj o c),  j < n,  sgn = negate ? -1 : +1.
+ * The reference's Evaluables write it as `lhs.mul_decompose(&(M::gadget_matrix(params, d) * scalar))`:
+ * src/bgg/public_key.rs:134-140, src/bgg/encoding.rs:191-200 (vector and key matrix), src/bgg/poly_encoding.rs:431-461 (once
+ * per slot plus the key), src/bgg/naive_vec.rs:441,607 - gate LargeScalarMul of src/circuit/poly_circuit/eval.rs:343-350.
+ * Through the existing entries that is gpu_matrix_fill_gadget, gpu_matrix_mul_scalar and gpupoly_matrix_mul_decompose: a
+ * d x dk matrix, a dk x dk digit matrix and a generic product.  Digits are taken per tower and entry (j, (j, t, e)) of G o c is
+ * non-zero in limb t only, so G^-1(G_d o c) = I_d (x) blockdiag_t(D_t) with D_t[e'][e] the polynomial whose coefficient i is
+ * digit e' of (c_t[i] * B^e mod q_t), B = 2^base_bits, written into every limb and transformed, and
+ *   out[i, (j, t, e)] = sum_{e' < dpt} lhs[i, (j, t, e')] * D_t[e'][e]      (every limb, every slot):
+ * L*dpt^2 digit polynomials instead of (d*k)^2, dpt ring multiplications per output instead of d*k.
+ *   k = dpt * (level + 1), dpt = ceil(crt_bits / base_bits)
+ *   lhss[j]     rows_j x (d_j * k), EVAL; rows_j and d_j may differ between operands and may be 0
+ *   outs[j]     lhss[j]'s shape, made by the caller, tagged EVAL on success
+ *   addends     NULL, or addends[j] NULL: no addend; else outs[j]'s shape, EVAL
+ *   scalar_1x1  1 x 1, COEFF or EVAL, left untouched (an EVAL scalar is inverse-transformed into scratch)
+ *   const_words host memory: words_per_const >= 1 little-endian 64-bit words of an integer C of any size, reduced mod every
+ *               q_t in the entry (gpupoly_matrix_load_coeff_words's rule; from_biguints(&[C]) of the reference)
+ * One context and one level per call (it may be below the top; scalar_1x1 is at that level).  The residues are canonical and
+ * equal, bit for bit, to those of gpu_matrix_fill_gadget, gpu_matrix_mul_scalar, gpupoly_matrix_mul_decompose and
+ * gpu_matrix_add / _sub / gpupoly_matrix_neg.  Enqueued on the context's stream, the host does not block; temporaries come
+ * from the context's allocator and are released stream-ordered; PACKED24 operands are unpacked first; n = 0 does nothing.
+ * _const_many: every D_t[e'][e] is a constant below 2^base_bits, its own transform - L^2*dpt^2 weights built on the host, no
+ * transform at all, ceil(n' / 64) launches for the n' operands that have entries, lhs read once and out written once.  The
+ * context keeps the weights per constant, as it keeps the gadget weight table: the first call for a constant uploads them
+ * (synchronous, once), later calls only launch.
+ * _scalar_many: one table kernel and one forward transform over L*dpt^2 polynomials per call, then one product launch per 64
+ * operands.  When the table (L^2*dpt^2*N words) exceeds gpupoly_matrix_mul_decompose's budget rule it is built and used in
+ * groups of towers; MXX_HIP_GADGET_SCALAR_BUDGET=<bytes> overrides the budget for this entry.
+ * Overlap: addends[j] may be the same block as outs[j] (every word is read and written by the same thread); outs[j] must not
+ * overlap any lhs, the scalar, another output or another operand's addend, row views included; any other overlap of an addend
+ * with an output is refused (the message contains "overlaps").
+ * Refused, with nothing launched and every outs[j] (residues AND tag) untouched, everything checked for every j before the
+ * first launch, the message naming the entry: null outs or lhss with n > 0; a null outs[j] or lhss[j]; a null scalar_1x1; a
+ * null const_words or words_per_const = 0; base_bits of 0 or >= 63; a context or level mismatch; lhss[j]->cols not a multiple
+ * of k; an out or addend whose shape is not the lhs's; an lhs or addend not in EVAL form; a scalar that is not 1 x 1; the
+ * overlaps above.                                                                                                        */
+int gpupoly_matrix_mul_decompose_gadget_scalar_many(GpuMatrix *const *outs, const GpuMatrix *const *lhss,
+                                                    const GpuMatrix *const *addends, size_t n, const GpuMatrix *scalar_1x1,
+                                                    int negate, uint32_t base_bits);
+/* The same gate for an integer constant C (const_words): its description, overlap rule and what is Refused are stated above -
+ * any overlap of outs[j] with an lhs, another output or another operand's addend is refused, an addend that is outs[j]'s own
+ * block is allowed.  The reference's callers pass &[shift], &[p_full], &[reconst_coeff]: src/bgg/public_key.rs:134-140,
+ * src/bgg/encoding.rs:191-200, src/bgg/poly_encoding.rs:431-461.                                                          */
+int gpupoly_matrix_mul_decompose_gadget_const_many(GpuMatrix *const *outs, const GpuMatrix *const *lhss,
+                                                   const GpuMatrix *const *addends, size_t n, const uint64_t *const_words,
+                                                   size_t words_per_const, int negate, uint32_t base_bits);
 /* kernel launches issued by the library since it was loaded (every context; copies / memsets not counted): bench.py
  * reports launches per step for the launch-bound small-ring chain                                              */
 uint64_t gpupoly_launch_count(void);

@@ -153,6 +153,8 @@ SIGNATURES = {
     "gpupoly_matrix_mul_acc": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "gpupoly_matrix_mul_gadget": (C.c_int, [_vp, _sz, _vp, _vp, _sz, _sz, _vp, C.c_int, C.c_uint32, C.c_int]),
     "gpupoly_matrix_gadget_mul": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_uint32, C.c_int]),
+    "gpupoly_matrix_mul_decompose_gadget_scalar_many": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _vp, C.c_int, C.c_uint32]),
+    "gpupoly_matrix_mul_decompose_gadget_const_many": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, C.POINTER(C.c_uint64), _sz, C.c_int, C.c_uint32]),
     "gpupoly_matrix_store_compact_bytes_many": (C.c_int, [C.POINTER(C.c_void_p), _sz, _vp, _sz, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "gpupoly_matrix_load_compact_bytes_many": (C.c_int, [C.POINTER(C.c_void_p), _sz, C.POINTER(C.c_void_p), C.POINTER(_sz), C.POINTER(C.c_uint16)]),
     "gpupoly_detmath_eval": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _sz]),

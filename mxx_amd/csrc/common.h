@@ -54,6 +54,8 @@ struct EnvSwitches {
     bool pack24 = true;           // MXX_HIP_PACK24=0|off: uniform samples stay in 4-byte words (layout.hip)
     size_t mul_decompose_many_budget = 0;  // MXX_HIP_MUL_DECOMPOSE_MANY_BUDGET=<bytes>: digit-matrix budget of gpupoly_matrix_mul_decompose_many
                                            // alone (0 = a third of the free memory, at least 8 GiB; tests reach its column chunks with it)
+    size_t gadget_scalar_budget = 0;  // MXX_HIP_GADGET_SCALAR_BUDGET=<bytes>: digit-polynomial table budget of
+                                      // gpupoly_matrix_mul_decompose_gadget_scalar_many alone (0 = the same rule; tests reach its tower groups with it)
     char mul_sum_path = 0;        // MXX_HIP_MUL_SUM_PATH: 0 auto, 't' the term-table tile kernel at every height, 's' products into
                                   // scratch + one combine pass per term above 8 rows (matmul_sum.hip; A/B, tests)
     void load();
@@ -113,6 +115,10 @@ struct GpuContext {
     // base_bits -> device table [limb_count][dpt] of {(2^base_bits mod q_l)^e, its Shoup companion}: built on the first
     // gadget product for that base (gadget_products.hip), under `mutex`, freed with the context
     std::map<uint32_t, void *> gadget_weights;
+    // {base_bits, limbs, C mod q_0, ...} -> device table [l][t][e'][e] of {delta mod q_l, its Shoup companion} for the
+    // constant C of gpupoly_matrix_mul_decompose_gadget_const_many (gadget_scalar.hip): built on the first call with that
+    // constant, under `mutex`, freed with the context; a bounded number of them is kept
+    std::map<std::vector<uint64_t>, void *> gadget_const_tables;
 };
 
 // the layout tag of a matrix's storage, copyable (local views copy a GpuMatrix) and read without the lock on the fast path

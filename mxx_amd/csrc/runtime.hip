@@ -286,6 +286,7 @@ void EnvSwitches::load() {
     if (const char *e = std::getenv("MXX_HIP_SERDE")) serde_general = e[0] == 'g';
     if (const char *e = std::getenv("MXX_HIP_PACK24")) pack24 = !(std::strcmp(e, "0") == 0 || std::strcmp(e, "off") == 0);
     if (const char *e = std::getenv("MXX_HIP_MUL_DECOMPOSE_MANY_BUDGET")) mul_decompose_many_budget = static_cast<size_t>(std::strtoull(e, nullptr, 10));
+    if (const char *e = std::getenv("MXX_HIP_GADGET_SCALAR_BUDGET")) gadget_scalar_budget = static_cast<size_t>(std::strtoull(e, nullptr, 10));
     if (const char *e = std::getenv("MXX_HIP_MUL_SUM_PATH")) mul_sum_path = (e[0] == 't' || e[0] == 's') ? e[0] : 0;
     if (const char *e = std::getenv("MXX_HIP_SAMPLER_PER_LANE")) {
         const int v = std::atoi(e);
@@ -507,6 +508,7 @@ static void context_release(GpuContext *ctx) {
     if (ctx->d_tw2_inv) (void)hipFree(ctx->d_tw2_inv);
     if (ctx->d_tw2s_inv) (void)hipFree(ctx->d_tw2s_inv);
     for (auto &kv : ctx->gadget_weights) (void)hipFree(kv.second);
+    for (auto &kv : ctx->gadget_const_tables) (void)hipFree(kv.second);
     if (ctx->timer_start) (void)hipEventDestroy(ctx->timer_start);
     if (ctx->timer_stop) (void)hipEventDestroy(ctx->timer_stop);
     for (hipEvent_t ev : ctx->marks)

@@ -1634,6 +1634,106 @@ class GpuDCRTPolyMatrix:
         check_status(st, "gpupoly_matrix_mul_decompose_many")
         return outs
 
+    # ---- the LargeScalarMul gate: lhs * G^-1(G o c) without G or its digit matrix ----
+    @staticmethod
+    def _int_words(value: int) -> np.ndarray:
+        value = int(value)
+        if value < 0:
+            raise ValueError("large_scalar_mul: negative constant (constants are unsigned)")
+        wpc = max(1, -(-value.bit_length() // 64))
+        return np.frombuffer(value.to_bytes(8 * wpc, "little"), dtype=np.uint64).copy()
+
+    @staticmethod
+    def _large_scalar(first, scalar):
+        """-> (constant as an int, None) or (None, 1 x 1 matrix at first's level)"""
+        if isinstance(scalar, (int, np.integer)):
+            return int(scalar), None
+        if isinstance(scalar, (list, tuple)):
+            if len(scalar) == 1:
+                return int(scalar[0]), None
+            assert len(scalar) <= first.params.ring_dimension(), "more coefficients than the ring dimension"
+            words = [GpuDCRTPolyMatrix._int_words(c) for c in scalar]
+            wpc = max((len(w) for w in words), default=1)
+            arr = np.zeros((1, 1, max(len(words), 1), wpc), dtype=np.uint64)
+            for i, w in enumerate(words):
+                arr[0, 0, i, : len(w)] = w
+            return None, GpuDCRTPolyMatrix.from_coeff_words(first.params, arr, True, level=first.level)
+        s = scalar.inner if hasattr(scalar, "inner") else scalar
+        assert s.size() == (1, 1), "large_scalar_mul: the scalar is a polynomial or a 1 x 1 matrix"
+        return None, s
+
+    def large_scalar_mul(self, scalar) -> "GpuDCRTPolyMatrix":
+        """self * G^-1(G_d o scalar), d = self.ncol / k: the LargeScalarMul gate of the reference's Evaluables
+        (src/bgg/public_key.rs:134-140, src/bgg/encoding.rs:191-200).  See large_scalar_mul_many."""
+        return GpuDCRTPolyMatrix.large_scalar_mul_many([self], scalar)[0]
+
+    @staticmethod
+    def large_scalar_mul_many(lhss, scalar, addends=None, negate: bool = False) -> list:
+        """[a +- l * G^-1(G o scalar) for l, a in zip(lhss, addends)] without G or its digit matrix
+        (gpupoly_matrix_mul_decompose_gadget_const_many / _scalar_many).  `scalar`: an int or a one-element list (the
+        constant entry: no transform at all), a longer coefficient list, a GpuDCRTPoly or a 1 x 1 matrix in either domain.
+        lhss[j] is rows_j x (d_j k) in the NTT domain; `addends` may be None or hold None entries.  The reference's sequence
+        (_large_scalar_mul_host) runs when its chunk switch is set."""
+        lhss = list(lhss)
+        n = len(lhss)
+        addends = [None] * n if addends is None else list(addends)
+        assert len(addends) == n, "large_scalar_mul_many: one addend slot per operand"
+        if n == 0:
+            return []
+        first = lhss[0]
+        k = GpuDCRTPolyMatrix._gadget_digits(first.params, first.level, False)
+        for l_, a_ in zip(lhss, addends):
+            assert l_.params == first.params and l_.level == first.level, "large_scalar_mul_many: one context and level per call"
+            assert l_.ncol % k == 0, "large_scalar_mul_many: lhs columns must be a multiple of the digit count"
+            assert a_ is None or (a_.nrow, a_.ncol) == (l_.nrow, l_.ncol), "large_scalar_mul_many: addend shape"
+        const, sc = GpuDCRTPolyMatrix._large_scalar(first, scalar)
+        if mul_decompose_column_chunk_width_is_set():
+            outs = []
+            for l_, a_ in zip(lhss, addends):
+                prod = l_._large_scalar_mul_host(const if sc is None else sc)
+                if a_ is None:
+                    outs.append(-prod if negate else prod)
+                else:
+                    outs.append(a_.ensure_eval() - prod if negate else a_.ensure_eval() + prod)
+            return outs
+        ls = [m.ensure_eval() for m in lhss]  # converted copies stay referenced until the call returns
+        ads = [None if m is None else m.ensure_eval() for m in addends]
+        outs = [GpuDCRTPolyMatrix(first.params, l_.nrow, l_.ncol, l_.level, True) for l_ in ls]
+        raw = lambda m: None if m is None else (m.raw.value if hasattr(m.raw, "value") else m.raw)
+        arr = lambda ms: (C.c_void_p * n)(*[raw(m) for m in ms])
+        base = first.params.base_bits()
+        if sc is None:
+            words = GpuDCRTPolyMatrix._int_words(const)
+            st = _ffi.lib().gpupoly_matrix_mul_decompose_gadget_const_many(
+                arr(outs), arr(ls), arr(ads), n, words.ctypes.data_as(C.POINTER(C.c_uint64)), len(words), 1 if negate else 0, base)
+            check_status(st, "gpupoly_matrix_mul_decompose_gadget_const_many")
+        else:
+            st = _ffi.lib().gpupoly_matrix_mul_decompose_gadget_scalar_many(arr(outs), arr(ls), arr(ads), n, sc.raw, 1 if negate else 0, base)
+            check_status(st, "gpupoly_matrix_mul_decompose_gadget_scalar_many")
+        return outs
+
+    def _large_scalar_mul_host(self, scalar) -> "GpuDCRTPolyMatrix":
+        """The reference's sequence, kept for comparison: G_d (gpu_matrix_fill_gadget), G_d o scalar (gpu_matrix_mul_scalar),
+        self * G^-1(.) (gpupoly_matrix_mul_decompose).  `scalar`: an int or a 1 x 1 matrix / polynomial."""
+        k = self._gadget_digits(self.params, self.level, False)
+        assert self.ncol % k == 0
+        d = self.ncol // k
+        out = GpuDCRTPolyMatrix(self.params, self.nrow, self.ncol, self.level, True)
+        if self.nrow == 0 or d == 0:
+            return out
+        if isinstance(scalar, (int, np.integer)):
+            words = self._int_words(scalar).reshape(1, 1, 1, -1)
+            scalar = GpuDCRTPolyMatrix.from_coeff_words(self.params, words, True, level=self.level)
+        s = (scalar.inner if hasattr(scalar, "inner") else scalar).ensure_eval()
+        g = GpuDCRTPolyMatrix(self.params, d, d * k, self.level, True)
+        check_status(_ffi.lib().gpu_matrix_fill_gadget(g.raw, self.params.base_bits()), "gpu_matrix_fill_gadget")
+        gs = GpuDCRTPolyMatrix(self.params, d, d * k, self.level, True)
+        check_status(_ffi.lib().gpu_matrix_mul_scalar(gs.raw, g.raw, s.raw), "gpu_matrix_mul_scalar")
+        lhs = self.ensure_eval()
+        st = _ffi.lib().gpupoly_matrix_mul_decompose(out.raw, lhs.raw, gs.raw, self.params.base_bits())
+        check_status(st, "gpupoly_matrix_mul_decompose")
+        return out
+
     def mul_decompose_small(self, other) -> "GpuDCRTPolyMatrix":
         k = -(-self.params.crt_bits() // self.params.base_bits())
         assert self.ncol == other.nrow * k
