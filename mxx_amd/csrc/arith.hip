@@ -10,8 +10,7 @@
 // of two residues < q are summed without reduction for as many terms as fit in
 // 64 bits (all of them for 24-bit primes), then reduced once with a mulhi by
 // floor(2^64/q).  One launch covers every limb (the reference launches per limb).
-#include "common.h"
-#include "modarith.h"
+#include "matmul_tile.h"
 
 #include <algorithm>
 #include <vector>
@@ -139,8 +138,7 @@ __global__ void __launch_bounds__(256)
     if (i >= N) return;
     const LimbConst lc = limbs[limb];
     const W q = static_cast<W>(lc.q);
-    typedef typename std::conditional<sizeof(W) * SV == 16, uint4, typename std::conditional<sizeof(W) * SV == 8, uint2, W>::type>::type VT;
-    static_assert(sizeof(VT) == sizeof(W) * SV, "vector width");
+    typedef typename TileTypes<W, SV>::VT VT;
 
     const size_t strideA = PA ? static_cast<size_t>(L) * N / 4 * 3 : static_cast<size_t>(L) * N;  // words between consecutive polys
     // clamp out-of-range tile rows/cols to a valid entry; their results are never stored
@@ -250,59 +248,17 @@ __global__ void __launch_bounds__(256)
     } else {
         // 64-bit words: 128-bit lazy accumulators (a 51-bit prime leaves room for 2^26 products before the one
         // reduction; lc.lazy_terms holds the window) instead of a Barrett reduction per term
-        u128_t acc[TR][TC][SV];
-#pragma unroll
-        for (int r = 0; r < TR; ++r)
-#pragma unroll
-            for (int c = 0; c < TC; ++c)
-#pragma unroll
-                for (int s = 0; s < SV; ++s) acc[r][c][s] = 0;
+        typedef typename TileTypes<W, SV>::wxs wxs;
+        typedef typename TileTypes<W, SV>::D D;
+        D acc[TR][TC][SV];
+        MXX_TILE_CLEAR(acc);
         const uint32_t lazy = lc.lazy_terms;
         uint32_t pending = 0;
-        // small tiles are latency-bound (one dependent pair of loads per k): the operands of KU iterations are loaded
-        // before any of them is multiplied, so KU loads are in flight instead of one (16 products (1 x 76)(76 x 4) at
-        // n = 256, L = 12: 0.46 -> 0.22 ms; M4 chain step 0.80 -> 0.73 ms).  The tail past `inner` re-reads the last valid operands and is not accumulated.
-        constexpr uint32_t KU = TR * TC * SV <= 8 ? 8 : 1;
-        for (uint32_t k0 = 0; k0 < inner; k0 += KU) {
-            W av[KU][TR][SV], bv[KU][TC][SV];
-#pragma unroll
-            for (uint32_t u = 0; u < KU; ++u) {
-                const uint32_t k = min(k0 + u, inner - 1);
-#pragma unroll
-                for (int r = 0; r < TR; ++r)
-                    *reinterpret_cast<VT *>(av[u][r]) = *reinterpret_cast<const VT *>(A + a_off[r] + k * strideA);
-#pragma unroll
-                for (int c = 0; c < TC; ++c) {
-                    typedef W wxs __attribute__((ext_vector_type(SV)));
-                    const wxs *src = reinterpret_cast<const wxs *>(B + b_off[c] + k * strideBk);
-                    wxs t;
-                    if constexpr (NTB) t = __builtin_nontemporal_load(src);  // see the 32-bit branch
-                    else t = *src;
-#pragma unroll
-                    for (int s_ = 0; s_ < SV; ++s_) bv[u][c][s_] = t[s_];
-                }
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < KU; ++u) {
-                if (KU > 1 && k0 + u >= inner) break;
-#pragma unroll
-                for (int r = 0; r < TR; ++r)
-#pragma unroll
-                    for (int c = 0; c < TC; ++c)
-#pragma unroll
-                        for (int s = 0; s < SV; ++s) acc[r][c][s] += static_cast<u128_t>(av[u][r][s]) * bv[u][c][s];
-                if (++pending == lazy) {
-                    pending = 0;
-#pragma unroll
-                    for (int r = 0; r < TR; ++r)
-#pragma unroll
-                        for (int c = 0; c < TC; ++c)
-#pragma unroll
-                            for (int s = 0; s < SV; ++s)
-                                acc[r][c][s] = reduce_u128_sum(acc[r][c][s], q, lc.mu, lc.kbits, lc.mu64);
-                }
-            }
-        }
+        // this kernel's own rule: unlike kTileKU, no second step ahead for the 2 x 4 x 2 tile
+#define MXX_TILE_KU (TR * TC * SV <= 8 ? 8 : 1)
+#define MXX_TILE_A(r, k) (A + a_off[r] + (k) * strideA)
+#define MXX_TILE_B(c, k) (B + b_off[c] + (k) * strideBk)
+#include "matmul_tile_loop.inc"
 #pragma unroll
         for (int r = 0; r < TR; ++r) {
             if (r0 + r >= rows) continue;
@@ -486,12 +442,9 @@ static int launch_matmul_cfg(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatr
     const uint32_t rows = static_cast<uint32_t>(lhs->rows), inner = static_cast<uint32_t>(lhs->cols),
                    cols = static_cast<uint32_t>(rhs->cols);
     const uint32_t L = static_cast<uint32_t>(matrix_limbs(out)), N = static_cast<uint32_t>(ctx->N);
-    const uint32_t row_tiles = (rows + TR - 1) / TR, col_tiles = (cols + TC - 1) / TC;
-    const uint32_t threads = std::min<uint32_t>(256, std::max<uint32_t>(64, N / SV));
-    const uint32_t gx = (N / SV + threads - 1) / threads;
-    if (static_cast<uint64_t>(row_tiles) * col_tiles > 65535) return set_error("gpu_matrix_mul: matrix too large");
-    dim3 grid(gx, row_tiles * col_tiles, L);
-    const bool nt = row_tiles == 1 && rhs->bytes > (size_t(1) << 28);
+    if (!tile_grid_fits(rows, cols, TR, TC)) return set_error("gpu_matrix_mul: matrix too large");
+    const TileGrid g = tile_grid<TR, TC, SV>(ctx, rows, cols, L, rhs->bytes);
+    const bool nt = g.streamed;
     auto label = [](bool nt_, int pk) {
         return std::string("matmul_kernel<") + (sizeof(W) == 4 ? "u32," : "u64,") + std::to_string(TR) + "," + std::to_string(TC) + "," +
                std::to_string(SV) + (PF ? ",loads-ahead" : "") + (nt_ ? ",nt" : "") +
@@ -501,11 +454,11 @@ static int launch_matmul_cfg(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatr
     };
     static const std::string name[2][3] = {{label(false, 0), label(false, 1), label(false, 2)}, {label(true, 0), label(true, 1), label(true, 2)}};
     W *c = static_cast<W *>(words_ptr(out));  // before the layout lock below: it may unpack
-    // B is read by this one row tile only and cannot live in the 256 MB Infinity Cache: streamed with non-temporal loads
+    // nt: B is read by this one row tile only and cannot live in the Infinity Cache (tile_grid): non-temporal loads
     // (a smaller B is often re-used from cache by the next product - the hint made repeated products on a 134 MB operand
     // 40 % slower)
 #define MXX_MM(NT, PK) \
-    MXX_LAUNCH((matmul_kernel<W, TR, TC, SV, PF, NT, PK>), grid, dim3(threads), 0, ctx->stream, c, a, b, ctx->d_limbs, rows, inner, cols, L, N, col_tiles)
+    MXX_LAUNCH((matmul_kernel<W, TR, TC, SV, PF, NT, PK>), g.grid, dim3(g.threads), 0, ctx->stream, c, a, b, ctx->d_limbs, rows, inner, cols, L, N, g.col_tiles)
     if constexpr (sizeof(W) == 4 && SV == 4) {
         if (lhs->ctx == ctx && rhs->ctx == ctx) {
             // one packed operand per product: with both packed, the products of two 24-bit-masked values came out wrong
@@ -546,20 +499,11 @@ int launch_matmul(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs) {
     GpuContext *ctx = out->ctx;
     const size_t rows = lhs->rows, cols = rhs->cols;
     const int N = ctx->N;
-    if (ctx->wide) {
-        // small rings (BASELINE configs[4]: n = 256): a register tile per thread leaves most of the chip idle -
-        // (2x72)*(72x4) at L = 12 is 24 waves of 4x4x2 tiles.  Below ~2 waves per SIMD of tiled work, shrink the
-        // tile until the grid covers the chip (every output then re-reads its operands from L2, which is cheap there).
-        const uint64_t slots = static_cast<uint64_t>(N) * matrix_limbs(out);
-        const uint64_t want = 1024ull * 2 * 64;  // lanes for two waves on every SIMD
-        if (N >= 2 && slots / 2 * ((rows + 3) / 4) * ((cols + 3) / 4) >= want) {
-            if (rows >= 4) return launch_matmul_cfg<uint64_t, 4, 4, 2>(out, lhs, rhs);
-            if (rows >= 2) return launch_matmul_cfg<uint64_t, 2, 4, 2>(out, lhs, rhs);
-            return launch_matmul_cfg<uint64_t, 1, 4, 2>(out, lhs, rhs);
-        }
-        if (slots * ((rows + 1) / 2) * ((cols + 1) / 2) >= want) return launch_matmul_cfg<uint64_t, 2, 2, 1>(out, lhs, rhs);
-        return launch_matmul_cfg<uint64_t, 1, 1, 1>(out, lhs, rhs);
-    }
+    if (ctx->wide)  // 64-bit words: the one tile rule of the register-tiled products (matmul_tile.h)
+        return dispatch_stacked_tile(ctx, stacked_tile(ctx, rows, cols, matrix_limbs(out)), [&](auto cfg) {
+            typedef decltype(cfg) T;
+            return launch_matmul_cfg<typename T::W, T::TR, T::TC, T::SV>(out, lhs, rhs);
+        });
     {
         // MXX_HIP_MATMUL_PATH = reg | lds | dma forces a kernel family (tests cover all)
         const char force = ctx->env.matmul_path;

@@ -12,11 +12,10 @@
 // Grouped product: the rows of all operands form one stacked left factor that is never materialised.  A descriptor per
 // operand (A, C, addend, scalar pointers, row count, first stacked row) rides in the kernel-argument segment like
 // MulBatchArgs (arith.hip); a workgroup takes a TR x TC tile of stacked rows x digit-matrix columns for one limb and a
-// run of slots, looks its TR rows up in the table (uniform per workgroup: scalar loads), accumulates lazily like
-// matmul_kernel and, in the epilogue, reduces, adds addend o scalar where present and stores into the operand's own
+// run of slots, looks its TR rows up in the table (uniform per workgroup: scalar loads), accumulates with the shared
+// register-tile loop (matmul_tile.h, which also chooses the tile and the grid) and, in the epilogue, reduces, adds addend o scalar where present and stores into the operand's own
 // output at columns [c0, c0 + cw).  No stacking copy, no split copy, no mul_scalar or add launch.
-#include "common.h"
-#include "modarith.h"
+#include "matmul_tile.h"
 
 #include <algorithm>
 #include <string>
@@ -51,10 +50,9 @@ __global__ void __launch_bounds__(256)
     if (i >= N) return;
     const LimbConst lc = limbs[limb];
     const W q = static_cast<W>(lc.q);
-    typedef typename std::conditional<sizeof(W) * SV == 16, uint4, typename std::conditional<sizeof(W) * SV == 8, uint2, W>::type>::type VT;
-    static_assert(sizeof(VT) == sizeof(W) * SV, "vector width");
-    typedef W wxs __attribute__((ext_vector_type(SV)));
-    typedef typename Wide<W>::type D;
+    typedef typename TileTypes<W, SV>::VT VT;
+    typedef typename TileTypes<W, SV>::wxs wxs;
+    typedef typename TileTypes<W, SV>::D D;
 
     const size_t poly = static_cast<size_t>(L) * N;  // words per polynomial
     const size_t in_poly = static_cast<size_t>(limb) * N + i;
@@ -79,60 +77,12 @@ __global__ void __launch_bounds__(256)
     const size_t strideBk = static_cast<size_t>(cw) * poly;
 
     D acc[TR][TC][SV];
-#pragma unroll
-    for (int r = 0; r < TR; ++r)
-#pragma unroll
-        for (int c = 0; c < TC; ++c)
-#pragma unroll
-            for (int s = 0; s < SV; ++s) acc[r][c][s] = 0;
-    auto reduce = [&](D v) -> W {
-        if constexpr (sizeof(W) == 4) return reduce_u64_sum(v, q, lc.mu64);
-        else return reduce_u128_sum(v, q, lc.mu, lc.kbits, lc.mu64);
-    };
+    MXX_TILE_CLEAR(acc);
     const uint32_t lazy = lc.lazy_terms;
     uint32_t pending = 0;
-    // small tiles are latency-bound (one dependent pair of loads per k): the operands of KU terms are loaded before any of
-    // them is multiplied (matmul_kernel's 64-bit branch).  The tail past `inner` re-reads the last term and is dropped.
-    constexpr uint32_t KU = TR * TC * SV <= 8 ? 8 : (TR * TC * SV * sizeof(W) <= 128 ? 2 : 1);
-    for (uint32_t k0 = 0; k0 < inner; k0 += KU) {
-        W av[KU][TR][SV], bv[KU][TC][SV];
-#pragma unroll
-        for (uint32_t u = 0; u < KU; ++u) {
-            const uint32_t k = min(k0 + u, inner - 1);
-#pragma unroll
-            for (int r = 0; r < TR; ++r) *reinterpret_cast<VT *>(av[u][r]) = *reinterpret_cast<const VT *>(a_ptr[r] + k * poly);
-#pragma unroll
-            for (int c = 0; c < TC; ++c) {
-                // NTB (one row tile): B is streamed exactly once and must not displace the left operands, which every column
-                // tile re-reads, from the caches (arith.hip, matmul_kernel); with several row tiles the others re-read it
-                const wxs *src = reinterpret_cast<const wxs *>(B + b_off[c] + k * strideBk);
-                wxs t;
-                if constexpr (NTB) t = __builtin_nontemporal_load(src);
-                else t = *src;
-#pragma unroll
-                for (int s = 0; s < SV; ++s) bv[u][c][s] = t[s];
-            }
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < KU; ++u) {
-            if (KU > 1 && k0 + u >= inner) break;
-#pragma unroll
-            for (int r = 0; r < TR; ++r)
-#pragma unroll
-                for (int c = 0; c < TC; ++c)
-#pragma unroll
-                    for (int s = 0; s < SV; ++s) acc[r][c][s] += static_cast<D>(av[u][r][s]) * bv[u][c][s];
-            if (++pending == lazy) {
-                pending = 0;
-#pragma unroll
-                for (int r = 0; r < TR; ++r)
-#pragma unroll
-                    for (int c = 0; c < TC; ++c)
-#pragma unroll
-                        for (int s = 0; s < SV; ++s) acc[r][c][s] = reduce(acc[r][c][s]);
-            }
-        }
-    }
+#define MXX_TILE_A(r, k) (a_ptr[r] + (k) * poly)
+#define MXX_TILE_B(c, k) (B + b_off[c] + (k) * strideBk)
+#include "matmul_tile_loop.inc"
     // epilogue: reduce, + addend o scalar, store into the operand's own output
 #pragma unroll
     for (int r = 0; r < TR; ++r) {
@@ -146,7 +96,7 @@ __global__ void __launch_bounds__(256)
             const size_t off = out_off[r] + static_cast<size_t>(c) * poly;
             W o[SV];
 #pragma unroll
-            for (int s = 0; s < SV; ++s) o[s] = reduce(acc[r][c][s]);
+            for (int s = 0; s < SV; ++s) o[s] = tile_reduce<W>(acc[r][c][s], q, lc);
             if (it.addend) {
                 W ad[SV];
                 *reinterpret_cast<VT *>(ad) = *reinterpret_cast<const VT *>(static_cast<const W *>(it.addend) + off);
@@ -165,67 +115,33 @@ template <typename W, int TR, int TC, int SV>
 static int launch_group_cfg(GpuContext *ctx, const MulGroupArgs &args, uint32_t items, uint32_t total_rows, const void *b,
                             size_t b_bytes, uint32_t inner, uint32_t cw, uint32_t col0, uint32_t out_cols, uint32_t L) {
     const uint32_t N = static_cast<uint32_t>(ctx->N);
-    const uint32_t row_tiles = (total_rows + TR - 1) / TR, col_tiles = (cw + TC - 1) / TC;
-    const uint32_t threads = std::min<uint32_t>(256, std::max<uint32_t>(64, N / SV));
-    const uint32_t gx = (N / SV + threads - 1) / threads;
-    const dim3 grid(gx, row_tiles * col_tiles, L);  // row_tiles * col_tiles <= 65535: checked before the first launch
+    const TileGrid g = tile_grid<TR, TC, SV>(ctx, total_rows, cw, L, b_bytes);  // its y extent: checked before the first launch
     static const std::string name = std::string("matmul_group_kernel<") + (sizeof(W) == 4 ? "u32," : "u64,") + std::to_string(TR) + "," +
                                     std::to_string(TC) + "," + std::to_string(SV) +
                                     "> (stacked rows of up to 64 operands x digit columns x slots per lane, addend o scalar in the epilogue)";
     ctx->last_kernel = name.c_str();
     const W *bw = static_cast<const W *>(b);
-    // the streamed-once hint as launch_matmul_cfg gives it: one row tile, and a B that cannot stay in the Infinity Cache
-    bool streamed = false;
+    bool streamed = false;  // the 64-bit tiles have no non-temporal instance
     if constexpr (sizeof(W) == 4) {
-        if (row_tiles == 1 && b_bytes > (size_t(1) << 28)) {
+        if (g.streamed) {
             streamed = true;
-            MXX_LAUNCH((matmul_group_kernel<W, TR, TC, SV, true>), grid, dim3(threads), 0, ctx->stream, args, items, bw, ctx->d_limbs,
-                       total_rows, inner, cw, col0, out_cols, L, N, row_tiles);
+            MXX_LAUNCH((matmul_group_kernel<W, TR, TC, SV, true>), g.grid, dim3(g.threads), 0, ctx->stream, args, items, bw, ctx->d_limbs,
+                       total_rows, inner, cw, col0, out_cols, L, N, g.row_tiles);
         }
     }
     if (!streamed)
-        MXX_LAUNCH((matmul_group_kernel<W, TR, TC, SV, false>), grid, dim3(threads), 0, ctx->stream, args, items, bw, ctx->d_limbs, total_rows,
-                   inner, cw, col0, out_cols, L, N, row_tiles);
+        MXX_LAUNCH((matmul_group_kernel<W, TR, TC, SV, false>), g.grid, dim3(g.threads), 0, ctx->stream, args, items, bw, ctx->d_limbs,
+                   total_rows, inner, cw, col0, out_cols, L, N, g.row_tiles);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// register tile (rows, columns; the slots per lane follow in launch_group) for `total` stacked rows against cw columns
-struct GroupTile {
-    uint32_t tr, tc;
-};
-static GroupTile group_tile(const GpuContext *ctx, uint32_t total, uint32_t cw, uint32_t L) {
-    const uint64_t N = static_cast<uint64_t>(ctx->N);
-    if (ctx->wide) {
-        // small rings (n = 256): launch-bound, and a register tile per lane leaves most of the chip idle; shrink the tile
-        // until the grid covers the chip, as launch_matmul does
-        const uint64_t slots = N * L, want = 1024ull * 2 * 64;
-        if (N >= 2 && slots / 2 * ((total + 3) / 4) * ((cw + 3) / 4) >= want) return {total >= 4 ? 4u : (total >= 2 ? 2u : 1u), 4};
-        if (slots * ((total + 1) / 2) * ((cw + 1) / 2) >= want) return {2, 2};
-        return {1, 1};
-    }
-    if (N >= 4 && total <= 2) return {total, 8};  // 16-byte loads: B is streamed once
-    return {total <= 4 ? 4u : 8u, 8};             // 5 and more: 8-row tiles, B is read once per 8 stacked rows
-}
-
 static int launch_group(GpuContext *ctx, const MulGroupArgs &args, uint32_t items, uint32_t total_rows, const void *b, size_t b_bytes,
                         uint32_t inner, uint32_t cw, uint32_t col0, uint32_t out_cols, uint32_t L) {
-    const uint32_t tr = group_tile(ctx, total_rows, cw, L).tr, tc = group_tile(ctx, total_rows, cw, L).tc;
-#define MXX_GROUP(W, R, C, S) return launch_group_cfg<W, R, C, S>(ctx, args, items, total_rows, b, b_bytes, inner, cw, col0, out_cols, L)
-    if (ctx->wide) {
-        if (tc == 4) {
-            if (tr == 4) MXX_GROUP(uint64_t, 4, 4, 2);
-            if (tr == 2) MXX_GROUP(uint64_t, 2, 4, 2);
-            MXX_GROUP(uint64_t, 1, 4, 2);
-        }
-        if (tr == 2) MXX_GROUP(uint64_t, 2, 2, 1);
-        MXX_GROUP(uint64_t, 1, 1, 1);
-    }
-    if (tr == 1) MXX_GROUP(uint32_t, 1, 8, 4);
-    if (tr == 2) MXX_GROUP(uint32_t, 2, 8, 4);
-    if (tr == 4) MXX_GROUP(uint32_t, 4, 8, 1);
-    MXX_GROUP(uint32_t, 8, 8, 1);
-#undef MXX_GROUP
+    return dispatch_stacked_tile(ctx, stacked_tile(ctx, total_rows, cw, L), [&](auto cfg) {
+        typedef decltype(cfg) T;
+        return launch_group_cfg<typename T::W, T::TR, T::TC, T::SV>(ctx, args, items, total_rows, b, b_bytes, inner, cw, col0, out_cols, L);
+    });
 }
 
 extern "C" int gpupoly_matrix_mul_decompose_many(GpuMatrix *const *outs, const GpuMatrix *const *lhss,
@@ -305,8 +221,8 @@ extern "C" int gpupoly_matrix_mul_decompose_many(GpuMatrix *const *outs, const G
         for (size_t cwid : widths)
             for (uint32_t rows_g : group_rows) {
                 if (cwid == 0) continue;
-                const GroupTile t = group_tile(ctx, rows_g, static_cast<uint32_t>(cwid), static_cast<uint32_t>(L));
-                if (static_cast<uint64_t>((rows_g + t.tr - 1) / t.tr) * ((cwid + t.tc - 1) / t.tc) > 65535) return refuse("matrix too large");
+                const TileShape t = stacked_tile(ctx, rows_g, cwid, L);
+                if (!tile_grid_fits(rows_g, cwid, t.tr, t.tc)) return refuse("matrix too large");
             }
     }
     // ---- accepted ----

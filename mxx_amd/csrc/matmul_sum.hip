@@ -9,7 +9,8 @@
 // Through gpu_matrix_mul that is a product launch, an add or sub launch (three more passes over the output), a temporary,
 // a neg launch for a negated term and a copy_block per chunk - each of them latency-bound on the small rings.
 //
-// Term-table product: where matmul_group_kernel's table runs over operands, this one runs over the INNER dimension.  Up to
+// Term-table product: the shared register-tile loop (matmul_tile.h, which also chooses the tile and the grid) once per
+// term.  Where matmul_group_kernel's table runs over operands, this one runs over the INNER dimension.  Up to
 // 64 {A_t, B_t, k_t} descriptors ride in the kernel-argument segment; a workgroup takes a TR x TC tile of out's block for
 // one limb and a run of slots and walks all terms - the virtual product [A_0 | A_1 | ...] * [B_0; B_1; ...], never
 // materialised.  The lazy accumulators AND the pending-product counter carry across term boundaries: one reduction per
@@ -18,8 +19,7 @@
 //
 // Above 8 rows the tuned products (gpu_matrix_mul's dispatcher: the streamed 32-row tiles, the LDS tile) go into scratch
 // and one combine pass per term folds them into the block (DESIGN.md 5j has the timing behind the rule).
-#include "common.h"
-#include "modarith.h"
+#include "matmul_tile.h"
 
 #include <algorithm>
 #include <string>
@@ -51,10 +51,9 @@ __global__ void __launch_bounds__(256)
     if (i >= N) return;
     const LimbConst lc = limbs[limb];
     const W q = static_cast<W>(lc.q);
-    typedef typename std::conditional<sizeof(W) * SV == 16, uint4, typename std::conditional<sizeof(W) * SV == 8, uint2, W>::type>::type VT;
-    static_assert(sizeof(VT) == sizeof(W) * SV, "vector width");
-    typedef W wxs __attribute__((ext_vector_type(SV)));
-    typedef typename Wide<W>::type D;
+    typedef typename TileTypes<W, SV>::VT VT;
+    typedef typename TileTypes<W, SV>::wxs wxs;
+    typedef typename TileTypes<W, SV>::D D;
 
     const size_t poly = static_cast<size_t>(L) * N;  // words per polynomial
     const size_t in_poly = static_cast<size_t>(limb) * N + i;
@@ -68,21 +67,9 @@ __global__ void __launch_bounds__(256)
     const size_t strideBk = static_cast<size_t>(cols) * poly;
 
     D acc[TR][TC][SV];
-#pragma unroll
-    for (int r = 0; r < TR; ++r)
-#pragma unroll
-        for (int c = 0; c < TC; ++c)
-#pragma unroll
-            for (int s = 0; s < SV; ++s) acc[r][c][s] = 0;
-    auto reduce = [&](D v) -> W {
-        if constexpr (sizeof(W) == 4) return reduce_u64_sum(v, q, lc.mu64);
-        else return reduce_u128_sum(v, q, lc.mu, lc.kbits, lc.mu64);
-    };
+    MXX_TILE_CLEAR(acc);
     const uint32_t lazy = lc.lazy_terms;
     uint32_t pending = 0;  // products since the last reduction: NOT reset at a term boundary
-    // small tiles are latency-bound: the operands of KU inner steps are loaded before any of them is multiplied
-    // (matmul_group_kernel).  The tail past a term's k re-reads its last step and is dropped.
-    constexpr uint32_t KU = TR * TC * SV <= 8 ? 8 : (TR * TC * SV * sizeof(W) <= 128 ? 2 : 1);
     for (uint32_t t = 0; t < terms; ++t) {
         const MulSumItem it = args.item[t];  // uniform: scalar loads from the kernel-argument segment
         const W *A = static_cast<const W *>(it.a), *B = static_cast<const W *>(it.b);
@@ -90,45 +77,9 @@ __global__ void __launch_bounds__(256)
         size_t a_off[TR];
 #pragma unroll
         for (int r = 0; r < TR; ++r) a_off[r] = static_cast<size_t>(row[r]) * inner * poly + in_poly;
-        for (uint32_t k0 = 0; k0 < inner; k0 += KU) {
-            W av[KU][TR][SV], bv[KU][TC][SV];
-#pragma unroll
-            for (uint32_t u = 0; u < KU; ++u) {
-                const uint32_t k = min(k0 + u, inner - 1);
-#pragma unroll
-                for (int r = 0; r < TR; ++r) *reinterpret_cast<VT *>(av[u][r]) = *reinterpret_cast<const VT *>(A + a_off[r] + k * poly);
-#pragma unroll
-                for (int c = 0; c < TC; ++c) {
-                    // NTB (one row tile, operands beyond the Infinity Cache): B is streamed exactly once and must not displace
-                    // the left operands, which every column tile re-reads (arith.hip, matmul_kernel)
-                    const wxs *src = reinterpret_cast<const wxs *>(B + b_off[c] + k * strideBk);
-                    wxs v;
-                    if constexpr (NTB) v = __builtin_nontemporal_load(src);
-                    else v = *src;
-#pragma unroll
-                    for (int s = 0; s < SV; ++s) bv[u][c][s] = v[s];
-                }
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < KU; ++u) {
-                if (KU > 1 && k0 + u >= inner) break;
-#pragma unroll
-                for (int r = 0; r < TR; ++r)
-#pragma unroll
-                    for (int c = 0; c < TC; ++c)
-#pragma unroll
-                        for (int s = 0; s < SV; ++s) acc[r][c][s] += static_cast<D>(av[u][r][s]) * bv[u][c][s];
-                if (++pending == lazy) {
-                    pending = 0;
-#pragma unroll
-                    for (int r = 0; r < TR; ++r)
-#pragma unroll
-                        for (int c = 0; c < TC; ++c)
-#pragma unroll
-                            for (int s = 0; s < SV; ++s) acc[r][c][s] = reduce(acc[r][c][s]);
-                }
-            }
-        }
+#define MXX_TILE_A(r, k) (A + a_off[r] + (k) * poly)
+#define MXX_TILE_B(c, k) (B + b_off[c] + (k) * strideBk)
+#include "matmul_tile_loop.inc"
     }
     // epilogue: reduce, negate, + addend block, store at dst_col
 #pragma unroll
@@ -141,7 +92,7 @@ __global__ void __launch_bounds__(256)
             W o[SV];
 #pragma unroll
             for (int s = 0; s < SV; ++s) {
-                o[s] = reduce(acc[r][c][s]);
+                o[s] = tile_reduce<W>(acc[r][c][s], q, lc);
                 if (negate) o[s] = o[s] ? static_cast<W>(q - o[s]) : static_cast<W>(0);
             }
             if (addend) {
@@ -193,64 +144,30 @@ template <typename W, int TR, int TC, int SV>
 int launch_sum_cfg(GpuContext *ctx, const MulSumArgs &args, uint32_t terms, size_t b_bytes, void *out, const void *addend,
                    const SumBlock &blk, int negate) {
     const uint32_t N = static_cast<uint32_t>(ctx->N);
-    const uint32_t row_tiles = (blk.rows + TR - 1) / TR, col_tiles = (blk.cols + TC - 1) / TC;
-    const uint32_t threads = std::min<uint32_t>(256, std::max<uint32_t>(64, N / SV));
-    const uint32_t gx = (N / SV + threads - 1) / threads;
-    const dim3 grid(gx, row_tiles * col_tiles, blk.L);  // row_tiles * col_tiles <= 65535: checked with the refusals
+    const TileGrid g = tile_grid<TR, TC, SV>(ctx, blk.rows, blk.cols, blk.L, b_bytes);  // its y extent: checked with the refusals
     W *o = static_cast<W *>(out);
     const W *ad = static_cast<const W *>(addend);
-    // the streamed-once hint under launch_group_cfg's condition: one row tile, and right operands that cannot stay in the
-    // Infinity Cache
-    bool streamed = false;
+    bool streamed = false;  // the 64-bit tiles have no non-temporal instance
     if constexpr (sizeof(W) == 4) {
-        if (row_tiles == 1 && b_bytes > (size_t(1) << 28)) {
+        if (g.streamed) {
             streamed = true;
-            MXX_LAUNCH((matmul_sum_kernel<W, TR, TC, SV, true>), grid, dim3(threads), 0, ctx->stream, args, terms, o, ad, ctx->d_limbs, blk.rows,
-                       blk.cols, blk.out_cols, blk.dst_col, blk.L, N, row_tiles, negate);
+            MXX_LAUNCH((matmul_sum_kernel<W, TR, TC, SV, true>), g.grid, dim3(g.threads), 0, ctx->stream, args, terms, o, ad, ctx->d_limbs,
+                       blk.rows, blk.cols, blk.out_cols, blk.dst_col, blk.L, N, g.row_tiles, negate);
         }
     }
     if (!streamed)
-        MXX_LAUNCH((matmul_sum_kernel<W, TR, TC, SV, false>), grid, dim3(threads), 0, ctx->stream, args, terms, o, ad, ctx->d_limbs, blk.rows,
-                   blk.cols, blk.out_cols, blk.dst_col, blk.L, N, row_tiles, negate);
+        MXX_LAUNCH((matmul_sum_kernel<W, TR, TC, SV, false>), g.grid, dim3(g.threads), 0, ctx->stream, args, terms, o, ad, ctx->d_limbs,
+                   blk.rows, blk.cols, blk.out_cols, blk.dst_col, blk.L, N, g.row_tiles, negate);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// register tile (rows, columns; the slots per lane follow in launch_sum): matmul_group.hip's rule for `rows` stacked rows
-struct SumTile {
-    uint32_t tr, tc;
-};
-SumTile sum_tile(const GpuContext *ctx, uint32_t rows, uint32_t cols, uint32_t L) {
-    const uint64_t N = static_cast<uint64_t>(ctx->N);
-    if (ctx->wide) {
-        // small rings (n = 256): launch-bound; shrink the tile until the grid covers the chip, as launch_matmul does
-        const uint64_t slots = N * L, want = 1024ull * 2 * 64;
-        if (N >= 2 && slots / 2 * ((rows + 3) / 4) * ((cols + 3) / 4) >= want) return {rows >= 4 ? 4u : (rows >= 2 ? 2u : 1u), 4};
-        if (slots * ((rows + 1) / 2) * ((cols + 1) / 2) >= want) return {2, 2};
-        return {1, 1};
-    }
-    if (N >= 4 && rows <= 2) return {rows, 8};  // 16-byte loads: B is streamed once
-    return {rows <= 4 ? 4u : 8u, 8};            // 5 and more: 8-row tiles
-}
-
 int launch_sum(GpuContext *ctx, const MulSumArgs &args, uint32_t terms, size_t b_bytes, void *out, const void *addend, const SumBlock &blk,
                int negate) {
-    const SumTile t = sum_tile(ctx, blk.rows, blk.cols, blk.L);
-#define MXX_SUM(W, R, C, S) return launch_sum_cfg<W, R, C, S>(ctx, args, terms, b_bytes, out, addend, blk, negate)
-    if (ctx->wide) {
-        if (t.tc == 4) {
-            if (t.tr == 4) MXX_SUM(uint64_t, 4, 4, 2);
-            if (t.tr == 2) MXX_SUM(uint64_t, 2, 4, 2);
-            MXX_SUM(uint64_t, 1, 4, 2);
-        }
-        if (t.tr == 2) MXX_SUM(uint64_t, 2, 2, 1);
-        MXX_SUM(uint64_t, 1, 1, 1);
-    }
-    if (t.tr == 1) MXX_SUM(uint32_t, 1, 8, 4);
-    if (t.tr == 2) MXX_SUM(uint32_t, 2, 8, 4);
-    if (t.tr == 4) MXX_SUM(uint32_t, 4, 8, 1);
-    MXX_SUM(uint32_t, 8, 8, 1);
-#undef MXX_SUM
+    return dispatch_stacked_tile(ctx, stacked_tile(ctx, blk.rows, blk.cols, blk.L), [&](auto cfg) {
+        typedef decltype(cfg) T;
+        return launch_sum_cfg<typename T::W, T::TR, T::TC, T::SV>(ctx, args, terms, b_bytes, out, addend, blk, negate);
+    });
 }
 
 template <typename W>
@@ -315,8 +232,8 @@ int mul_sum_impl(const char *who, GpuMatrix *out, size_t dst_col, size_t cols, c
     }
     if (out->rows > 0xffffffffull || out->cols > 0xffffffffull) return refuse("matrix too large");
     if (out->rows && cols) {  // the grid's y extent holds row tiles x column tiles
-        const SumTile tl = sum_tile(ctx, static_cast<uint32_t>(out->rows), static_cast<uint32_t>(cols), static_cast<uint32_t>(L));
-        if (static_cast<uint64_t>((out->rows + tl.tr - 1) / tl.tr) * ((cols + tl.tc - 1) / tl.tc) > 65535) return refuse("matrix too large");
+        const TileShape tl = stacked_tile(ctx, out->rows, cols, L);
+        if (!tile_grid_fits(out->rows, cols, tl.tr, tl.tc)) return refuse("matrix too large");
     }
     // ---- accepted ----
     out->format = GPU_POLY_FORMAT_EVAL;
