@@ -198,6 +198,76 @@ def gadget(size: int, moduli, base_bits: int, n: int) -> np.ndarray:
     return out
 
 
+def gadget_small(size: int, moduli, base_bits: int, n: int) -> np.ndarray:
+    """The `small` gadget matrix I_size (x) (1, 2^b, ..., 2^((dpt-1) b)) in coefficient form, (size, size * dpt, L, n):
+    entry (r, r*dpt + e) is the constant 2^(e b) mod q_l in every tower l."""
+    L = len(moduli)
+    dpt = digits_per_tower(moduli, base_bits)
+    out = np.zeros((size, size * dpt, L, n), dtype=np.uint64)
+    for r in range(size):
+        for e in range(dpt):
+            for l in range(L):
+                out[r, r * dpt + e, l, 0] = pow(2, e * base_bits, int(moduli[l]))
+    return out
+
+
+def gadget_scalar_digits(c, moduli, base_bits: int, dpt: int) -> np.ndarray:
+    """G^-1(g o c) for a ring element c given as (L, n) coefficient residues: the k x k block (k = L * dpt, returned as
+    (k, k, L, n) coefficient residues) whose column (t, e) holds the digits of the element that is c_t * 2^(e b) mod q_t
+    in tower t and 0 in every other tower - entry t*dpt + e of g o c."""
+    L, n = np.asarray(c).shape
+    k = L * dpt
+    out = np.zeros((k, k, L, n), dtype=np.uint64)
+    for t in range(L):
+        q = int(moduli[t])
+        for e in range(dpt):
+            elem = np.zeros((L, n), dtype=np.uint64)
+            elem[t] = [int(v) * pow(2, e * base_bits, q) % q for v in c[t]]
+            out[:, t * dpt + e] = digits(elem, moduli, base_bits, dpt)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- fused products
+def slot_mul_sum(addend, lhss, rhss, moduli, negate: bool, slots=None) -> np.ndarray:
+    """addend +- sum_t lhss[t] rhss[t] in the evaluation domain, slot by slot:
+    out[i, c, l, s] = addend[i, c, l, s] +- sum_t sum_k lhss[t][i, k, l, s] * rhss[t][k, c, l, s] mod q_l for s in `slots`
+    (None: every index of the last axis).  lhss[t] is (rows, k_t, L, n), rhss[t] (k_t, cols, L, n), addend (rows, cols, L, n)
+    or None (zero).  Python integers throughout; returns (rows, cols, L, len(slots)) uint64."""
+    pick = (lambda a: np.asarray(a)) if slots is None else (lambda a: np.asarray(a)[..., [int(s) for s in slots]])
+    q = np.asarray([int(v) for v in moduli], dtype=object).reshape(1, 1, -1, 1)
+    total = None
+    for lhs, rhs in zip(lhss, rhss):
+        a, b = pick(lhs).astype(object), pick(rhs).astype(object)
+        assert a.shape[1] == b.shape[0]
+        for k in range(a.shape[1]):
+            term = a[:, k, None] * b[None, k]
+            total = term if total is None else total + term
+    if addend is None:
+        assert total is not None, "no operand to take the shape from"
+        base = np.zeros(total.shape, dtype=object)
+    else:
+        base = pick(addend).astype(object)
+    if total is None:
+        total = np.zeros(base.shape, dtype=object)
+    out = (base - total) % q if negate else (base + total) % q
+    return out.astype(np.uint64)
+
+
+def monomial_mul(a, shift: int, q) -> np.ndarray:
+    """a * x^shift in Z_q[x] / (x^n + 1) for shift in [0, 2n), on coefficient residues (..., n): coefficient i goes to
+    position i + shift, and every pass over x^n changes its sign.  q: an integer, or an array that broadcasts against
+    a (one modulus per tower as an (L, 1) column)."""
+    a = np.asarray(a, dtype=np.uint64)
+    n = a.shape[-1]
+    assert 0 <= shift < 2 * n
+    qv = np.asarray(q, dtype=np.uint64)  # residues and moduli are below 2^62: q - a stays in uint64
+    dst = np.arange(n) + int(shift)
+    signed = np.where((dst // n) % 2 == 1, (qv - a) % qv, a)
+    out = np.empty_like(a)
+    out[..., dst % n] = signed
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- wire format
 def centred_crt(residues, moduli) -> int:
     """The integer x in (-Q/2, Q/2] with x = residues[l] (mod moduli[l]) for every l, Q = prod(moduli)."""

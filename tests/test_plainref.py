@@ -135,3 +135,91 @@ def test_compact_payload_matches_oracle(spec):
     assert P.compact_pack(vals, w) == payload
     c = Q // 3
     assert P.modulus_switch(c, Q, 1 << 20) == (c << 20) // Q
+
+
+# ---------------------------------------------------------------------------------------------- fused operations
+# plainref's definitions of the fused products (slot_mul_sum, monomial_mul, gadget_small, gadget_scalar_digits) against
+# the oracle's restatement of the same operation, composed there from O.matmul, O.pointwise, O.ntt_vec, O.matrix_ntt,
+# O.gadget_matrix and O.decompose where the oracle has no entry of its own.  tests/test_gpu_fused_width_classes.py holds
+# the kernels to plainref alone.
+def _fused_rings(bits, low):
+    """(n, moduli) of one class: n = 4 and 32 (2 and 4 at 10 bits); bits = "mixed": a 51-bit and a low 12-bit limb."""
+    if bits == "mixed":
+        return [(n, [P.primes(n, 51, 1)[0], P.primes(n, 12, 1, low=True)[0]]) for n in (4, 32)]
+    return [(n, P.primes(n, bits, 2, low=low)) for n in ((2, 4) if bits <= 10 else (4, 32))]
+
+
+def _rand(rng, shape, moduli):
+    """(shape[0], shape[1], L, n) residues"""
+    return np.stack([rng.integers(0, int(q), shape, dtype=np.uint64) for q in moduli], axis=2)
+
+
+FUSED_CLASSES = [(b, low) for b in WIDTHS for low in (False, True)] + [("mixed", False)]
+
+
+@pytest.mark.parametrize("bits,low", FUSED_CLASSES)
+def test_slot_mul_sum_matches_oracle(bits, low):
+    for n, moduli in _fused_rings(bits, low):
+        rng = np.random.default_rng(n + 31 * len(moduli) + (bits if bits != "mixed" else 99))
+        top = np.asarray(moduli, dtype=np.uint64).reshape(-1, 1) - np.uint64(1)
+        lhss = [_rand(rng, (2, k, n), moduli) for k in (1, 4, 2)]
+        rhss = [_rand(rng, (k, 3, n), moduli) for k in (1, 4, 2)]
+        lhss[1][:, 1:3] = top  # (q - 1)^2 products, two in a row
+        rhss[1][1:3] = top
+        addend = _rand(rng, (2, 3, n), moduli)
+        addend[0, 0] = top
+        prod = np.zeros_like(addend)
+        for a, b in zip(lhss, rhss):
+            prod = O.pointwise("add", prod, O.matmul(a, b, moduli), moduli)
+        for negate in (False, True):
+            want = O.pointwise("sub" if negate else "add", addend, prod, moduli)
+            assert np.array_equal(P.slot_mul_sum(addend, lhss, rhss, moduli, negate), want)
+            zero = np.zeros_like(addend)
+            assert np.array_equal(P.slot_mul_sum(None, lhss, rhss, moduli, negate), O.pointwise("sub" if negate else "add", zero, prod, moduli))
+        slots = [0, n - 1]
+        assert np.array_equal(P.slot_mul_sum(addend, lhss, rhss, moduli, True, slots), O.pointwise("sub", addend, prod, moduli)[..., slots])
+        assert np.array_equal(P.slot_mul_sum(addend, [], [], moduli, True), addend)
+
+
+@pytest.mark.parametrize("bits,low", FUSED_CLASSES)
+def test_monomial_mul_matches_oracle(bits, low):
+    """a * x^s is the negacyclic product with the one-hot +-x^(s mod n), and slot by slot the product with its transform."""
+    for n, moduli in _fused_rings(bits, low):
+        pats = _patterns(moduli, n, 5 * n + len(moduli))
+        for l, q in enumerate(moduli):
+            for s in sorted({0, 1, n - 1, n, n + 1, 2 * n - 1, (3 * n) // 2}):
+                mono = np.zeros(n, dtype=np.uint64)
+                mono[s % n] = 1 if s < n else q - 1
+                assert np.array_equal(P.monomial_mul(np.asarray([1] + [0] * (n - 1)), s, q), mono)
+                for a in pats[:, l]:
+                    got = P.monomial_mul(a, s, q)
+                    assert np.array_equal(got, O.negacyclic_schoolbook(a, mono, q)), (bits, low, n, l, s)
+                    slotwise = [int(x) * int(f) % q for x, f in zip(O.ntt_vec(a, q), O.ntt_vec(mono, q))]
+                    assert [int(v) for v in O.ntt_vec(got, q)] == slotwise
+        # every tower at once, one modulus per row
+        col = np.asarray(moduli, dtype=np.uint64).reshape(-1, 1)
+        assert np.array_equal(P.monomial_mul(pats[0], n + 1, col), np.stack([P.monomial_mul(pats[0, l], n + 1, q) for l, q in enumerate(moduli)]))
+
+
+def _fused_bases(moduli):
+    """two digits per tower, and a smaller base whose last digit is short where the width allows one"""
+    width = max(int(q).bit_length() for q in moduli)
+    return sorted({(width + 1) // 2, width // 3 + 1, max(width // 5, 1) + 1})
+
+
+@pytest.mark.parametrize("bits,low", FUSED_CLASSES)
+def test_gadget_small_and_scalar_digits_match_oracle(bits, low):
+    for n, moduli in _fused_rings(bits, low):
+        L = len(moduli)
+        pats = _patterns(moduli, n, 3 * n + L)
+        for base in _fused_bases(moduli):
+            dpt = P.digits_per_tower(moduli, base)
+            k = L * dpt
+            assert np.array_equal(P.gadget_small(2, moduli, base, n), O.gadget_matrix(2, moduli, n, base, small=True, eval_format=False))
+            g_eval = O.gadget_matrix(1, moduli, n, base)  # 1 x k, evaluation domain
+            for c in pats:
+                c_eval = O.matrix_ntt(c[None, None], moduli)
+                gc = O.matrix_ntt(O.pointwise("mul", g_eval, c_eval, moduli), moduli, inverse=True)  # g o c, coefficients
+                want = O.decompose(gc, moduli, base)
+                assert want.shape == (k, k, L, n)
+                assert np.array_equal(P.gadget_scalar_digits(c, moduli, base, dpt), want), (bits, low, n, base)
