@@ -45,7 +45,8 @@
  *       3. Every other entry that reads matrices and writes one refuses any overlap between what it writes and what
  *          it reads, the same block included (gpu_matrix_gauss_samp_gq_arb_base before its source is transformed).
  *          gpupoly_matrix_add_rows / _ntt_add_rows are judged on the destination row block: an operand may be a view
- *          of other rows of `out`.  In gpupoly_matrix_mul_decompose_gadget_scalar_many / _const_many no outs[j] overlaps
+ *          of other rows of `out`.  gpupoly_matrix_decompose_rows is judged like gpu_matrix_decompose_base: its `out`
+ *          overlaps no byte of `src`, whichever rows the window reads.  In gpupoly_matrix_mul_decompose_gadget_scalar_many / _const_many no outs[j] overlaps
  *          any lhss[o], scalar_1x1, another output or another operand's addend.
  *       4. Several outputs: the blocks of gpupoly_matrix_split_columns are pairwise disjoint and disjoint from the
  *          source (the blocks of a concat may repeat, its output is disjoint from all of them); in
@@ -285,6 +286,44 @@ int gpupoly_matrix_fill_identity(GpuMatrix *out, const GpuMatrix *scalar_1x1);
  * src/sampler/gpu.rs:91-115, `sample_hash_decomposed` / `sample_hash_small_decomposed`).                   */
 int gpupoly_matrix_sample_decomposed(GpuMatrix *out, int dist_type, double sigma, GpuRngSeed seed, uint32_t base_bits,
                                      int small);
+/* A row window of a decomposition: out (R x c, c == src->cols) = rows [row_start, row_start + R) of D = G^-1(src), the
+ * (src->rows * k) x c matrix gpu_matrix_decompose_base (small != 0: _small) writes - L = limbs of out's level, dpt =
+ * ceil(crt_bits / base_bits), k = small ? dpt : dpt * L, row j*k + t*dpt + e of D = digit e of tower t of src[j, .]
+ * (small: row j*dpt + e, tower 0).  The window rule: row_start + R <= src->rows * k, and the window may start and end
+ * anywhere - inside a tower's digit block, across towers, across source rows.  Bit for bit the result of
+ * gpu_matrix_decompose_base(_small) followed by gpu_matrix_copy_block of those rows, `out` keeping the format it was
+ * created with (EVAL or COEFF), but the digit transforms - the cost of a decomposition - run for the R rows kept only:
+ * the reference builds all r*k digit rows and slices (decompose_chunk / small_decompose_chunk of its matrix type; the
+ * rhs_full.slice(inner_start, ..) of src/lookup/ggh15/poly_encoding_gpu.rs:515,566).  src is COEFF or EVAL and is left
+ * untouched (a PACKED24 src is unpacked first); of an EVAL src only the source rows the window touches are inverse-
+ * transformed into scratch, which comes from the context's allocator, is released stream-ordered and is sized by the
+ * window.  Enqueued on the context's stream; the host does not block.  R = 0 or c = 0 succeed with nothing launched
+ * (`out` tagged EVAL, as gpu_matrix_decompose_base tags an empty result).
+ * Overlap: rule 3 - `out` must not overlap `src`, row views included (the message contains "overlap").
+ * Refused, with nothing launched and `out` (contents AND tag) untouched, everything checked before the first launch,
+ * the message naming this entry: a null matrix; base_bits of 0 or >= 63; a context, level or column mismatch; a window
+ * past src->rows * k; `out` overlapping `src`.                                                                        */
+int gpupoly_matrix_decompose_rows(const GpuMatrix *src, uint32_t base_bits, int small, size_t row_start, GpuMatrix *out);
+/* The same window of the decomposition of a SAMPLED matrix: out (R x c) = rows [row_start, row_start + R) of G^-1 of
+ * columns [col_offset, col_offset + c) of the src_rows x full_ncol matrix gpu_matrix_sample_distribution(seed) fills.
+ * The window rule: col_offset + c <= full_ncol and row_start + R <= src_rows * k (k as above, from out's level).  Bit
+ * for bit gpu_matrix_sample_distribution_columns + gpu_matrix_decompose_base(_small) + gpu_matrix_copy_block, for every
+ * dist_type, under the default keying and under MXX_HIP_RNG_COMPAT=reference.  Only the source rows the window touches
+ * are sampled and, for the uniform distribution (whose limbs are keyed separately), only the towers it touches when
+ * the window lies inside one source row; the samples stay coefficients, no source transform runs in either direction.
+ * This is what every production caller asks for: sample_hash_decomposed_columns / sample_hash_small_decomposed_columns
+ * take a column chunk of a conceptual d x m_g matrix (src/lookup/ggh15/pubkey_gpu.rs:398-407,495-504,
+ * src/lookup/ggh15/poly_encoding_gpu.rs:453-462,520-543; also ggh15/encoding.rs, ggh15/pubkey.rs, lwe/utils.rs,
+ * src/slot_transfer/bgg_poly_encoding_gpu.rs) and poly_encoding_gpu.rs:515,566 keep rows [inner_start, inner_start +
+ * inner_len) of it.  Stream, scratch and empty-window behaviour as gpupoly_matrix_decompose_rows.
+ * Overlap: the only matrix is `out`; nothing can overlap.
+ * Refused, with nothing launched and `out` (contents AND tag) untouched, everything checked before the first launch,
+ * the message naming this entry: a null `out`; base_bits of 0 or >= 63; an invalid dist_type; a Gaussian sigma that is
+ * not positive; a window past src_rows * k or past full_ncol; src_rows * full_ncol beyond the samplers' 48-bit stream
+ * ids.                                                                                                               */
+int gpupoly_matrix_sample_decomposed_window(GpuMatrix *out, int dist_type, double sigma, GpuRngSeed seed,
+                                            uint32_t base_bits, int small, size_t src_rows, size_t full_ncol,
+                                            size_t col_offset, size_t row_start);
 /* hipEvent timing on the context's compute stream (bench.py's roofline leg). */
 int gpupoly_timer_start(GpuContext *ctx);
 int gpupoly_timer_stop(GpuContext *ctx, float *out_ms);

@@ -119,6 +119,8 @@ SIGNATURES = {
     "gpupoly_matrix_fill_zero": (C.c_int, [_vp]),
     "gpupoly_matrix_fill_identity": (C.c_int, [_vp, _vp]),
     "gpupoly_matrix_sample_decomposed": (C.c_int, [_vp, C.c_int, C.c_double, GpuRngSeed, C.c_uint32, C.c_int]),
+    "gpupoly_matrix_decompose_rows": (C.c_int, [_vp, C.c_uint32, C.c_int, _sz, _vp]),
+    "gpupoly_matrix_sample_decomposed_window": (C.c_int, [_vp, C.c_int, C.c_double, GpuRngSeed, C.c_uint32, C.c_int, _sz, _sz, _sz, _sz]),
     "gpupoly_timer_start": (C.c_int, [_vp]),
     "gpupoly_timer_stop": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "gpupoly_timer_mark": (C.c_int, [_vp, C.c_uint32]),

@@ -302,7 +302,10 @@ bool pack24_eligible(const GpuMatrix *m);
 int pack24_store(GpuMatrix *m, bool ntt);
 
 // sampling.hip: fills `out` with samples; keep_coeff leaves them in the coefficient domain
-int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t full_ncol, size_t col_offset, bool keep_coeff);
+// row_offset: `out` holds rows [row_offset, row_offset + out->rows) of the conceptual matrix; tower_count > 0 (uniform
+// only, whose limbs are keyed separately): only limbs [tower_first, tower_first + tower_count) are written
+int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t full_ncol, size_t col_offset, bool keep_coeff,
+                size_t row_offset = 0, uint32_t tower_first = 0, uint32_t tower_count = 0);
 
 int ctx_activate(const GpuContext *ctx);                   // hipSetDevice
 bool ctx_is_registered(const GpuContext *ctx);             // still a live context of this process (runtime.hip's registry)
@@ -333,10 +336,10 @@ int launch_ntt(GpuContext *ctx, void *data, size_t vectors, int limbs_per_poly, 
 // tuned LDS kernels (ntt_lds_u32.hip / ntt_lds_u64.hip); return -1 when no tuned kernel covers logN
 int launch_ntt_lds_u32(GpuContext *ctx, uint32_t *data, size_t vectors, uint32_t L, bool inverse);
 int launch_ntt_digits_u32(GpuContext *ctx, uint32_t *out, const uint32_t *coeff, size_t out_vectors, uint32_t L,
-                          uint32_t src_cols, uint32_t towers, uint32_t dpt, uint32_t base_bits, size_t k);
+                          uint32_t src_cols, uint32_t towers, uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0 = 0);
 int launch_ntt_lds_u64(GpuContext *ctx, uint64_t *data, size_t vectors, uint32_t L, bool inverse);
 int launch_ntt_digits_u64(GpuContext *ctx, uint64_t *out, const uint64_t *coeff, size_t out_vectors, uint32_t L,
-                          uint32_t src_cols, uint32_t towers, uint32_t dpt, uint32_t base_bits, size_t k);
+                          uint32_t src_cols, uint32_t towers, uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0 = 0);
 // out <- INTT(in o w), w one resident EVAL-form ring element [L][N]; -1: no fused kernel for this context
 int launch_intt_oop_u32(GpuContext *ctx, uint32_t *out, const uint32_t *in, size_t vectors, uint32_t L);
 int launch_ntt_add_u32(GpuContext *ctx, uint32_t *out, const uint32_t *src, const uint32_t *add, size_t vectors, uint32_t L);

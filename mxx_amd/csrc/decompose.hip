@@ -52,6 +52,37 @@ __global__ void decompose_kernel(W *__restrict__ out, const W *__restrict__ src,
     }
 }
 
+// The same digits for a launch that writes only digit rows [td0, td0 + ky) of each source row, ky consecutive output
+// rows per source row (a piece of a row window, decompose_window): item = (source row, local digit row, column,
+// coefficient), so the work is that of the rows written
+template <typename W>
+__global__ void decompose_rows_kernel(W *__restrict__ out, const W *__restrict__ src, const LimbConst *__restrict__ limbs,
+                                      size_t src_rows, uint32_t src_cols, uint32_t L, uint32_t N, uint32_t dpt,
+                                      uint32_t base_bits, uint32_t ky, uint32_t td0) {
+    const size_t idx = item_index();
+    const size_t total = src_rows * ky * src_cols * N;
+    if (idx >= total) return;
+    const uint32_t i = static_cast<uint32_t>(idx % N);
+    const size_t opoly = idx / N;  // (r * ky + y) * src_cols + c
+    const size_t orow = opoly / src_cols, c = opoly - orow * src_cols;
+    const size_t r = orow / ky;
+    const uint32_t td = static_cast<uint32_t>(orow - r * ky) + td0;
+    const uint32_t t = td / dpt, d = td - t * dpt;
+    const uint64_t residue = static_cast<uint64_t>(src[((r * src_cols + c) * L + t) * N + i]);
+    const uint32_t src_bits = limbs[t].kbits, shift = d * base_bits;
+    uint64_t mask = 0;
+    if (shift < src_bits) {
+        const uint32_t rem = src_bits - shift;
+        const uint32_t db = base_bits < rem ? base_bits : rem;
+        mask = db >= 64 ? ~0ull : ((1ull << db) - 1);
+    }
+    const uint64_t digit = shift >= 64 ? 0 : ((residue >> shift) & mask);
+    for (uint32_t l = 0; l < L; ++l) {
+        const uint64_t ql = limbs[l].q;
+        out[(opoly * L + l) * N + i] = static_cast<W>(digit >= ql ? digit % ql : digit);
+    }
+}
+
 // G = I_size (x) g written in EVAL form (all slots of a constant poly are equal)
 template <typename W>
 __global__ void fill_gadget_kernel(W *__restrict__ out, const LimbConst *__restrict__ limbs, size_t rows, size_t cols,
@@ -122,73 +153,122 @@ static int fill_gadget_impl(GpuMatrix *out, uint32_t base_bits, bool small) {
     return 0;
 }
 
+// Digit rows [td0, td0 + ky) of each of `nsrc` source rows at `coeff` (coefficient words, rows x src_cols x L), written
+// as nsrc * ky consecutive rows at `out`.  EVAL: the digits are generated inside the forward transform's load where such a
+// kernel exists (no COEFF digit matrix is written), else the plain kernel followed by the transform.
+static int decompose_segment(GpuContext *ctx, void *out, const void *coeff, size_t nsrc, size_t cols, size_t L, size_t k,
+                             uint32_t towers, uint32_t dpt, uint32_t base_bits, size_t ky, uint32_t td0, bool eval) {
+    const size_t out_vectors = nsrc * ky * cols * L;
+    if (eval) {
+        const int frc = ctx->wide ? launch_ntt_digits_u64(ctx, static_cast<uint64_t *>(out), static_cast<const uint64_t *>(coeff), out_vectors,
+                                                          static_cast<uint32_t>(L), (uint32_t)cols, towers, dpt, base_bits, ky, td0)
+                                  : launch_ntt_digits_u32(ctx, static_cast<uint32_t *>(out), static_cast<const uint32_t *>(coeff), out_vectors,
+                                                          static_cast<uint32_t>(L), (uint32_t)cols, towers, dpt, base_bits, ky, td0);
+        if (frc >= 0) return frc;
+    }
+    if (td0 == 0 && ky == k) {  // every digit row: each source residue is read once for all its digits
+        const size_t polys = nsrc * cols;
+        const dim3 blocks = item_grid(polys * towers * static_cast<size_t>(ctx->N), 256);
+        if (ctx->wide)
+            MXX_LAUNCH(decompose_kernel<uint64_t>, blocks, dim3(256), 0, ctx->stream, static_cast<uint64_t *>(out),
+                       static_cast<const uint64_t *>(coeff), ctx->d_limbs, polys, (uint32_t)cols, (uint32_t)L, (uint32_t)ctx->N, towers,
+                       dpt, base_bits, k);
+        else
+            MXX_LAUNCH(decompose_kernel<uint32_t>, blocks, dim3(256), 0, ctx->stream, static_cast<uint32_t *>(out),
+                       static_cast<const uint32_t *>(coeff), ctx->d_limbs, polys, (uint32_t)cols, (uint32_t)L, (uint32_t)ctx->N, towers,
+                       dpt, base_bits, k);
+    } else {
+        const dim3 blocks = item_grid(nsrc * ky * cols * static_cast<size_t>(ctx->N), 256);
+        if (ctx->wide)
+            MXX_LAUNCH(decompose_rows_kernel<uint64_t>, blocks, dim3(256), 0, ctx->stream, static_cast<uint64_t *>(out),
+                       static_cast<const uint64_t *>(coeff), ctx->d_limbs, nsrc, (uint32_t)cols, (uint32_t)L, (uint32_t)ctx->N, dpt,
+                       base_bits, (uint32_t)ky, td0);
+        else
+            MXX_LAUNCH(decompose_rows_kernel<uint32_t>, blocks, dim3(256), 0, ctx->stream, static_cast<uint32_t *>(out),
+                       static_cast<const uint32_t *>(coeff), ctx->d_limbs, nsrc, (uint32_t)cols, (uint32_t)L, (uint32_t)ctx->N, dpt,
+                       base_bits, (uint32_t)ky, td0);
+    }
+    HIP_TRY(hipGetLastError());
+    // output honours the format it was created with (MatrixDecompose.cu:910-914,1318-1328)
+    return eval ? launch_ntt(ctx, out, out_vectors, static_cast<int>(L), false) : 0;
+}
+
+// Rows [row_start, row_start + R) of G^-1 of the source rows at `coeff` (row 0 there = source row row_start / k), cut at
+// source-row boundaries: the rest of the first source row, the source rows the window holds whole, the start of the
+// last one - at most three launches, each with exactly one workgroup set per window row and none of the kernels
+// dividing by k.  The whole matrix (row_start = 0, R = r k) is the middle piece alone: the one launch it always was.
+static int decompose_window(GpuContext *ctx, void *out, const void *coeff, size_t cols, size_t L, size_t k, uint32_t towers,
+                            uint32_t dpt, uint32_t base_bits, size_t row_start, size_t R, bool eval) {
+    const size_t row_bytes = cols * L * static_cast<size_t>(ctx->N) * static_cast<size_t>(ctx->word_bytes);
+    char *o = static_cast<char *>(out);
+    const char *c = static_cast<const char *>(coeff);
+    const size_t first = row_start % k;
+    size_t done = 0;
+    if (first || R < k) {
+        const size_t ky = std::min(R, k - first);
+        if (int rc = decompose_segment(ctx, o, c, 1, cols, L, k, towers, dpt, base_bits, ky, static_cast<uint32_t>(first), eval)) return rc;
+        done = ky;
+        c += row_bytes;
+    }
+    if (const size_t whole = (R - done) / k) {
+        if (int rc = decompose_segment(ctx, o + done * row_bytes, c, whole, cols, L, k, towers, dpt, base_bits, k, 0, eval)) return rc;
+        done += whole * k;
+        c += whole * row_bytes;
+    }
+    if (done < R) return decompose_segment(ctx, o + done * row_bytes, c, 1, cols, L, k, towers, dpt, base_bits, R - done, 0, eval);
+    return 0;
+}
+
+// out (R x cols, checked by the caller together with everything else that can refuse) <- rows [row_start, row_start + R)
+// of G^-1(src).  Digits are taken from coefficient-domain residues: of an EVAL source, the rows the window touches are
+// inverse-transformed into scratch.
+static int decompose_core(const GpuMatrix *src, uint32_t base_bits, bool small, size_t row_start, GpuMatrix *out) {
+    GpuContext *ctx = src->ctx;
+    const int requested = out->format;
+    const size_t L = matrix_limbs(src), R = out->rows, cols = src->cols;
+    const uint32_t dpt = (ctx->crt_bits + base_bits - 1) / base_bits;
+    const size_t k = small ? dpt : static_cast<size_t>(dpt) * L;
+    if (R == 0 || cols == 0) {
+        out->format = GPU_POLY_FORMAT_EVAL;
+        return 0;
+    }
+    if (ctx_activate(ctx)) return 1;
+    const size_t r0 = row_start / k, nsrc = (row_start + R - 1) / k - r0 + 1;
+    const size_t row_bytes = cols * L * static_cast<size_t>(ctx->N) * static_cast<size_t>(ctx->word_bytes);
+    const void *coeff = static_cast<const char *>(words_ptr(src)) + r0 * row_bytes;
+    CtxBlock tmp_block(ctx);  // back to the cache at scope exit (stream-ordered behind its readers), error paths included
+    if (src->format == GPU_POLY_FORMAT_EVAL) {
+        const size_t bytes = nsrc * row_bytes;
+        if (tmp_block.alloc(bytes)) return 1;
+        int rc = ctx->wide ? -1 : launch_intt_oop_u32(ctx, static_cast<uint32_t *>(tmp_block.ptr), static_cast<const uint32_t *>(coeff),
+                                                      nsrc * cols * L, static_cast<uint32_t>(L));
+        if (rc < 0) {  // no out-of-place transform for this context: copy, then in place
+            MXX_TRACED_COPY("copy (device to device)", ctx->stream, 2.0 * bytes,
+                            HIP_TRY(hipMemcpyAsync(tmp_block.ptr, coeff, bytes, hipMemcpyDeviceToDevice, ctx->stream)));
+            rc = launch_ntt(ctx, tmp_block.ptr, nsrc * cols * L, static_cast<int>(L), true);
+        }
+        if (rc) return rc;
+        coeff = tmp_block.ptr;
+    }
+    const uint32_t towers = small ? 1u : static_cast<uint32_t>(L);
+    const bool eval = requested == GPU_POLY_FORMAT_EVAL;
+    const int rc = decompose_window(ctx, words_ptr(out), coeff, cols, L, k, towers, dpt, base_bits, row_start - r0 * k, R, eval);
+    if (rc == 0) out->format = eval ? GPU_POLY_FORMAT_EVAL : GPU_POLY_FORMAT_COEFF;
+    return rc;
+}
+
 static int decompose_impl(const GpuMatrix *src, uint32_t base_bits, GpuMatrix *out, bool small) {
     if (!src || !out) return set_error("gpu_matrix_decompose_base: null matrix");
     if (base_bits == 0) return set_error("base_bits must be non-zero in gpu_matrix_decompose_base");
     if (src->ctx != out->ctx || src->level != out->level)
         return set_error("context mismatch in gpu_matrix_decompose_base");
     if (storage_overlaps(src, out)) return set_error("gpu_matrix_decompose_base: output must not alias the source");
-    GpuContext *ctx = src->ctx;
-    const int requested = out->format;
     const size_t L = matrix_limbs(src);
-    const uint32_t dpt = (ctx->crt_bits + base_bits - 1) / base_bits;
+    const uint32_t dpt = (src->ctx->crt_bits + base_bits - 1) / base_bits;
     const size_t k = small ? dpt : static_cast<size_t>(dpt) * L;
     if (out->rows != src->rows * k || out->cols != src->cols)
         return set_error("output size mismatch in gpu_matrix_decompose_base");
-    const size_t polys = matrix_polys(src);
-    if (polys == 0) {
-        out->format = GPU_POLY_FORMAT_EVAL;
-        return 0;
-    }
-    if (ctx_activate(ctx)) return 1;
-    // digits are taken from coefficient-domain residues: INTT a private copy if needed
-    const void *coeff = words_ptr(src);
-    CtxBlock tmp_block(ctx);  // back to the cache at scope exit (stream-ordered behind its readers), error paths included
-    if (src->format == GPU_POLY_FORMAT_EVAL) {
-        if (tmp_block.alloc(src->bytes)) return 1;
-        int rc = ctx->wide ? -1 : launch_intt_oop_u32(ctx, static_cast<uint32_t *>(tmp_block.ptr), static_cast<const uint32_t *>(words_ptr(src)),
-                                                      polys * L, static_cast<uint32_t>(L));
-        if (rc < 0) {  // no out-of-place transform for this context: copy, then in place
-            MXX_TRACED_COPY("copy (device to device)", ctx->stream, 2.0 * src->bytes,
-                            HIP_TRY(hipMemcpyAsync(tmp_block.ptr, words_ptr(src), src->bytes, hipMemcpyDeviceToDevice, ctx->stream)));
-            rc = launch_ntt(ctx, tmp_block.ptr, polys * L, static_cast<int>(L), true);
-        }
-        if (rc) return rc;
-        coeff = tmp_block.ptr;
-    }
-    const uint32_t towers = small ? 1u : static_cast<uint32_t>(L);
-    if (requested == GPU_POLY_FORMAT_EVAL) {
-        // digits generated inside the forward transform's load: no COEFF digit matrix is written
-        const int frc = ctx->wide ? launch_ntt_digits_u64(ctx, static_cast<uint64_t *>(words_ptr(out)), static_cast<const uint64_t *>(coeff),
-                                                          matrix_polys(out) * L, static_cast<uint32_t>(L), (uint32_t)src->cols,
-                                                          towers, dpt, base_bits, k)
-                                  : launch_ntt_digits_u32(ctx, static_cast<uint32_t *>(words_ptr(out)), static_cast<const uint32_t *>(coeff),
-                                                          matrix_polys(out) * L, static_cast<uint32_t>(L), (uint32_t)src->cols,
-                                                          towers, dpt, base_bits, k);
-        if (frc >= 0) {
-            if (frc == 0) out->format = GPU_POLY_FORMAT_EVAL;
-            return frc;
-        }
-    }
-    const size_t total = polys * towers * static_cast<size_t>(ctx->N);
-    const dim3 blocks = item_grid(total, 256);
-    if (ctx->wide)
-        MXX_LAUNCH(decompose_kernel<uint64_t>, blocks, dim3(256), 0, ctx->stream,
-                           static_cast<uint64_t *>(words_ptr(out)), static_cast<const uint64_t *>(coeff), ctx->d_limbs, polys,
-                           (uint32_t)src->cols, (uint32_t)L, (uint32_t)ctx->N, towers, dpt, base_bits, k);
-    else
-        MXX_LAUNCH(decompose_kernel<uint32_t>, blocks, dim3(256), 0, ctx->stream,
-                           static_cast<uint32_t *>(words_ptr(out)), static_cast<const uint32_t *>(coeff), ctx->d_limbs, polys,
-                           (uint32_t)src->cols, (uint32_t)L, (uint32_t)ctx->N, towers, dpt, base_bits, k);
-    HIP_TRY(hipGetLastError());
-    out->format = GPU_POLY_FORMAT_COEFF;
-    if (requested == GPU_POLY_FORMAT_EVAL) {
-        // output honours the format it was created with (MatrixDecompose.cu:910-914,1318-1328)
-        int rc = launch_ntt(ctx, words_ptr(out), matrix_polys(out) * L, static_cast<int>(L), false);
-        if (rc) return rc;
-        out->format = GPU_POLY_FORMAT_EVAL;
-    }
-    return 0;
+    return decompose_core(src, base_bits, small, 0, out);
 }
 
 extern "C" int gpu_matrix_fill_gadget(GpuMatrix *out, uint32_t base_bits) {
@@ -285,6 +365,86 @@ extern "C" int gpupoly_matrix_sample_decomposed(GpuMatrix *out, int dist_type, d
     src.borrowed = true;  // the block is this scope's: never swapped for packed storage
     int rc = sample_impl(&src, dist_type, sigma, seed, src.cols, 0, true);
     if (rc == 0) rc = decompose_impl(&src, base_bits, out, small != 0);
+    return rc;
+    ABI_GUARD_END
+}
+
+// ---- row windows of a decomposition ----------------------------------------------------------------------------------
+// Every production caller of the decomposed hash samples asks for a window: a column chunk of the conceptual d x m_g
+// matrix (src/lookup/ggh15/pubkey_gpu.rs:398-407,495-504, poly_encoding_gpu.rs:453-462,520-543), of which
+// poly_encoding_gpu.rs:515,566 keep only rows [inner_start, inner_start + inner_len).  The digit transforms are the cost
+// of a decomposition, so both entries run them for the window's rows only, and touch (inverse-transform / sample) only
+// the source rows - for uniform samples, only the towers - those rows are digits of.
+static size_t window_digit_count(const GpuMatrix *out, uint32_t base_bits, int small) {
+    const uint32_t dpt = (out->ctx->crt_bits + base_bits - 1) / base_bits;
+    return small ? dpt : static_cast<size_t>(dpt) * matrix_limbs(out);
+}
+
+extern "C" int gpupoly_matrix_decompose_rows(const GpuMatrix *src, uint32_t base_bits, int small, size_t row_start,
+                                             GpuMatrix *out) {
+    ABI_GUARD_BEGIN
+    if (!src || !out) return set_error("gpupoly_matrix_decompose_rows: null matrix");
+    if (base_bits == 0 || base_bits >= 63) return set_error("gpupoly_matrix_decompose_rows: base_bits must be in 1..62");
+    if (src->ctx != out->ctx) return set_error("gpupoly_matrix_decompose_rows: context mismatch");
+    if (src->level != out->level) return set_error("gpupoly_matrix_decompose_rows: level mismatch");
+    if (src->cols != out->cols) return set_error("gpupoly_matrix_decompose_rows: column count mismatch");
+    const size_t k = window_digit_count(out, base_bits, small);
+    const size_t total = src->rows * k;
+    if (row_start > total || out->rows > total - row_start)
+        return set_error("gpupoly_matrix_decompose_rows: row window past the decomposition's rows");
+    if (storage_overlaps(src, out)) return set_error("gpupoly_matrix_decompose_rows: output must not overlap the source");
+    return decompose_core(src, base_bits, small != 0, row_start, out);
+    ABI_GUARD_END
+}
+
+extern "C" int gpupoly_matrix_sample_decomposed_window(GpuMatrix *out, int dist_type, double sigma, GpuRngSeed seed,
+                                                       uint32_t base_bits, int small, size_t src_rows, size_t full_ncol,
+                                                       size_t col_offset, size_t row_start) {
+    ABI_GUARD_BEGIN
+    if (!out) return set_error("gpupoly_matrix_sample_decomposed_window: null matrix");
+    if (base_bits == 0 || base_bits >= 63) return set_error("gpupoly_matrix_sample_decomposed_window: base_bits must be in 1..62");
+    if (dist_type < GPU_MATRIX_DIST_UNIFORM || dist_type > GPU_MATRIX_DIST_TERNARY)
+        return set_error("gpupoly_matrix_sample_decomposed_window: invalid dist_type");
+    if (dist_type == GPU_MATRIX_DIST_GAUSS && !(sigma > 0.0))
+        return set_error("gpupoly_matrix_sample_decomposed_window: sigma must be positive for Gaussian sampling");
+    if (col_offset > full_ncol || out->cols > full_ncol - col_offset)
+        return set_error("gpupoly_matrix_sample_decomposed_window: column window past full_ncol");
+    GpuContext *ctx = out->ctx;
+    const size_t L = matrix_limbs(out);
+    const uint32_t dpt = (ctx->crt_bits + base_bits - 1) / base_bits;
+    const size_t k = window_digit_count(out, base_bits, small);
+    if (src_rows > ~size_t(0) / k || row_start > src_rows * k || out->rows > src_rows * k - row_start)
+        return set_error("gpupoly_matrix_sample_decomposed_window: row window past the decomposition's rows");
+    // the stream ids of the whole conceptual matrix (sample_impl's rule)
+    if (full_ncol && src_rows > ((size_t(1) << 48) - 2) / full_ncol)
+        return set_error("gpupoly_matrix_sample_decomposed_window: matrix too large for the RNG's 48-bit stream ids");
+    const size_t R = out->rows;
+    if (R == 0 || out->cols == 0) {
+        out->format = GPU_POLY_FORMAT_EVAL;
+        return 0;
+    }
+    const size_t r0 = row_start / k, r1 = (row_start + R - 1) / k;
+    if (dist_type == GPU_MATRIX_DIST_GAUSS && ((r1 - r0 + 1) * out->cols) >> 32)
+        return set_error("gpupoly_matrix_sample_decomposed_window: too many polynomials");
+    GpuMatrix src;
+    src.ctx = ctx;
+    src.level = out->level;
+    src.rows = r1 - r0 + 1;
+    src.cols = out->cols;
+    src.bytes = src.rows * src.cols * L * static_cast<size_t>(ctx->N) * static_cast<size_t>(ctx->word_bytes);
+    if (ctx_activate(ctx)) return 1;
+    CtxBlock block(ctx);
+    if (block.alloc(src.bytes)) return 1;
+    src.storage = block.ptr;
+    src.borrowed = true;  // the block is this scope's: never swapped for packed storage
+    // the towers whose digits the window holds: a contiguous run when it lies inside one source row
+    uint32_t t0 = 0, tn = small ? 1u : static_cast<uint32_t>(L);
+    if (r0 == r1) {
+        t0 = static_cast<uint32_t>((row_start - r0 * k) / dpt);
+        tn = static_cast<uint32_t>((row_start + R - 1 - r0 * k) / dpt) - t0 + 1;
+    }
+    int rc = sample_impl(&src, dist_type, sigma, seed, full_ncol, col_offset, true, r0, t0, tn);
+    if (rc == 0) rc = decompose_core(&src, base_bits, small != 0, row_start - r0 * k, out);
     return rc;
     ABI_GUARD_END
 }

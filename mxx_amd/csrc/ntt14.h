@@ -300,21 +300,23 @@ struct LoadDigit {
 };
 
 // grid = (8 * L * ceil(src_cols / 8), k, source rows): blockIdx.x = (col % 8) + 8 * (limb + L * (col / 8)),
-// blockIdx.y = t * dpt + d, blockIdx.z = r.  The L * dpt transforms that read one source vector (entry, tower t) then
+// blockIdx.y + td0 = t * dpt + d, blockIdx.z = r.  A launch writes the k digit rows [td0, td0 + k) of each of its source
+// rows, k consecutive output rows per source row; the whole decomposition is td0 = 0 with k = all of them, a row window
+// (gpupoly_matrix_decompose_rows) is at most three such launches: one workgroup set per window row, no division added.  The L * dpt transforms that read one source vector (entry, tower t) then
 // have the same block id modulo 8, i.e. run on one XCD and share its L2 (hardware places consecutive workgroup ids
 // on consecutive XCDs; with limb fastest in x the eight limbs of a source landed on eight different L2s).
 template <typename W, bool REDUCE, bool TIGHT = false, bool NTS = false>
 __global__ void __launch_bounds__(512, 8 / (sizeof(W) / 4))
     fwd_digits_kernel(W *__restrict__ out, const W *__restrict__ coeff, const TwPair<W> *__restrict__ tw_all,
                       const LimbConst *__restrict__ limbs, uint32_t L, uint32_t src_cols, uint32_t towers, uint32_t dpt,
-                      uint32_t base_bits, uint32_t k) {
+                      uint32_t base_bits, uint32_t k, uint32_t td0) {
     const uint32_t rest = blockIdx.x >> 3, col_hi = rest / L, limb = rest - col_hi * L;
     const uint32_t col = col_hi * 8u + (blockIdx.x & 7u);
     if (col >= src_cols) return;  // padding of the last group of 8 columns (whole workgroup)
-    const uint32_t td = blockIdx.y;
+    const uint32_t td = blockIdx.y + td0;
     const size_t r = blockIdx.z;
     const uint32_t t = td / dpt, d = td - t * dpt;
-    const size_t vec = ((r * k + td) * src_cols + col) * L + limb;
+    const size_t vec = ((r * k + blockIdx.y) * src_cols + col) * L + limb;
     const LimbConst lc = limbs[limb];
     const uint32_t src_bits = limbs[t].kbits, shift = d * base_bits;
     LoadDigit<W, REDUCE> load;

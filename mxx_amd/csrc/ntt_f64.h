@@ -255,7 +255,7 @@ template <int PRE, int ELIM, bool DIGITS, bool REDUCE, bool NTS>
 __global__ void __launch_bounds__(256)
     head_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ coeff, const TwF *__restrict__ tw_all,
                 const F64Limb *__restrict__ flimbs, const LimbConst *__restrict__ limbs, uint32_t L, uint32_t logN, uint32_t src_cols,
-                uint32_t dpt, uint32_t base_bits, uint32_t k) {
+                uint32_t dpt, uint32_t base_bits, uint32_t k, uint32_t td0) {
     constexpr int R = 1 << PRE;
     const uint32_t S = (1u << logN) >> PRE;
     const uint32_t sets_blocks = S / blockDim.x;
@@ -268,7 +268,7 @@ __global__ void __launch_bounds__(256)
         const uint32_t sb = blockIdx.x % sets_blocks, rest = blockIdx.x / sets_blocks;
         limb = rest % L;
         const uint32_t col = rest / L;
-        const uint32_t td = blockIdx.y, t = td / dpt, d = td - t * dpt;
+        const uint32_t td = blockIdx.y + td0, t = td / dpt, d = td - t * dpt;
         const size_t r = blockIdx.z;
         j = sb * blockDim.x + threadIdx.x;
         const uint32_t src_bits = limbs[t].kbits, shift = d * base_bits;
@@ -281,7 +281,7 @@ __global__ void __launch_bounds__(256)
         sh = shift < 64 ? shift : 0;
         qred = limbs[limb].q;
         src = coeff + (((r * src_cols + col) * L + t) << logN) + j;
-        g = out + (((((r * k + td) * src_cols + col) * L) + limb) << logN) + j;
+        g = out + (((((r * k + blockIdx.y) * src_cols + col) * L) + limb) << logN) + j;
     } else {
         const size_t vec = blockIdx.x / sets_blocks;
         j = (blockIdx.x - static_cast<uint32_t>(vec) * sets_blocks) * blockDim.x + threadIdx.x;
@@ -306,18 +306,18 @@ __global__ void __launch_bounds__(256)
     for (int u = 0; u < R; ++u) nt_store<NTS, uint64_t>(f64_raw(fold(v[u], lc.q, lc.qinv)), g + static_cast<size_t>(S) * u);
 }
 
-// decompose + forward transform (decompose.hip): grid = (L * src_cols, k, source rows), as ntt_fwd_lazy_digits_kernel
+// decompose + forward transform (decompose.hip): grid = (L * src_cols, k, source rows) and td0 as ntt_fwd_lazy_digits_kernel
 template <int LOGN, int LOGR, int WAVES_PER_EU, int ELIM, bool REDUCE, bool NTS>
 __global__ void __launch_bounds__(1 << (LOGN - LOGR), WAVES_PER_EU)
     fwd_digits_kernel(uint64_t *__restrict__ out, const uint64_t *__restrict__ coeff, const TwF *__restrict__ tw_all,
                       const F64Limb *__restrict__ flimbs, const LimbConst *__restrict__ limbs, uint32_t L, uint32_t src_cols,
-                      uint32_t dpt, uint32_t base_bits, uint32_t k) {
+                      uint32_t dpt, uint32_t base_bits, uint32_t k, uint32_t td0) {
     const uint32_t limb = blockIdx.x % L, col = blockIdx.x / L;
-    const uint32_t td = blockIdx.y, t = td / dpt, d = td - t * dpt;
+    const uint32_t td = blockIdx.y + td0, t = td / dpt, d = td - t * dpt;
     const size_t r = blockIdx.z;
     const F64Limb lc = flimbs[limb];
     const uint64_t *src = coeff + (((r * src_cols + col) * L + t) << LOGN);
-    uint64_t *g = out + (((((r * k + td) * src_cols + col) * L) + limb) << LOGN);
+    uint64_t *g = out + (((((r * k + blockIdx.y) * src_cols + col) * L) + limb) << LOGN);
     fwd_body<LOGN, LOGR, 0, ELIM, NTS>(g, load_digit_of<uint64_t, REDUCE>(src, limbs, t, d, base_bits, limbs[limb].q),
                                        tw_all + (static_cast<size_t>(limb) << LOGN), lc, 0u);
 }

@@ -416,19 +416,20 @@ __device__ __forceinline__ LoadDigitOf<W, REDUCE> load_digit_of(const W *src, co
 // decompose + forward transform for the rings whose vector fits LDS (the 2^14 grouped kernel and the head kernel of the
 // larger rings have their own forms): output vector (orow, col, limb), orow = r k + t dpt + d, is the transform of digit d
 // of the tower-t coefficient residues of source entry (r, col).  One pass over the k-times larger digit matrix (written with
-// non-temporal stores, NTS, when it is at least 1 GiB) instead of three.  grid = (L * src_cols, k, source rows)
+// non-temporal stores, NTS, when it is at least 1 GiB) instead of three.  grid = (L * src_cols, k, source rows); the launch
+// writes digit rows [td0, td0 + k) of each source row, k output rows per source row (ntt14::fwd_digits_kernel)
 template <typename W, int LOGN, int LOGR, int WAVES_PER_EU, bool TIGHT, bool REDUCE, bool NTS>
 __global__ void __launch_bounds__(1 << (LOGN - LOGR), WAVES_PER_EU)
     ntt_fwd_lazy_digits_kernel(W *__restrict__ out, const W *__restrict__ coeff, const TwPair<W> *__restrict__ tw_all,
                                const LimbConst *__restrict__ limbs, uint32_t L, uint32_t src_cols, uint32_t dpt,
-                               uint32_t base_bits, uint32_t k) {
+                               uint32_t base_bits, uint32_t k, uint32_t td0) {
     const uint32_t limb = blockIdx.x % L, col = blockIdx.x / L;
-    const uint32_t td = blockIdx.y, t = td / dpt, d = td - t * dpt;
+    const uint32_t td = blockIdx.y + td0, t = td / dpt, d = td - t * dpt;
     const size_t r = blockIdx.z;
     const LimbConst lc = limbs[limb];
     const TwPair<W> *tw = tw_all + (static_cast<size_t>(limb) << LOGN);
     const W *src = coeff + (((r * src_cols + col) * L + t) << LOGN);
-    W *g = out + (((((r * k + td) * src_cols + col) * L) + limb) << LOGN);
+    W *g = out + (((((r * k + blockIdx.y) * src_cols + col) * L) + limb) << LOGN);
     ntt_fwd_lazy_body<W, LOGN, LOGR, 0, TIGHT, NTS>(g, load_digit_of<W, REDUCE>(src, limbs, t, d, base_bits, static_cast<W>(lc.q)), tw,
                                                      lc, 0u);
 }
@@ -561,18 +562,18 @@ __global__ void __launch_bounds__(256)
 // r k + t dpt + d, starts from digit d of the tower-t coefficient residues of source entry (r, col) instead of from its
 // own contents.  Two-step decomposition at these sizes costs five passes over the k-times larger digit matrix (digits
 // written, head read + write, sub-vectors read + write); this way three.
-// grid = (sets_blocks * L * src_cols, k, source rows)
+// grid = (sets_blocks * L * src_cols, k, source rows); td0 as in ntt_fwd_lazy_digits_kernel
 template <typename W, int PRE, bool REDUCE, bool NTS>
 __global__ void __launch_bounds__(256)
     ntt_fwd_head_digits_kernel(W *__restrict__ out, const W *__restrict__ coeff, const TwPair<W> *__restrict__ tw_all,
                                const LimbConst *__restrict__ limbs, uint32_t L, uint32_t logN, uint32_t src_cols, uint32_t dpt,
-                               uint32_t base_bits, uint32_t k) {
+                               uint32_t base_bits, uint32_t k, uint32_t td0) {
     constexpr int R = 1 << PRE;
     const uint32_t S = (1u << logN) >> PRE;
     const uint32_t sets_blocks = S / blockDim.x;
     const uint32_t sb = blockIdx.x % sets_blocks, rest = blockIdx.x / sets_blocks;
     const uint32_t limb = rest % L, col = rest / L;
-    const uint32_t td = blockIdx.y, t = td / dpt, d = td - t * dpt;
+    const uint32_t td = blockIdx.y + td0, t = td / dpt, d = td - t * dpt;
     const size_t r = blockIdx.z;
     const uint32_t j = sb * blockDim.x + threadIdx.x;
     const LimbConst lc = limbs[limb];
@@ -587,7 +588,7 @@ __global__ void __launch_bounds__(256)
     }
     const uint32_t sh = shift < 8 * sizeof(W) ? shift : 0;
     const W *src = coeff + (((r * src_cols + col) * L + t) << logN) + j;
-    W *g = out + (((((r * k + td) * src_cols + col) * L) + limb) << logN) + j;
+    W *g = out + (((((r * k + blockIdx.y) * src_cols + col) * L) + limb) << logN) + j;
     W v[R];
 #pragma unroll
     for (int u = 0; u < R; ++u) {

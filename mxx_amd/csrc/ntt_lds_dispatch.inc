@@ -135,7 +135,7 @@ static int launch_split(GpuContext *ctx, W *data, size_t vectors, uint32_t L, bo
 // decompose + forward transform at the split sizes: head kernel with the digits in its load, then the sub-vectors
 template <int SUBLOG, int LOGR, int WPE, int PRE, bool TIGHT>
 static int launch_split_digits(GpuContext *ctx, W *out, const W *coeff, uint32_t L, uint32_t src_cols, size_t src_rows,
-                               uint32_t dpt, uint32_t base_bits, size_t k, bool reduce) {
+                               uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0, bool reduce) {
     const size_t lds = lds_padded_words(size_t(1) << SUBLOG) * sizeof(W);
     const size_t vectors = src_rows * k * src_cols * L;
     if (lds > kLdsLimitBytes || vectors > (0x7fffffffull >> PRE)) return -1;
@@ -155,7 +155,7 @@ static int launch_split_digits(GpuContext *ctx, W *out, const W *coeff, uint32_t
 #define MXX_HEAD(RED, NTSF)                                                                                                   \
     MXX_LAUNCH((ntt_fwd_head_digits_kernel<W, PRE, RED, NTSF>), set_grid, dim3(256), 0, ctx->stream, out, coeff,         \
                        static_cast<const TwPair<W> *>(ctx->d_tw2_fwd), ctx->d_limbs, L, logN, src_cols, dpt, base_bits,          \
-                       static_cast<uint32_t>(k))
+                       static_cast<uint32_t>(k), td0)
     if (reduce) {
         if (nts) MXX_HEAD(true, true);
         else MXX_HEAD(true, false);
@@ -173,7 +173,7 @@ static int launch_split_digits(GpuContext *ctx, W *out, const W *coeff, uint32_t
 // decompose + forward transform with the whole vector in LDS (ntt_fwd_lazy_digits_kernel)
 template <int LOGN, int LOGR, int WPE, bool TIGHT>
 static int launch_lazy_digits(GpuContext *ctx, W *out, const W *coeff, uint32_t L, uint32_t src_cols, size_t src_rows,
-                              uint32_t dpt, uint32_t base_bits, size_t k, bool reduce) {
+                              uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0, bool reduce) {
     const size_t lds = lds_padded_words(size_t(1) << LOGN) * sizeof(W);
     if (lds > kLdsLimitBytes) return -1;
     const size_t vectors = src_rows * k * src_cols * L;
@@ -194,7 +194,7 @@ static int launch_lazy_digits(GpuContext *ctx, W *out, const W *coeff, uint32_t 
     const TwPair<W> *tw = static_cast<const TwPair<W> *>(ctx->d_tw2_fwd);
 #define MXX_LZD(RED, NTSF)                                                                                                      \
     MXX_LAUNCH((ntt_fwd_lazy_digits_kernel<W, LOGN, LOGR, WPE, TIGHT, RED, NTSF>), grid, block, lds, ctx->stream, out,     \
-                       coeff, tw, ctx->d_limbs, L, src_cols, dpt, base_bits, static_cast<uint32_t>(k))
+                       coeff, tw, ctx->d_limbs, L, src_cols, dpt, base_bits, static_cast<uint32_t>(k), td0)
     if (reduce) {
         if (nts) MXX_LZD(true, true);
         else MXX_LZD(true, false);
@@ -210,8 +210,8 @@ static int launch_lazy_digits(GpuContext *ctx, W *out, const W *coeff, uint32_t 
 // every ring with a tuned transform except the 32-bit 2^14 grouped kernel (ntt_lds_u32.hip); -1: none for this ring
 template <bool TIGHT>
 static int dispatch_ntt_digits_impl(GpuContext *ctx, W *out, const W *coeff, uint32_t L, uint32_t src_cols, size_t src_rows,
-                                    uint32_t dpt, uint32_t base_bits, size_t k, bool reduce) {
-#define MXX_ARGS ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, reduce
+                                    uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0, bool reduce) {
+#define MXX_ARGS ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, td0, reduce
     if constexpr (sizeof(W) == 8) {
         switch (ctx->logN) {
             case 14: return launch_lazy_digits<14, 5, 2, false>(MXX_ARGS);
@@ -239,14 +239,14 @@ static int dispatch_ntt_digits_impl(GpuContext *ctx, W *out, const W *coeff, uin
 }
 
 static int dispatch_ntt_digits(GpuContext *ctx, W *out, const W *coeff, uint32_t L, uint32_t src_cols, size_t src_rows,
-                               uint32_t dpt, uint32_t base_bits, size_t k, bool reduce) {
+                               uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0, bool reduce) {
     if constexpr (sizeof(W) == 4) {
         if (!ctx->lazy_ok)
-            return ctx->tight_ok ? dispatch_ntt_digits_impl<true>(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, reduce) : -1;
+            return ctx->tight_ok ? dispatch_ntt_digits_impl<true>(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, td0, reduce) : -1;
     } else {
         if (!ctx->lazy_ok) return -1;
     }
-    return dispatch_ntt_digits_impl<false>(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, reduce);
+    return dispatch_ntt_digits_impl<false>(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, td0, reduce);
 }
 
 template <bool TIGHT>

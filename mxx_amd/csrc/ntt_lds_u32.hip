@@ -63,9 +63,12 @@ int launch_ntt_add_u32(GpuContext *ctx, uint32_t *out, const uint32_t *src, cons
 }
 
 // decompose + forward NTT in one pass (ntt14.h, fwd_digits_kernel); -1: not available for this
-// context / path override, the caller then runs the digit kernel and the transform separately
+// context / path override, the caller then runs the digit kernel and the transform separately.
+// The launch writes digit rows [td0, td0 + k) of each of its out_vectors / (k src_cols L) source rows, k consecutive
+// output rows per source row: the whole decomposition is td0 = 0 and k = its digit count, a row window is a few such
+// launches (decompose.hip, decompose_window)
 int launch_ntt_digits_u32(GpuContext *ctx, uint32_t *out, const uint32_t *coeff, size_t out_vectors, uint32_t L,
-                          uint32_t src_cols, uint32_t towers, uint32_t dpt, uint32_t base_bits, size_t k) {
+                          uint32_t src_cols, uint32_t towers, uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0) {
     const EnvSwitches &env = ctx->env;
     const bool tight = !ctx->lazy_ok;
     if (!(ctx->lazy_ok || ctx->tight_ok) || env.ntt14 == 1 || env.ntt_path > 1 || !env.decompose_fused ||
@@ -82,7 +85,7 @@ int launch_ntt_digits_u32(GpuContext *ctx, uint32_t *out, const uint32_t *coeff,
     (void)towers;
     // SURVEY 8d decompose: (r c + r k c) n L w - the source read once, the digit matrix written once
     MXX_TRACE_BYTES((static_cast<double>(src_rows) * src_cols * L + static_cast<double>(out_vectors)) * ctx->N * sizeof(W));
-    if (ctx->logN != 14) return dispatch_ntt_digits(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, reduce);
+    if (ctx->logN != 14) return dispatch_ntt_digits(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, td0, reduce);
     const dim3 grid(8u * L * ((src_cols + 7u) / 8u), static_cast<unsigned>(k), static_cast<unsigned>(src_rows));
     const dim3 block(ntt14::T);
     const size_t lds = ntt14::lds_bytes(sizeof(W));
@@ -93,10 +96,10 @@ int launch_ntt_digits_u32(GpuContext *ctx, uint32_t *out, const uint32_t *coeff,
     do {                                                                                                                         \
         if (nts)                                                                                                                 \
             MXX_LAUNCH((ntt14::fwd_digits_kernel<W, RED, TGT, true>), grid, block, lds, ctx->stream, out, coeff, tw,      \
-                               ctx->d_limbs, L, src_cols, towers, dpt, base_bits, k32);                                           \
+                               ctx->d_limbs, L, src_cols, towers, dpt, base_bits, k32, td0);                                           \
         else                                                                                                                     \
             MXX_LAUNCH((ntt14::fwd_digits_kernel<W, RED, TGT, false>), grid, block, lds, ctx->stream, out, coeff, tw,     \
-                               ctx->d_limbs, L, src_cols, towers, dpt, base_bits, k32);                                           \
+                               ctx->d_limbs, L, src_cols, towers, dpt, base_bits, k32, td0);                                           \
     } while (0)
     if (reduce) {
         if (tight) MXX_DIGITS(true, true);

@@ -64,7 +64,7 @@ static int launch_f64_split(GpuContext *ctx, uint64_t *data, size_t vectors, uin
     if (!inverse) {
         const TwF *tw = static_cast<const TwF *>(ctx->d_twf_fwd);
         MXX_LAUNCH((nttf::head_kernel<PRE, ELIM, false, false, false>), set_grid, set_block, 0, ctx->stream, data, data, tw, fl, ctx->d_limbs,
-                   L, logN, 0u, 0u, 0u, 0u);
+                   L, logN, 0u, 0u, 0u, 0u, 0u);
         MXX_LAUNCH((nttf::fwd_kernel<SUBLOG, LOGR, WPE, ELIM, false, PRE>), sub_grid, sub_block, lds, ctx->stream, data, tw, fl, L);
     } else {
         const TwF *tw = static_cast<const TwF *>(ctx->d_twf_inv);
@@ -124,7 +124,7 @@ int launch_ntt_lds_u64(GpuContext *ctx, uint64_t *data, size_t vectors, uint32_t
 
 template <int LOGN, int LOGR, int WPE, int ELIM>
 static int launch_f64_digits(GpuContext *ctx, uint64_t *out, const uint64_t *coeff, uint32_t L, uint32_t src_cols, size_t src_rows,
-                             uint32_t dpt, uint32_t base_bits, size_t k, bool reduce) {
+                             uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0, bool reduce) {
     const size_t lds = lds_padded_words(size_t(1) << LOGN) * sizeof(double);
     const size_t vectors = src_rows * k * src_cols * L;
     const bool nts = (vectors << LOGN) * sizeof(uint64_t) >= (size_t(1) << 29);
@@ -145,7 +145,7 @@ static int launch_f64_digits(GpuContext *ctx, uint64_t *out, const uint64_t *coe
     const F64Limb *fl = static_cast<const F64Limb *>(ctx->d_flimbs);
 #define MXX_F64D(RED, NTSF)                                                                                                    \
     MXX_LAUNCH((nttf::fwd_digits_kernel<LOGN, LOGR, WPE, ELIM, RED, NTSF>), grid, block, lds, ctx->stream, out, coeff, tw, fl,  \
-               ctx->d_limbs, L, src_cols, dpt, base_bits, static_cast<uint32_t>(k))
+               ctx->d_limbs, L, src_cols, dpt, base_bits, static_cast<uint32_t>(k), td0)
     if (reduce) {
         if (nts) MXX_F64D(true, true);
         else MXX_F64D(true, false);
@@ -161,7 +161,7 @@ static int launch_f64_digits(GpuContext *ctx, uint64_t *out, const uint64_t *coe
 // decompose + forward transform at the split sizes: head kernel with the digits in its load, then the sub-vectors
 template <int SUBLOG, int LOGR, int WPE, int PRE, int ELIM>
 static int launch_f64_split_digits(GpuContext *ctx, uint64_t *out, const uint64_t *coeff, uint32_t L, uint32_t src_cols, size_t src_rows,
-                                   uint32_t dpt, uint32_t base_bits, size_t k, bool reduce) {
+                                   uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0, bool reduce) {
     const size_t lds = lds_padded_words(size_t(1) << SUBLOG) * sizeof(double);
     const size_t vectors = src_rows * k * src_cols * L;
     if (vectors > (0x7fffffffull >> PRE)) return -1;
@@ -182,7 +182,7 @@ static int launch_f64_split_digits(GpuContext *ctx, uint64_t *out, const uint64_
     const F64Limb *fl = static_cast<const F64Limb *>(ctx->d_flimbs);
 #define MXX_F64H(RED, NTSF)                                                                                                     \
     MXX_LAUNCH((nttf::head_kernel<PRE, ELIM, true, RED, NTSF>), set_grid, dim3(256), 0, ctx->stream, out, coeff, tw, fl, ctx->d_limbs, \
-               L, logN, src_cols, dpt, base_bits, static_cast<uint32_t>(k))
+               L, logN, src_cols, dpt, base_bits, static_cast<uint32_t>(k), td0)
     if (reduce) {
         if (nts) MXX_F64H(true, true);
         else MXX_F64H(true, false);
@@ -198,8 +198,8 @@ static int launch_f64_split_digits(GpuContext *ctx, uint64_t *out, const uint64_
 
 template <int ELIM>
 static int dispatch_f64_digits(GpuContext *ctx, uint64_t *out, const uint64_t *coeff, uint32_t L, uint32_t src_cols, size_t src_rows,
-                               uint32_t dpt, uint32_t base_bits, size_t k, bool reduce) {
-#define MXX_ARGS ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, reduce
+                               uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0, bool reduce) {
+#define MXX_ARGS ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, td0, reduce
     switch (ctx->logN) {
         case 15: return launch_f64_split_digits<11, 4, 1, 4, ELIM>(MXX_ARGS);
         case 16: return launch_f64_split_digits<12, 4, 1, 4, ELIM>(MXX_ARGS);
@@ -216,7 +216,7 @@ static int dispatch_f64_digits(GpuContext *ctx, uint64_t *out, const uint64_t *c
 
 // decompose + forward transform in one pass for 64-bit words (see launch_ntt_digits_u32); -1: not available
 int launch_ntt_digits_u64(GpuContext *ctx, uint64_t *out, const uint64_t *coeff, size_t out_vectors, uint32_t L,
-                          uint32_t src_cols, uint32_t towers, uint32_t dpt, uint32_t base_bits, size_t k) {
+                          uint32_t src_cols, uint32_t towers, uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0) {
     const EnvSwitches &env = ctx->env;
     if (!ctx->lazy_ok || env.ntt_path > 1 || !env.decompose_fused || out_vectors > 0x7fffffffull || k >> 32) return -1;
     if (k == 0 || src_cols == 0 || out_vectors % (k * src_cols * L) != 0) return -1;
@@ -228,10 +228,10 @@ int launch_ntt_digits_u64(GpuContext *ctx, uint64_t *out, const uint64_t *coeff,
     const bool reduce = digit_bits >= 63 || ((1ull << digit_bits) - 1) >= min_q;
     (void)towers;
     if (f64_path(ctx)) {
-        const int rc = ctx->crt_bits <= 40   ? dispatch_f64_digits<4095>(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, reduce)
-                       : ctx->crt_bits <= 49 ? dispatch_f64_digits<63>(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, reduce)
-                                             : dispatch_f64_digits<15>(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, reduce);
+        const int rc = ctx->crt_bits <= 40   ? dispatch_f64_digits<4095>(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, td0, reduce)
+                       : ctx->crt_bits <= 49 ? dispatch_f64_digits<63>(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, td0, reduce)
+                                             : dispatch_f64_digits<15>(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, td0, reduce);
         if (rc >= 0) return rc;
     }
-    return dispatch_ntt_digits(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, reduce);
+    return dispatch_ntt_digits(ctx, out, coeff, L, src_cols, src_rows, dpt, base_bits, k, td0, reduce);
 }

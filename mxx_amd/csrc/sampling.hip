@@ -77,13 +77,15 @@ template <typename W>
 __global__ void __launch_bounds__(256) sample_uniform_kernel(W *__restrict__ out, const LimbConst *__restrict__ limbs,
                                                              const ChaChaKey *__restrict__ keys, size_t polys, size_t local_ncol,
                                                              size_t full_ncol, size_t col_offset, uint32_t L, uint32_t N,
-                                                             uint32_t groups /* ceil(N / 8) */) {
+                                                             uint32_t groups /* ceil(N / 8) */, uint32_t l0, uint32_t Ls) {
+    // limbs [l0, l0 + Ls) of every polynomial are written (all of them: l0 = 0, Ls = L); the others are left alone
     const size_t idx = item_index();
-    if (idx >= polys * L * groups) return;
-    const size_t vec = idx / groups;  // (polynomial, limb) vector
-    const uint32_t g = static_cast<uint32_t>(idx - vec * groups);
-    const size_t p = vec / L;
-    const uint32_t l = static_cast<uint32_t>(vec - p * L);
+    if (idx >= polys * Ls * groups) return;
+    const size_t sv = idx / groups;  // (polynomial, sampled limb)
+    const uint32_t g = static_cast<uint32_t>(idx - sv * groups);
+    const size_t p = sv / Ls;
+    const uint32_t l = l0 + static_cast<uint32_t>(sv - p * Ls);
+    const size_t vec = p * L + l;  // (polynomial, limb) vector
     const size_t row = p / local_ncol, lcol = p - row * local_ncol;
     const uint64_t gpoly = row * full_ncol + col_offset + lcol;
     const ChaChaKey key = load_key(keys, l);
@@ -343,7 +345,8 @@ __device__ int64_t ref_karney(RefRng &r, double mean, double stddev) {
 template <typename W>
 __global__ void __launch_bounds__(128) sample_compat_kernel(W *__restrict__ out, const LimbConst *__restrict__ limbs, size_t polys,
                                                             size_t local_ncol, size_t full_ncol, size_t col_offset, uint32_t L,
-                                                            uint32_t logN, int dist, double sigma, GpuRngSeed seed) {
+                                                            uint32_t logN, int dist, double sigma, GpuRngSeed seed, uint32_t l0,
+                                                            uint32_t Ls /* uniform: limbs [l0, l0 + Ls) only */) {
     const size_t idx = item_index();
     if (idx >= (polys << logN)) return;
     const size_t p = idx >> logN;
@@ -352,7 +355,7 @@ __global__ void __launch_bounds__(128) sample_compat_kernel(W *__restrict__ out,
     const uint64_t gpoly = row * full_ncol + col_offset + lcol;
     RefRng r;
     if (dist == GPU_MATRIX_DIST_UNIFORM) {
-        for (uint32_t l = 0; l < L; ++l) {
+        for (uint32_t l = l0; l < l0 + Ls; ++l) {
             const uint64_t q = limbs[l].q, threshold = ~0ull - (~0ull % q);
             ref_rng_init(r, seed, gpoly + 1, static_cast<uint64_t>(i) + 1, static_cast<uint64_t>(l) + 1, kTagUniform);
             uint64_t x;
@@ -377,8 +380,13 @@ __global__ void __launch_bounds__(128) sample_compat_kernel(W *__restrict__ out,
         out[((p * L + l) << logN) + i] = signed_to_residue_mu<W>(z, limbs[l].q, limbs[l].mu64);
 }
 
-// keep_coeff: leave the samples as coefficients (for a caller that decomposes them next) instead of finishing in EVAL
-int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t full_ncol, size_t col_offset, bool keep_coeff) {
+// keep_coeff: leave the samples as coefficients (for a caller that decomposes them next) instead of finishing in EVAL.
+// row_offset: `out` is rows [row_offset, row_offset + out->rows) of the conceptual matrix - every kernel forms the global
+// polynomial index as row * full_ncol + col_offset + column, so the offset rides in col_offset.  tower_count > 0 (with
+// keep_coeff, uniform only): limbs [tower_first, tower_first + tower_count) alone are sampled, the rest of `out` is not
+// written (gpupoly_matrix_sample_decomposed_window reads only the towers its window touches).
+int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t full_ncol, size_t col_offset, bool keep_coeff,
+                size_t row_offset, uint32_t tower_first, uint32_t tower_count) {
     if (!out) return set_error("gpu_matrix_sample_distribution: null matrix");
     if (dist < GPU_MATRIX_DIST_UNIFORM || dist > GPU_MATRIX_DIST_TERNARY)
         return set_error("gpu_matrix_sample_distribution: invalid dist_type");
@@ -387,9 +395,11 @@ int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t 
     if (col_offset + out->cols > full_ncol)
         return set_error("gpu_matrix_sample_distribution_columns: column window out of range");
     // stream ids (global polynomial index + 1) are 48 bits wide in the nonce layout of rng.h: refuse what would wrap
-    if (full_ncol && (out->rows > ((size_t(1) << 48) - 2) / full_ncol))
+    const size_t row_limit = full_ncol ? ((size_t(1) << 48) - 2) / full_ncol : ~size_t(0);
+    if (row_offset > row_limit || out->rows > row_limit - row_offset)
         return set_error("gpu_matrix_sample_distribution: matrix too large for the RNG's 48-bit stream ids");
     GpuContext *ctx = out->ctx;
+    col_offset += row_offset * full_ncol;  // from here on only the kernels' index term
     out->format = keep_coeff ? GPU_POLY_FORMAT_COEFF : GPU_POLY_FORMAT_EVAL;
     const size_t polys = matrix_polys(out);
     if (polys == 0) return 0;
@@ -397,15 +407,17 @@ int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t 
     const size_t total = polys * static_cast<size_t>(ctx->N);
     const uint32_t L = static_cast<uint32_t>(matrix_limbs(out));
     const uint32_t N = static_cast<uint32_t>(ctx->N);
+    const bool subset = keep_coeff && dist == GPU_MATRIX_DIST_UNIFORM && tower_count > 0 && tower_first + tower_count <= L;
+    const uint32_t l0 = subset ? tower_first : 0u, Ls = subset ? tower_count : L;
     if (ctx->env.rng_compat) {
         const dim3 blocks = item_grid(total, 128);
-        MXX_TRACE_BYTES(static_cast<double>(out->bytes));
+        MXX_TRACE_BYTES(static_cast<double>(out->bytes) / L * (dist == GPU_MATRIX_DIST_UNIFORM ? Ls : L));
         if (ctx->wide)
             MXX_LAUNCH(sample_compat_kernel<uint64_t>, blocks, dim3(128), 0, ctx->stream, static_cast<uint64_t *>(words_ptr(out)), ctx->d_limbs,
-                       polys, out->cols, full_ncol, col_offset, L, ctx->logN, dist, sigma, seed);
+                       polys, out->cols, full_ncol, col_offset, L, ctx->logN, dist, sigma, seed, l0, Ls);
         else
             MXX_LAUNCH(sample_compat_kernel<uint32_t>, blocks, dim3(128), 0, ctx->stream, static_cast<uint32_t *>(words_ptr(out)), ctx->d_limbs,
-                       polys, out->cols, full_ncol, col_offset, L, ctx->logN, dist, sigma, seed);
+                       polys, out->cols, full_ncol, col_offset, L, ctx->logN, dist, sigma, seed, l0, Ls);
         HIP_TRY(hipGetLastError());
         if (keep_coeff) return 0;
         if (dist == GPU_MATRIX_DIST_UNIFORM && pack24_eligible(out)) return pack24_store(out, true);
@@ -455,15 +467,15 @@ int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t 
         const uint64_t tag = uniform ? kTagUniform : (dist == GPU_MATRIX_DIST_BIT ? kTagBit : kTagTernary);
         MXX_LAUNCH(derive_subkeys_kernel, dim3(1), dim3(64), 0, ctx->stream, d_keys, seed, tag, nkeys, uniform ? 1u : 0u);
         HIP_TRY(hipGetLastError());
-        const size_t threads = polys * (uniform ? L : 1u) * groups;
+        const size_t threads = polys * (uniform ? Ls : 1u) * groups;
         const dim3 blocks = item_grid(threads, 256);
 #define MXX_SAMPLE(KERNEL, WORD, ...)                                                                                     \
     MXX_LAUNCH(KERNEL<WORD>, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<WORD *>(words_ptr(out)), ctx->d_limbs, \
                        d_keys, polys, out->cols, full_ncol, col_offset, L, N, groups, ##__VA_ARGS__)
-        MXX_TRACE_BYTES(static_cast<double>(out->bytes));  // no input: the residues written once
+        MXX_TRACE_BYTES(static_cast<double>(out->bytes) / L * (uniform ? Ls : L));  // no input: the residues written once
         if (uniform) {
-            if (ctx->wide) MXX_SAMPLE(sample_uniform_kernel, uint64_t);
-            else MXX_SAMPLE(sample_uniform_kernel, uint32_t);
+            if (ctx->wide) MXX_SAMPLE(sample_uniform_kernel, uint64_t, l0, Ls);
+            else MXX_SAMPLE(sample_uniform_kernel, uint32_t, l0, Ls);
         } else {
             if (ctx->wide) MXX_SAMPLE(sample_small_kernel, uint64_t, dist);
             else MXX_SAMPLE(sample_small_kernel, uint32_t, dist);

@@ -1479,20 +1479,39 @@ class GpuDCRTPolyMatrix:
             out.is_ntt = True if kind in ("mul", "mul_scalar", "decompose", "mul_decompose") else (rhs if rhs is not None else lhs).is_ntt
         return outs
 
+    def _digit_count(self, small) -> int:
+        """digit rows per source row at this matrix's level: k of include/gpupoly.h"""
+        dpt = -(-self.params.crt_bits() // self.params.base_bits())
+        return dpt if small else dpt * (self.level + 1)
+
+    def decompose_rows(self, row_start, row_end, small=False, is_ntt=True) -> "GpuDCRTPolyMatrix":
+        """Rows [row_start, row_end) of `decompose()` (small: of `small_decompose()`) through
+        `gpupoly_matrix_decompose_rows`: the digit transforms run for those rows only, and of an EVAL source only the
+        source rows they are digits of are inverse-transformed.  The window may start and end anywhere."""
+        total = self.nrow * self._digit_count(small)
+        assert 0 <= row_start <= row_end <= total, f"decompose_rows window [{row_start}, {row_end}) out of range: {total} digit rows"
+        out = GpuDCRTPolyMatrix(self.params, row_end - row_start, self.ncol, self.level, is_ntt)
+        st = _ffi.lib().gpupoly_matrix_decompose_rows(self.raw, self.params.base_bits(), 1 if small else 0, row_start, out.raw)
+        check_status(st, "gpupoly_matrix_decompose_rows")
+        if row_end == row_start or self.ncol == 0:
+            out.is_ntt = True  # an empty result is tagged EVAL, as by gpu_matrix_decompose_base
+        return out
+
     # ---- PolyMatrix trait defaults the GPU wrapper inherits (src/matrix/mod.rs:185-345) ------------------------
+    # the defaults build all nrow * chunk_count digit rows and slice nrow of them; here only the kept rows are built
     def decompose_chunk(self, chunk_idx, chunk_count) -> "GpuDCRTPolyMatrix":
         assert chunk_count > 0, "decompose_chunk chunk_count must be > 0"
         assert chunk_idx < chunk_count, f"decompose_chunk chunk_idx out of range: chunk_idx={chunk_idx}, chunk_count={chunk_count}"
-        full = self.decompose()
-        assert full.nrow == self.nrow * chunk_count, f"decompose_chunk expected decomposed row count {self.nrow * chunk_count} but got {full.nrow}"
-        return full.slice(chunk_idx * self.nrow, (chunk_idx + 1) * self.nrow, 0, self.ncol)
+        rows = self.nrow * self._digit_count(False)
+        assert rows == self.nrow * chunk_count, f"decompose_chunk expected decomposed row count {self.nrow * chunk_count} but got {rows}"
+        return self.decompose_rows(chunk_idx * self.nrow, (chunk_idx + 1) * self.nrow, False)
 
     def small_decompose_chunk(self, chunk_idx, chunk_count) -> "GpuDCRTPolyMatrix":
         assert chunk_count > 0, "small_decompose_chunk chunk_count must be > 0"
         assert chunk_idx < chunk_count, f"small_decompose_chunk chunk_idx out of range: chunk_idx={chunk_idx}, chunk_count={chunk_count}"
-        full = self.small_decompose()
-        assert full.nrow == self.nrow * chunk_count, f"small_decompose_chunk expected decomposed row count {self.nrow * chunk_count} but got {full.nrow}"
-        return full.slice(chunk_idx * self.nrow, (chunk_idx + 1) * self.nrow, 0, self.ncol)
+        rows = self.nrow * self._digit_count(True)
+        assert rows == self.nrow * chunk_count, f"small_decompose_chunk expected decomposed row count {self.nrow * chunk_count} but got {rows}"
+        return self.decompose_rows(chunk_idx * self.nrow, (chunk_idx + 1) * self.nrow, True)
 
     @classmethod
     def small_decomposed_identity_chunk_from_scalar(cls, params, size, scalar, chunk_idx, chunk_count):
@@ -1783,6 +1802,29 @@ class GpuDCRTPolyMatrix:
             return out
         st = _ffi.lib().gpupoly_matrix_sample_decomposed(out.raw, dist, sigma, seed, params.base_bits(), 1 if small else 0)
         check_status(st, "gpupoly_matrix_sample_decomposed")
+        return out
+
+    @classmethod
+    def sample_distribution_decomposed_window(cls, params, nrow, total_ncol, col_start, col_len, dist: int, sigma: float,
+                                              seed: GpuRngSeed, small=False, row_start=0, row_end=None, is_ntt=True,
+                                              level=None):
+        """Rows [row_start, row_end) (all of them by default) of G^-1 (or the small G^-1) of
+        `sample_distribution_columns(params, nrow, total_ncol, col_start, col_len, ...)` (at `level`, the top one by default) through
+        `gpupoly_matrix_sample_decomposed_window`: only the source rows (uniform: and towers) the window touches are
+        sampled, the samples never leave the coefficient domain, and only the window's digit transforms run."""
+        assert col_start + col_len <= total_ncol, "sample_distribution_decomposed_window column range out of bounds"
+        level = params.crt_depth() - 1 if level is None else level
+        dpt = -(-params.crt_bits() // params.base_bits())
+        k = dpt if small else dpt * (level + 1)
+        if row_end is None:
+            row_end = nrow * k
+        assert 0 <= row_start <= row_end <= nrow * k, f"sample_distribution_decomposed_window rows [{row_start}, {row_end}) out of range: {nrow * k} digit rows"
+        out = cls(params, row_end - row_start, col_len, level, is_ntt)
+        st = _ffi.lib().gpupoly_matrix_sample_decomposed_window(out.raw, dist, sigma, seed, params.base_bits(), 1 if small else 0,
+                                                                nrow, total_ncol, col_start, row_start)
+        check_status(st, "gpupoly_matrix_sample_decomposed_window")
+        if row_end == row_start or col_len == 0:
+            out.is_ntt = True  # an empty result is tagged EVAL, as by gpu_matrix_decompose_base
         return out
 
     def gauss_samp_gq_arb_base(self, c: float, dgg_stddev: float, seed: GpuRngSeed, coeff_out: bool = False) -> "GpuDCRTPolyMatrix":

@@ -182,11 +182,18 @@ class GpuDCRTPolyHashSampler:
         seed = hash_seed_for_matrix(key, tag, self.hash_name)
         return GpuDCRTPolyMatrix.sample_distribution_decomposed(params, nrow, ncol, dist.as_ffi(), dist.sigma, seed, True)
 
+    def sample_hash_decomposed_columns(self, params, key, tag, nrow, total_ncol, col_start, col_len, dist,
+                                       row_start=0, row_end=None):
+        """== sample_hash_columns(...).decompose() (the trait default, src/sampler/mod.rs:84-97), in one extension call;
+        with row_start / row_end, its rows [row_start, row_end) - the `rhs_full.slice(inner_start, ..)` of
+        src/lookup/ggh15/poly_encoding_gpu.rs:515,566 - of which only those are computed."""
+        seed = hash_seed_for_matrix(key, tag, self.hash_name)
+        return GpuDCRTPolyMatrix.sample_distribution_decomposed_window(
+            params, nrow, total_ncol, col_start, col_len, dist.as_ffi(), dist.sigma, seed, False, row_start, row_end)
 
-    def sample_hash_decomposed_columns(self, params, key, tag, nrow, total_ncol, col_start, col_len, dist):
-        """trait default (src/sampler/mod.rs:84-97)"""
-        return self.sample_hash_columns(params, key, tag, nrow, total_ncol, col_start, col_len, dist).decompose_owned()
-
-    def sample_hash_small_decomposed_columns(self, params, key, tag, nrow, total_ncol, col_start, col_len, dist):
-        """trait default (src/sampler/mod.rs:111-124)"""
-        return self.sample_hash_columns(params, key, tag, nrow, total_ncol, col_start, col_len, dist).small_decompose_owned()
+    def sample_hash_small_decomposed_columns(self, params, key, tag, nrow, total_ncol, col_start, col_len, dist,
+                                             row_start=0, row_end=None):
+        """== sample_hash_columns(...).small_decompose() (the trait default, src/sampler/mod.rs:111-124), likewise"""
+        seed = hash_seed_for_matrix(key, tag, self.hash_name)
+        return GpuDCRTPolyMatrix.sample_distribution_decomposed_window(
+            params, nrow, total_ncol, col_start, col_len, dist.as_ffi(), dist.sigma, seed, True, row_start, row_end)
