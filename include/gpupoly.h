@@ -455,6 +455,38 @@ int gpupoly_matrix_load_coeff_words(GpuMatrix *mat, const uint64_t *words, size_
  * (tests/test_gpu_diamond_injector_q_bits_vs_max_error_plot_generates_svg.rs:145-163).  A null argument or a
  * words_per_value below what Q_level needs is refused with nothing launched and nothing written.                  */
 int gpupoly_matrix_centered_max_abs(const GpuMatrix *mat, uint64_t *out, size_t words_per_value);
+/* One bit per coefficient (extension): with c_k in [0, Q_level) coefficient k of entry (row, col), bit
+ * k % 8 of byte out[(row * cols + col) * bytes_per_poly + k / 8] is set iff c_k lies in the interval that the bounds
+ * `lo` and `hi` give - words_per_bound little-endian 64-bit words each, both in [0, Q_level] (Q_level itself allowed):
+ *   lo <= hi: [lo, hi);   lo > hi: the wrap-around set [lo, Q_level) u [0, hi)  (|x| <= B in the centred
+ *   representative is lo = Q_level - B, hi = B + 1);   lo == hi is the empty set, (0, Q_level) everything.
+ * `out` is host memory (synchronous); every byte of every slot is written, bits at or above N and bytes at or above
+ * ceil(N / 8) as zero.  COEFF or EVAL input (an EVAL input is inverse-transformed in scratch; `mat`'s residues and
+ * format are left as they were); 0 rows or 0 columns succeed with nothing launched.  One thread per coefficient: Garner's
+ * mixed-radix digits compared with the bounds' digits, top digit first - no big integer is built.  Replaces the host
+ * loops over coeffs() of extract_bits_with_threshold (src/poly/dcrt/gpu.rs:1070-1081; lo = (Q/2) >> 1, hi = 3 lo) and of
+ * the boolean centred decode (decode_centered_masked_boolean_coeff, src/decoder/masked_high_bit.rs:31-35;
+ * lo = ceil((Q + 1) / 4), hi = ceil((3 Q + 1) / 4)).
+ * Refused, with nothing launched and `out` untouched: a null argument, words_per_bound = 0, a bound above Q_level
+ * (non-zero words above Q_level's words included), bytes_per_poly < ceil(N / 8).                                    */
+int gpupoly_matrix_extract_bits(const GpuMatrix *mat, const uint64_t *lo, const uint64_t *hi, size_t words_per_bound,
+                                uint8_t *out, size_t bytes_per_poly);
+/* The first coeffs_per_poly (<= N) coefficients of every entry as machine integers (extension): elements
+ * of elem_bytes (4 or 8) bytes, b = 8 * elem_bytes bits, order [row][col][k], into host memory `out` (synchronous).
+ *   centred == 0: the element is c mod 2^b, c in [0, Q_level); it fits iff c < 2^b.
+ *   centred != 0: the element is x mod 2^b (two's complement), x the representative of c in (-Q_level/2, Q_level/2];
+ *                 it fits iff -2^(b-1) <= x <= 2^(b-1) - 1.
+ * A coefficient that does not fit is still written, truncated as stated, and the call still returns 0:
+ * *out_misfit_count is the number of such coefficients and *out_first_misfit the smallest linear index
+ * (row * cols + col) * coeffs_per_poly + k among them, UINT64_MAX when there are none.  COEFF or EVAL input (an EVAL
+ * input is inverse-transformed in scratch; `mat` is left as it was).  0 rows, 0 columns or coeffs_per_poly = 0 succeed
+ * with nothing launched, count 0 and first UINT64_MAX.  Replaces the host loops over coeffs() of to_bool_vec
+ * (src/poly/dcrt/gpu.rs:1083-1097) and coeffs_digits (src/poly/mod.rs:130-139), and the store + host CRT of
+ * const_coeff_u64 (gpu.rs:1103-1120; coeffs_per_poly = 1).
+ * Refused, with nothing launched and nothing written (both counters included): a null argument, elem_bytes other than
+ * 4 or 8, coeffs_per_poly > N.                                                                                        */
+int gpupoly_matrix_store_coeff_ints(const GpuMatrix *mat, void *out, int elem_bytes, int centred, size_t coeffs_per_poly,
+                                    uint64_t *out_misfit_count, uint64_t *out_first_misfit);
 /* The compact wire format for MANY matrices in one call (extension): what a loop over
  * gpu_matrix_store_compact_bytes / gpu_matrix_load_compact_bytes gives, with one width launch, one pack launch, one copy
  * of the widths, one copy of the payloads and two synchronises per CALL (up to 32 matrices of a level per launch)

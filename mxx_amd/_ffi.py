@@ -148,6 +148,8 @@ SIGNATURES = {
     "gpupoly_matrix_store_coeff_words": (C.c_int, [_vp, C.POINTER(C.c_uint64), _sz]),
     "gpupoly_matrix_load_coeff_words": (C.c_int, [_vp, C.POINTER(C.c_uint64), _sz, _sz, C.c_int]),
     "gpupoly_matrix_centered_max_abs": (C.c_int, [_vp, C.POINTER(C.c_uint64), _sz]),
+    "gpupoly_matrix_extract_bits": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _sz, _u8p, _sz]),
+    "gpupoly_matrix_store_coeff_ints": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gpupoly_matrix_fill_monomial": (C.c_int, [_vp, C.c_uint64, C.c_int]),
     "gpupoly_matrix_mul_monomial": (C.c_int, [_vp, _vp, C.c_uint64]),
     "gpupoly_matrix_monomial_sum": (C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), _sz, C.c_int]),

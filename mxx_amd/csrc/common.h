@@ -330,6 +330,10 @@ struct CtxBlock {
     }
 };
 int matrix_check_same_shape(const GpuMatrix *a, const GpuMatrix *b, const char *who);
+// *src <- the words of `mat` in the coefficient domain, `mat` (residues and tag) left as it is: its own words for a COEFF
+// matrix; for an EVAL matrix a copy in `scratch`, inverse-transformed on the context's stream (matrix.hip).  The read-out
+// entries use it (readout.hip); scale_round.hip and norm.hip still carry the same block inline
+int coeff_domain_source(const GpuMatrix *mat, CtxBlock &scratch, const void **src);
 
 // internal launchers shared across translation units
 int launch_ntt(GpuContext *ctx, void *data, size_t vectors, int limbs_per_poly, bool inverse);

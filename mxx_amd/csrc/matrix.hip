@@ -154,6 +154,20 @@ int launch_scatter_i64(GpuMatrix *out, const int64_t *vals) {
     return 0;
 }
 
+// common.h: the coefficient-domain words of a matrix for an entry that reads them and leaves the matrix as it is
+int coeff_domain_source(const GpuMatrix *mat, CtxBlock &scratch, const void **src) {
+    GpuContext *ctx = mat->ctx;
+    *src = words_ptr(mat);
+    if (mat->format != GPU_POLY_FORMAT_EVAL) return 0;
+    if (scratch.alloc(mat->bytes)) return 1;
+    MXX_TRACED_COPY("copy (device to device)", ctx->stream, 2.0 * mat->bytes,
+                    HIP_TRY(hipMemcpyAsync(scratch.ptr, words_ptr(mat), mat->bytes, hipMemcpyDeviceToDevice, ctx->stream)));
+    const int rc = launch_ntt(ctx, scratch.ptr, matrix_polys(mat) * matrix_limbs(mat), mat->level + 1, true);
+    if (rc) return rc;
+    *src = scratch.ptr;
+    return 0;
+}
+
 int launch_copy_block(GpuMatrix *out, const GpuMatrix *src, size_t dst_row, size_t dst_col, size_t src_row,
                       size_t src_col, size_t rows, size_t cols, bool add) {
     const char *who = add ? "gpu_matrix_add_block" : "gpu_matrix_copy_block";

@@ -608,6 +608,86 @@ class GpuDCRTPolyMatrix:
         entries = [[max((min(v, Q - v) for v in poly), default=0) for poly in row] for row in self.coeffs()]
         return _max_along(entries, axis, self.nrow, self.ncol)
 
+    # ------------------------------------------------------------------ bits and machine integers
+    def _level_modulus(self) -> int:
+        Q = 1
+        for q in self.params.moduli()[: self.level + 1]:
+            Q *= q
+        return Q
+
+    def extract_bits(self, lo: int, hi: int) -> np.ndarray:
+        """A bool array (rows, cols, n): coefficient c in [0, Q_level) -> whether it lies in [lo, hi), or for lo > hi in
+        the wrap-around set [lo, Q_level) u [0, hi) (|x| <= B in the centred representative: lo = Q_level - B,
+        hi = B + 1).  0 <= lo, hi <= Q_level.  One device call (gpupoly_matrix_extract_bits, the matrix left as it is):
+        no big integer is built on either side."""
+        n = self.params.ring_dimension()
+        Q = self._level_modulus()
+        if not (0 <= lo <= Q and 0 <= hi <= Q):
+            raise ValueError(f"extract_bits: bounds must lie in [0, Q_level] (got {lo}, {hi})")
+        if self.nrow == 0 or self.ncol == 0:
+            return np.zeros((self.nrow, self.ncol, n), dtype=bool)
+        wpb = -(-Q.bit_length() // 64)
+        bounds = np.array([[(b >> (64 * w)) & 0xFFFFFFFFFFFFFFFF for w in range(wpb)] for b in (lo, hi)], dtype=np.uint64)
+        bpp = -(-n // 8)
+        out = np.empty((self.nrow, self.ncol, bpp), dtype=np.uint8)
+        u64p = C.POINTER(C.c_uint64)
+        st = _ffi.lib().gpupoly_matrix_extract_bits(self.raw, bounds[0].ctypes.data_as(u64p), bounds[1].ctypes.data_as(u64p), wpb,
+                                                    out.ctypes.data_as(C.POINTER(C.c_uint8)), bpp)
+        check_status(st, "gpupoly_matrix_extract_bits")
+        return np.unpackbits(out, axis=-1, bitorder="little")[..., :n].astype(bool)
+
+    def extract_bits_with_threshold(self) -> np.ndarray:
+        """`extract_bits_with_threshold` (src/poly/dcrt/gpu.rs:1070-1081) of every entry: c in [quarter, 3 quarter),
+        quarter = (Q_level // 2) >> 1."""
+        quarter = (self._level_modulus() // 2) >> 1
+        return self.extract_bits(quarter, 3 * quarter)
+
+    def decode_bits(self) -> np.ndarray:
+        """The boolean centred decode (decode_centered_masked_boolean_coeff, src/decoder/masked_high_bit.rs:31-35):
+        floor((2 c + floor(Q/2)) / Q) mod 2 per coefficient, as a bool array (rows, cols, n).  For odd Q that is 1 exactly
+        when ceil((Q + 1) / 4) <= c < ceil((3 Q + 1) / 4): 2 c + floor(Q/2) reaches Q at the first and 2 Q at the second."""
+        Q = self._level_modulus()
+        return self.extract_bits(-(-(Q + 1) // 4), -(-(3 * Q + 1) // 4))
+
+    def coeffs_ints_misfits(self, dtype, coeffs_per_poly=None):
+        """(array, misfit count, first misfit): the first coeffs_per_poly (default n) coefficients of every entry as a
+        (rows, cols, coeffs_per_poly) array of np.uint32 / np.uint64 (c mod 2^b, c in [0, Q_level)) or np.int32 /
+        np.int64 (the representative in (-Q_level/2, Q_level/2], two's complement); coefficients that do not fit are
+        truncated and counted, `first` is the (row, col, k) of the first of them or None.  One device call
+        (gpupoly_matrix_store_coeff_ints, the matrix left as it is)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.uint32), np.dtype(np.uint64), np.dtype(np.int32), np.dtype(np.int64)):
+            raise TypeError(f"coeffs_ints: dtype must be uint32, uint64, int32 or int64 (got {dt})")
+        n = self.params.ring_dimension()
+        cpp = n if coeffs_per_poly is None else int(coeffs_per_poly)
+        if not 0 <= cpp <= n:
+            raise ValueError(f"coeffs_ints: coeffs_per_poly must lie in [0, {n}] (got {cpp})")
+        out = np.zeros((self.nrow, self.ncol, cpp), dtype=dt)
+        if out.size == 0:
+            return out, 0, None
+        count, first = C.c_uint64(0), C.c_uint64(0)
+        st = _ffi.lib().gpupoly_matrix_store_coeff_ints(self.raw, C.c_void_p(out.ctypes.data), dt.itemsize, 1 if dt.kind == "i" else 0,
+                                                        cpp, C.byref(count), C.byref(first))
+        check_status(st, "gpupoly_matrix_store_coeff_ints")
+        if count.value == 0:
+            return out, 0, None
+        poly, k = divmod(first.value, cpp)
+        return out, count.value, (poly // self.ncol, poly % self.ncol, k)
+
+    def coeffs_ints(self, dtype, coeffs_per_poly=None, strict=True) -> np.ndarray:
+        """coeffs_ints_misfits' array.  strict: an OverflowError naming the first coefficient that does not fit the
+        dtype; otherwise such coefficients are truncated (two's complement for the signed dtypes)."""
+        out, count, first = self.coeffs_ints_misfits(dtype, coeffs_per_poly)
+        if strict and count:
+            raise OverflowError(f"coeffs_ints: {count} coefficient(s) do not fit {np.dtype(dtype).name}, the first at "
+                                f"(row, col, k) = {first}")
+        return out
+
+    def const_coeffs_u64(self, strict=True) -> np.ndarray:
+        """The constant coefficient of every entry as np.uint64, (rows, cols) (`const_coeff_u64`,
+        src/poly/dcrt/gpu.rs:1103-1120, for a whole matrix in one call)."""
+        return self.coeffs_ints(np.uint64, 1, strict)[..., 0]
+
     # ------------------------------------------------------------------ compact wire format
     def to_compact_bytes(self) -> bytes:
         """`into_compact_bytes` (gpu_dcrt_poly.rs:956-1002): bincode(standard) tuple

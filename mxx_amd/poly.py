@@ -180,7 +180,16 @@ class GpuDCRTPoly:
         return self.inner.to_compact_bytes()
 
     def const_coeff_u64(self) -> int:
-        """Constant coefficient through `gpu_matrix_store_const_coeff_batch` + CRT (gpu.rs:1103-1120)."""
+        """Constant coefficient as a u64 (gpu.rs:1103-1120): one device call (gpupoly_matrix_store_coeff_ints, one
+        coefficient); a value that does not fit takes the host path and raises as before."""
+        value, misfits, _ = self.inner.coeffs_ints_misfits(np.uint64, 1)
+        if misfits:
+            return self._const_coeff_u64_host()
+        return int(value[0, 0, 0])
+
+    def _const_coeff_u64_host(self) -> int:
+        """const_coeff_u64 through `gpu_matrix_store_const_coeff_batch` + a host CRT over the limbs, as the reference
+        runs it (kept for comparison, and for the error of a value above 64 bits)."""
         poly = self.inner.ensure_coeff()
         residues = [int(v) for v in poly.store_const_coeff_words().reshape(-1)]
         moduli = poly.params.moduli()[: poly.level + 1]
@@ -197,17 +206,39 @@ class GpuDCRTPoly:
         return value
 
     def extract_bits_with_threshold(self) -> list[bool]:
-        """coefficient in [q/4, 3q/4) -> True (gpu.rs:1070-1081; quarter = (q/2) >> 1)."""
+        """coefficient in [q/4, 3q/4) -> True (gpu.rs:1070-1081; quarter = (q/2) >> 1, q = params.modulus()): one device
+        call (gpupoly_matrix_extract_bits).  Below full level the bounds are capped at the level's own modulus, which
+        no coefficient reaches."""
+        quarter = (self.inner.params.modulus() // 2) >> 1
+        Ql = self.inner._level_modulus()
+        return self.inner.extract_bits(min(quarter, Ql), min(3 * quarter, Ql))[0, 0].tolist()
+
+    def _extract_bits_with_threshold_host(self) -> list[bool]:
+        """extract_bits_with_threshold over coeffs(), as the reference runs it (kept for comparison)."""
         quarter = (self.inner.params.modulus() // 2) >> 1
         return [quarter <= c < 3 * quarter for c in self.coeffs()]
 
     def to_bool_vec(self) -> list[bool]:
+        """gpu.rs:1083-1097: one device call (gpupoly_matrix_store_coeff_ints); a coefficient that is neither 0 nor 1
+        takes the host path and raises as before."""
+        value, misfits, _ = self.inner.coeffs_ints_misfits(np.uint32)
+        if misfits or (value > 1).any():
+            return self._to_bool_vec_host()
+        return (value[0, 0] == 1).tolist()
+
+    def _to_bool_vec_host(self) -> list[bool]:
+        """to_bool_vec over coeffs(), as the reference runs it (kept for comparison, and for its error)."""
         out = []
         for c in self.coeffs():
             if c not in (0, 1):
                 raise ValueError(f"Coefficient is not 0 or 1: {c}")
             out.append(c == 1)
         return out
+
+    def coeffs_digits(self) -> list[int]:
+        """`coeffs_digits` (src/poly/mod.rs:130-139): every coefficient as one u32 digit; a coefficient of more than
+        32 bits (the reference's debug assertion) raises OverflowError."""
+        return self.inner.coeffs_ints(np.uint32).reshape(-1).tolist()
 
     # ---- arithmetic -------------------------------------------------------------------
     def _pair(self, other):
