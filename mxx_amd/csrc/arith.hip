@@ -569,6 +569,10 @@ int launch_matmul(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs) {
         const uint64_t tile_waves = static_cast<uint64_t>((N / 4 + 63) / 64) * ((rows + 1) / 2) * ((cols + tc - 1) / tc) * matrix_limbs(out);
         const bool ahead = tile_waves <= (rows >= 2 ? 1024u : 8192u);  // the 2-row tile drops to 2 waves per SIMD with the second operand set
         if (rows >= 2) return ahead ? launch_matmul_cfg<uint32_t, 2, 8, 4, true>(out, lhs, rhs) : launch_matmul_cfg<uint32_t, 2, 8, 4>(out, lhs, rhs);
+        if (cols >= 8) {  // packed B streamed once: the kernel built for that stream (matmul_skinny24.hip)
+            const int rc = launch_matmul_skinny24(out, lhs, rhs, ahead);
+            if (rc >= 0) return rc;
+        }
         if (cols >= 8) return ahead ? launch_matmul_cfg<uint32_t, 1, 8, 4, true>(out, lhs, rhs) : launch_matmul_cfg<uint32_t, 1, 8, 4>(out, lhs, rhs);
         return ahead ? launch_matmul_cfg<uint32_t, 1, 4, 4, true>(out, lhs, rhs) : launch_matmul_cfg<uint32_t, 1, 4, 4>(out, lhs, rhs);
     }

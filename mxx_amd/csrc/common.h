@@ -52,6 +52,8 @@ struct EnvSwitches {
     bool serde_general = false;   // MXX_HIP_SERDE=general: compact store always through the kernels that carry the general Garner path (tests, A/B)
     bool rng_compat = false;      // MXX_HIP_RNG_COMPAT=reference: sample_distribution* keyed exactly as the reference's device RNG (sampling.hip)
     bool pack24 = true;           // MXX_HIP_PACK24=0|off: uniform samples stay in 4-byte words (layout.hip)
+    int skinny24 = 0;             // MXX_HIP_SKINNY24: 0 auto, 1 = "0" never (matmul_kernel reads packed B, the A/B baseline), 2 = force[:TC,G,WPE,MAP]
+    int skinny24_shape = 0;       // the shape after "force:" (matmul_skinny24.hip; 0: the default shape)
     size_t mul_decompose_many_budget = 0;  // MXX_HIP_MUL_DECOMPOSE_MANY_BUDGET=<bytes>: digit-matrix budget of gpupoly_matrix_mul_decompose_many
                                            // alone (0 = a third of the free memory, at least 8 GiB; tests reach its column chunks with it)
     size_t gadget_scalar_budget = 0;  // MXX_HIP_GADGET_SCALAR_BUDGET=<bytes>: digit-polynomial table budget of
@@ -351,6 +353,8 @@ int launch_mul_intt_u32(GpuContext *ctx, uint32_t *out, const uint32_t *in, cons
 int launch_matmul(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs);
 // forward 2^14 transform of `in` (words) into PACKED24 rows at `out` (3N bytes per vector); -1: no fused kernel here
 int launch_ntt_fwd_pack24_u32(GpuContext *ctx, uint32_t *out, const uint32_t *in, size_t vectors, uint32_t L);
+int launch_matmul_skinny24(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs, bool small_grid);  // -1: not a one-row product against packed B
+int skinny24_parse_shape(const char *s);  // "TC,G,WPE,MAP" -> EnvSwitches::skinny24_shape, 0: not a shape
 int launch_matmul_dma_u32(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs);  // -1: shape not supported
 int launch_matmul_dma32_u32(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs);  // 32 slots x 32x32 tile, 16 waves
 int launch_matmul_mfma_u32(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs);  // -1: shape / moduli not supported

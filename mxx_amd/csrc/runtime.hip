@@ -285,6 +285,14 @@ void EnvSwitches::load() {
     if (const char *e = std::getenv("MXX_HIP_RNG_COMPAT")) rng_compat = e[0] == 'r';
     if (const char *e = std::getenv("MXX_HIP_SERDE")) serde_general = e[0] == 'g';
     if (const char *e = std::getenv("MXX_HIP_PACK24")) pack24 = !(std::strcmp(e, "0") == 0 || std::strcmp(e, "off") == 0);
+    if (const char *e = std::getenv("MXX_HIP_SKINNY24")) {  // 0 | auto | force | force:TC,G,WPE,MAP
+        if (std::strcmp(e, "0") == 0) skinny24 = 1;
+        else if (std::strncmp(e, "force", 5) == 0 && (e[5] == 0 || e[5] == ':')) {
+            skinny24 = 2;
+            // a shape that does not parse stays a shape that is not instantiated: the product refuses it
+            if (e[5] == ':') skinny24_shape = skinny24_parse_shape(e + 6) ? skinny24_parse_shape(e + 6) : -1;
+        }
+    }
     if (const char *e = std::getenv("MXX_HIP_MUL_DECOMPOSE_MANY_BUDGET")) mul_decompose_many_budget = static_cast<size_t>(std::strtoull(e, nullptr, 10));
     if (const char *e = std::getenv("MXX_HIP_GADGET_SCALAR_BUDGET")) gadget_scalar_budget = static_cast<size_t>(std::strtoull(e, nullptr, 10));
     if (const char *e = std::getenv("MXX_HIP_MUL_SUM_PATH")) mul_sum_path = (e[0] == 't' || e[0] == 's') ? e[0] : 0;
