@@ -426,6 +426,32 @@ int gpupoly_trapdoor_preimage_many(const GpuMatrix *re, const GpuP1CovarianceCac
  * level mismatch.  Refused with an error containing "unsupported", likewise untouched: t >= 2^64 - 59, an input below
  * full level (rescale those on the host).                                                                         */
 int gpupoly_matrix_scale_round(GpuMatrix *out, const GpuMatrix *in, uint64_t t, int round_half);
+/* Rounded CRT recomposition of decoded level vectors in one call (extension): crt_recompose_rows
+ * (src/noise_refresh/naive_vec.rs:2086-2118) and the combination of terms in front of it on the online path
+ * (src/noise_refresh/naive_vec.rs:1654-1690).  With L the context's limb count, Q its full modulus and
+ * T = terms_per_level in 1..8, `terms` holds num_slots * L * T matrices; terms[(slot * L + i) * T + t] is term t of
+ * level (slot, i), signs[t] is +1 or -1 and is shared by every level, and level (slot, i) = sum_t signs[t] * term_t
+ * mod Q.  T = 1 with sign +1 is the reference function; T = 4 with signs (+, +, -, -) is the online path's
+ * `input_term + refresh_term - one_term - decoder` (:1687).  The result is
+ *   out[slot][col] limb i, coefficient k = floor((q_i * c + floor(Q/2)) / Q) mod q_i,
+ * c in [0, Q) coefficient k of entry col of level (slot, i): the centred decode for the plaintext modulus q_i
+ * (decode_centered_masked_integer_coeff, src/decoder/masked_high_bit.rs:21-29).  That is the reference's
+ * sum_i decode(level_i, q_i) * reconst_coeffs[i] exactly, because reconst_coeffs[i] (src/poly/mod.rs:45-60) is 1 mod
+ * q_i and 0 mod every other limb.  Every term is 1 x c, at full level, on out's context, and all terms of a call have
+ * one format (all COEFF or all EVAL); `out` is num_slots x c at full level, is written whole and tagged EVAL.  Terms may
+ * repeat; no term is modified.  The signed sums go into scratch of the call (EVAL terms are summed as they lie, then one
+ * inverse transform per level), one thread per output word runs the exact rounding of gpupoly_matrix_scale_round with
+ * t = q_i, and one forward transform of `out` follows.  Scratch comes from the context's allocator, capped by
+ * MXX_HIP_CRT_RECOMPOSE_CHUNK_BYTES (default 256 MiB, never less than one slot): the call works through whole slots per
+ * chunk.  Enqueued on the context's stream; the host does not block.  c = 0 launches nothing and sets the tag.
+ * Overlap: rule 3 - `out` must not overlap any term, row views included (the message contains "overlap").
+ * Refused, before the first launch and with `out` (contents and tag) untouched, the message naming this entry: a null
+ * `out`, `terms` or `signs`; a null terms[j]; num_slots = 0; T = 0 or T > 8; a sign other than +1 / -1; a context or
+ * shape mismatch (`out` not num_slots x c, a term not 1 x c); terms of mixed formats; `out` not at full level; any
+ * overlap of `out` with a term.  Refused likewise with an error containing "unsupported": a term below full level
+ * (recompose those with the per-level calls).                                                                     */
+int gpupoly_matrix_crt_recompose_rounded(GpuMatrix *out, const GpuMatrix *const *terms, const int *signs,
+                                         size_t terms_per_level, size_t num_slots);
 /* Every coefficient of `mat` as its value in [0, Q_level): little-endian 64-bit words, words_per_coeff words each
  * (zero above the words Q_level needs), order [row][col][k], into host memory `out` (synchronous).  COEFF or EVAL
  * input (an EVAL input is inverse-transformed in scratch; `mat` is left as it was).  Replaces the host CRT of

@@ -60,6 +60,9 @@ struct EnvSwitches {
                                       // gpupoly_matrix_mul_decompose_gadget_scalar_many alone (0 = the same rule; tests reach its tower groups with it)
     char mul_sum_path = 0;        // MXX_HIP_MUL_SUM_PATH: 0 auto, 't' the term-table tile kernel at every height, 's' products into
                                   // scratch + one combine pass per term above 8 rows (matmul_sum.hip; A/B, tests)
+    size_t crt_recompose_chunk_bytes = size_t(256) << 20;  // MXX_HIP_CRT_RECOMPOSE_CHUNK_BYTES=<bytes>: scratch cap of
+                                  // gpupoly_matrix_crt_recompose_rounded, which works through whole slots per chunk (at least one
+                                  // slot whatever the cap; tests reach its chunks with it)
     void load();
 };
 

@@ -295,6 +295,10 @@ void EnvSwitches::load() {
     }
     if (const char *e = std::getenv("MXX_HIP_MUL_DECOMPOSE_MANY_BUDGET")) mul_decompose_many_budget = static_cast<size_t>(std::strtoull(e, nullptr, 10));
     if (const char *e = std::getenv("MXX_HIP_GADGET_SCALAR_BUDGET")) gadget_scalar_budget = static_cast<size_t>(std::strtoull(e, nullptr, 10));
+    if (const char *e = std::getenv("MXX_HIP_CRT_RECOMPOSE_CHUNK_BYTES")) {
+        const size_t v = static_cast<size_t>(std::strtoull(e, nullptr, 10));
+        if (v >= 1) crt_recompose_chunk_bytes = v;
+    }
     if (const char *e = std::getenv("MXX_HIP_MUL_SUM_PATH")) mul_sum_path = (e[0] == 't' || e[0] == 's') ? e[0] : 0;
     if (const char *e = std::getenv("MXX_HIP_SAMPLER_PER_LANE")) {
         const int v = std::atoi(e);

@@ -19,10 +19,9 @@
 #include "common.h"
 #include "crt.h"
 #include "modarith.h"
+#include "scale_exact.h"
 
 namespace {
-
-constexpr uint64_t kAuxM = 0xFFFFFFFFFFFFFFC5ull;  // 2^64 - 59, prime; 2^64 = 59 (mod m)
 
 struct ScaleConsts {
     int limbs;
@@ -40,38 +39,6 @@ struct WordConsts {
     int words;  // 64-bit words of Q_level
     uint64_t q[GPUPOLY_MAX_LIMBS];
 };
-
-// x mod m for x < 2^128: x = hi 2^64 + lo = 59 hi + lo (mod m), twice
-__device__ __forceinline__ uint64_t aux_reduce(u128_t x) {
-    const u128_t y = static_cast<u128_t>(static_cast<uint64_t>(x >> 64)) * 59u + static_cast<uint64_t>(x);  // < 2^70
-    const uint64_t lo = static_cast<uint64_t>(y), hi = static_cast<uint64_t>(y >> 64);                       // hi < 64
-    uint64_t r = lo + hi * 59u;
-    if (r < lo) r += 59u;  // wrapped past 2^64: r < 3776 here
-    return r >= kAuxM ? r - kAuxM : r;
-}
-__device__ __forceinline__ uint64_t aux_mul(uint64_t a, uint64_t b) { return aux_reduce(static_cast<u128_t>(a) * b); }
-__device__ __forceinline__ uint64_t aux_add(uint64_t a, uint64_t b) {  // a, b < m
-    const uint64_t r = a + b;
-    return (r < a || r >= kAuxM) ? r - kAuxM : r;
-}
-__device__ __forceinline__ uint64_t aux_sub(uint64_t a, uint64_t b) { return a >= b ? a - b : a + (kAuxM - b); }
-
-// v < 2^64 -> v mod q with floor(2^64 / q): the quotient estimate is at most one short
-__device__ __forceinline__ uint64_t reduce_word(uint64_t v, uint64_t q, uint64_t mu64) {
-    uint64_t r = v - __umul64hi(v, mu64) * q;
-    return r >= q ? r - q : r;
-}
-
-template <typename W, int ML>
-__device__ __forceinline__ void load_residues(const W *src, size_t poly, uint32_t i, uint32_t N, int L, uint64_t *res) {
-    if constexpr (ML <= 16) {
-#pragma unroll
-        for (int k = 0; k < ML; ++k)
-            if (k < L) res[k] = static_cast<uint64_t>(src[(poly * L + k) * N + i]);
-    } else {
-        for (int k = 0; k < L; ++k) res[k] = static_cast<uint64_t>(src[(poly * L + k) * N + i]);
-    }
-}
 
 // src and dst may be the same matrix: a thread reads all residues of its coefficient before it writes any
 template <typename W, int ML>
@@ -143,38 +110,7 @@ __global__ void __launch_bounds__(256) coeff_words_kernel(const W *__restrict__ 
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
-typedef unsigned __int128 u128h;
-
-uint64_t h_mulmod64(uint64_t a, uint64_t b, uint64_t m) { return static_cast<uint64_t>(static_cast<u128h>(a) * b % m); }
-
-uint64_t h_powmod64(uint64_t b, uint64_t e, uint64_t m) {
-    uint64_t r = 1 % m;
-    for (b %= m; e; e >>= 1, b = h_mulmod64(b, b, m))
-        if (e & 1) r = h_mulmod64(r, b, m);
-    return r;
-}
-
-// little-endian words of q_0 .. q_{L-1}
-std::vector<uint64_t> h_product_words(const std::vector<uint64_t> &moduli, int L) {
-    std::vector<uint64_t> Q(1, 1);
-    for (int l = 0; l < L; ++l) {
-        u128h carry = 0;
-        for (size_t w = 0; w < Q.size(); ++w) {
-            const u128h p = static_cast<u128h>(Q[w]) * moduli[l] + carry;
-            Q[w] = static_cast<uint64_t>(p);
-            carry = p >> 64;
-        }
-        if (carry) Q.push_back(static_cast<uint64_t>(carry));
-    }
-    return Q;
-}
-
-uint64_t h_words_mod(const std::vector<uint64_t> &x, uint64_t m) {
-    u128h r = 0;
-    for (size_t w = x.size(); w-- > 0;) r = ((r << 64) | x[w]) % m;
-    return static_cast<uint64_t>(r);
-}
-
+// the multi-word helpers that build the constants: scale_exact.h
 #define BY_LIMBS(KERNEL, WT, L, ...)                                                                       \
     do {                                                                                                   \
         if ((L) <= 8) MXX_LAUNCH((KERNEL<WT, 8>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__);           \
@@ -209,9 +145,7 @@ extern "C" int gpupoly_matrix_scale_round(GpuMatrix *out, const GpuMatrix *in, u
     sc.limbs = L;
     sc.t = t;
     const std::vector<uint64_t> Q = h_product_words(ctx->moduli, L);
-    std::vector<uint64_t> half(Q.size(), 0);  // floor(Q/2)
-    if (round_half)
-        for (size_t w = 0; w < Q.size(); ++w) half[w] = (Q[w] >> 1) | (w + 1 < Q.size() ? Q[w + 1] << 63 : 0);
+    const std::vector<uint64_t> half = round_half ? h_half_words(Q) : std::vector<uint64_t>(Q.size(), 0);  // h
     sc.h_m = h_words_mod(half, kAuxM);
     sc.qinv_m = h_powmod64(h_words_mod(Q, kAuxM), kAuxM - 2, kAuxM);
     uint64_t pm = 1;

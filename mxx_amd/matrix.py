@@ -906,6 +906,83 @@ class GpuDCRTPolyMatrix:
         out.ntt_all_in_place()
         return out
 
+    @staticmethod
+    def _check_crt_levels(params, firsts, num_slots) -> int:
+        """the reference's assertions on the level vectors (naive_vec.rs:2090-2099); returns the column count"""
+        _, _, crt_depth = params.to_crt()
+        assert len(firsts) == num_slots * crt_depth, "level vector count must equal num_slots * crt_depth"
+        assert len(firsts) > 0, "CRT recomposition requires at least one level vector"
+        output_cols = firsts[0].col_size()
+        assert all(v.row_size() == 1 and v.col_size() == output_cols for v in firsts), \
+            "CRT recomposition level vectors must be one-row matrices with a consistent column count"
+        return output_cols
+
+    @staticmethod
+    def crt_recompose_rows(params, crt_values, num_slots) -> "GpuDCRTPolyMatrix":
+        """`crt_recompose_rows` (src/noise_refresh/naive_vec.rs:2086-2118): crt_values[slot * crt_depth + i] is the 1 x c
+        level vector of (slot, limb i); row `slot` of the num_slots x c result is sum_i decode_centered(level_i, q_i) *
+        reconst_coeffs[i].  One device call (gpupoly_matrix_crt_recompose_rounded): limb i of the row is the decode of
+        level i alone.  The reference's loop over the per-level calls where the entry reports "unsupported" (a level vector
+        below full level).  EVAL at full level; the level vectors are left as they were."""
+        crt_values = list(crt_values)
+        return GpuDCRTPolyMatrix.crt_recompose_rows_terms(params, [[v] for v in crt_values], [1], num_slots)
+
+    @staticmethod
+    def crt_recompose_rows_terms(params, terms, signs, num_slots) -> "GpuDCRTPolyMatrix":
+        """Extension: crt_recompose_rows of the levels sum_t signs[t] * terms[level][t] without forming them - terms[level]
+        is a list of T <= 8 one-row matrices, signs[t] is +1 or -1 for every level (the online path's
+        `input_term + refresh_term - one_term - decoder`, naive_vec.rs:1687, is T = 4 with signs (+, +, -, -)).  Terms in
+        mixed domains are brought to EVAL on copies: the caller's matrices are never changed."""
+        terms = [list(level) for level in terms]
+        signs = [int(s) for s in signs]
+        T = len(signs)
+        assert 1 <= T <= 8, "1 to 8 terms per level"
+        assert all(s in (1, -1) for s in signs), "signs are +1 or -1"
+        assert all(len(level) == T for level in terms), "every level has one term per sign"
+        flat = [m for level in terms for m in level]
+        output_cols = GpuDCRTPolyMatrix._check_crt_levels(params, [level[0] for level in terms], num_slots)
+        for m in flat:
+            assert m.params == params, "CRT recomposition requires the level vectors' params"
+            assert m.row_size() == 1 and m.col_size() == output_cols, "terms of a level share its shape"
+        if len({m.is_ntt for m in flat}) > 1:
+            flat = [m.ensure_eval() for m in flat]
+        out = GpuDCRTPolyMatrix(params, num_slots, output_cols, params.crt_depth() - 1, True)
+        tarr = (C.c_void_p * len(flat))(*[m.raw.value for m in flat])
+        sarr = (C.c_int * T)(*signs)
+        st = _ffi.lib().gpupoly_matrix_crt_recompose_rounded(out.raw, tarr, sarr, T, num_slots)
+        if st != 0 and "unsupported" in _ffi.last_error_string():
+            levels = []
+            for j in range(len(terms)):
+                acc = None
+                for m, s in zip(flat[j * T:(j + 1) * T], signs):
+                    acc = (m if s > 0 else -m) if acc is None else (acc + m if s > 0 else acc - m)
+                levels.append(acc)
+            return GpuDCRTPolyMatrix._crt_recompose_rows_loop(params, levels, num_slots)
+        check_status(st, "gpupoly_matrix_crt_recompose_rounded")
+        out.is_ntt = True
+        return out
+
+    @staticmethod
+    def _crt_recompose_rows_loop(params, crt_values, num_slots) -> "GpuDCRTPolyMatrix":
+        """crt_recompose_rows as the reference runs it (naive_vec.rs:2100-2117), over the per-level device calls: for every
+        slot a zero row, for every limb decode_centered(level, q_i) * constant_poly(reconst_coeffs[i]) added in place, the
+        rows concatenated."""
+        from .poly import GpuDCRTPoly
+
+        crt_values = list(crt_values)
+        q_moduli, _, crt_depth = params.to_crt()
+        output_cols = GpuDCRTPolyMatrix._check_crt_levels(params, crt_values, num_slots)
+        reconst_coeffs = params.reconst_coeffs()
+        rows = []
+        for slot_idx in range(num_slots):
+            row = GpuDCRTPolyMatrix.zero(params, 1, output_cols)
+            for crt_idx in range(crt_depth):
+                level = crt_values[slot_idx * crt_depth + crt_idx]
+                rounded = level.decode_centered(q_moduli[crt_idx])
+                row.add_in_place(rounded.mul_scalar(GpuDCRTPoly.from_biguint_to_constant(params, reconst_coeffs[crt_idx])))
+            rows.append(row)
+        return rows[0].concat_rows(rows[1:])
+
     @classmethod
     def from_compact_bytes(cls, params, data: bytes) -> "GpuDCRTPolyMatrix":
         """gpu_dcrt_poly.rs:1004-1044."""

@@ -108,6 +108,16 @@ class DCRTPolyParams:
     def to_crt(self):
         return list(self._moduli), self._crt_bits, self._depth
 
+    def reconst_coeffs(self) -> list:
+        """CRT reconstruction coefficients (Q / q_i) * ((Q / q_i)^-1 mod q_i) mod Q, one per limb (src/poly/mod.rs:45-60)."""
+        return [self.to_crt_coeffs(i)[1] for i in range(self._depth)]
+
+    def to_crt_coeffs(self, crt_idx: int):
+        """(Q / q_i, the reconstruction coefficient of limb i) (src/poly/mod.rs:62-76)."""
+        q = self._moduli[crt_idx]
+        q_over_qi = self._modulus // q
+        return q_over_qi, q_over_qi * pow(q_over_qi % q, -1, q) % self._modulus
+
     def __eq__(self, other):
         return isinstance(other, DCRTPolyParams) and (self._n, self._moduli, self._base_bits) == (
             other._n,
@@ -295,6 +305,14 @@ class GpuDCRTPolyParams:
             Qi = Q // q
             out.append(Qi * pow(Qi % q, -1, q) % Q)
         return out
+
+    def reconst_coeffs(self) -> list:
+        """CRT reconstruction coefficients, one per limb (src/poly/mod.rs:45-60): the full-level weights."""
+        return self.reconstruct_coeffs_for_level(len(self._moduli) - 1)
+
+    def to_crt_coeffs(self, crt_idx: int):
+        """(Q / q_i, the reconstruction coefficient of limb i) (src/poly/mod.rs:62-76)."""
+        return self._modulus // self._moduli[crt_idx], self.reconst_coeffs()[crt_idx]
 
     def __eq__(self, other):
         return (
