@@ -232,6 +232,19 @@ int set_error(hipError_t err, const char *what);
         if (_e != hipSuccess) return set_error(_e, #expr);     \
     } while (0)
 
+// Kernels that ask for more than 64 KB of dynamic LDS must opt in, once per (kernel set, device).  `lds` is a property of
+// the kernel set: every launch of these kernels asks for the same amount.
+template <auto... KERNELS>
+static int lds_opt_in(const GpuContext *ctx, size_t lds) {
+    static std::atomic<uint64_t> configured{0};
+    const uint64_t bit = 1ull << (ctx->device & 63);
+    if (lds <= 64 * 1024 || (configured.load() & bit)) return 0;
+    for (const void *f : {reinterpret_cast<const void *>(KERNELS)...})
+        HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    configured.fetch_or(bit);
+    return 0;
+}
+
 // roctx range around an ABI entry (rocprofv3 --marker-trace attributes kernels to the FFI call that launched them).
 // Active under rocprofv3 (ROCP_TOOL_LIBRARIES is set by it) or with MXX_HIP_ROCTX=1; one predictable branch otherwise.
 extern int (*g_roctx_push)(const char *);
@@ -342,7 +355,7 @@ int coeff_domain_source(const GpuMatrix *mat, CtxBlock &scratch, const void **sr
 
 // internal launchers shared across translation units
 int launch_ntt(GpuContext *ctx, void *data, size_t vectors, int limbs_per_poly, bool inverse);
-// tuned LDS kernels (ntt_lds_u32.hip / ntt_lds_u64.hip); return -1 when no tuned kernel covers logN
+// tuned LDS kernels (ntt_lds_u32.hip / ntt_lds_u64.hip over the ring table of ntt_rings.h); return -1 when no tuned kernel covers logN
 int launch_ntt_lds_u32(GpuContext *ctx, uint32_t *data, size_t vectors, uint32_t L, bool inverse);
 int launch_ntt_digits_u32(GpuContext *ctx, uint32_t *out, const uint32_t *coeff, size_t out_vectors, uint32_t L,
                           uint32_t src_cols, uint32_t towers, uint32_t dpt, uint32_t base_bits, size_t k, uint32_t td0 = 0);

@@ -119,11 +119,8 @@ static int launch_generic(GpuContext *ctx, W *data, size_t vectors, uint32_t L) 
     const uint32_t logN = ctx->logN;
     const size_t N = size_t(1) << logN;
     const size_t lds = N * sizeof(W);
-    auto kern = ntt_generic_kernel<W, INV>;
-    if (lds > 64 * 1024) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>(lds)));
-    }
+    // one ring size per word type lies between 64 KB and kMaxLdsBytes (2^15 points in 32-bit words, 2^14 in 64-bit)
+    if (int rc = lds_opt_in<ntt_generic_kernel<W, INV>>(ctx, lds)) return rc;
     unsigned threads = static_cast<unsigned>(N / 2);
     if (threads < 64) threads = 64;
     if (threads > 512) threads = 512;

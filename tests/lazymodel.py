@@ -25,9 +25,9 @@ Sources restated (mxx_amd/csrc, line numbers as of this model; a change there mu
 - ntt_f64.h: kFolded = 2 :31, mulmod :33-38, fold :39, fwd_next / inv_next :42-43, CtStages :47-71, GsStages :75-102,
   to_residue :104-109, small_kernel :123-180, fwd_body :186-238, head_kernel :256-307, inv_kernel :328-391,
   tail_kernel :396-412.
-- ntt_lds_dispatch.inc: launch_ntt14 :62-101, launch_split :104-133, dispatch_ntt_lds_impl :253-277 (pass split per
-  ring size and word size), launch_mul_intt :353-374.  ntt_lds_u64.hip: dispatch_f64 :80-93, the small kernel below
-  2^10 :114-115, ELIM by the widest modulus (40 / 49 bits) :117-119.
+- ntt_rings.h: visit_ring (the ring table: pass split per ring size and word size), launch_ntt14, launch_split,
+  launch_ntt_lds.  ntt_lds_u32.hip: launch_mul_intt_u32.  ntt_lds_u64.hip: launch_ntt_lds_u64 (the small kernel below
+  2^10 first, then the same table), by_elim (ELIM by the widest modulus, 40 / 49 bits).
 - runtime.hip: Shoup companions floor(w 2^W / q) :414, centred signed twiddles :467-474, lazy_ok `+ 7` :620,
   tight_ok `+ 4` :621, signed_ok `<= 24` :622, the 2^32 of the MULW N^-1 constants :640-646.
 
@@ -80,7 +80,7 @@ def _lds_split(logn, logr):
 
 
 def int_schedule(W: int, logn: int, ntt14: str = "grouped"):
-    """Pass split of the integer lazy kernels (ntt_lds_dispatch.inc dispatch_ntt_lds_impl / launch_ntt14 /
+    """Pass split of the integer lazy kernels (ntt_rings.h visit_ring / launch_ntt14 /
     launch_split).  Returns (name, forward passes [(stages, prefold)] from stage 0 up, inverse passes [stages] from
     stage logn - 1 down).  `ntt14`: "grouped" (ntt14.h) or "whole" (MXX_HIP_NTT14=whole, and every 64-bit 2^14)."""
     if logn == 14 and W == 32 and ntt14 != "whole":
@@ -99,12 +99,13 @@ def int_schedule(W: int, logn: int, ntt14: str = "grouped"):
 
 
 def f64_elim(bits: int) -> int:
-    """ntt_lds_u64.hip launch_ntt_lds_u64: the fold schedule by the widest modulus."""
+    """ntt_lds_u64.hip by_elim: the fold schedule by the widest modulus."""
     return 4095 if bits <= 40 else 63 if bits <= 49 else 15
 
 
 def f64_schedule(logn: int):
-    """ntt_lds_u64.hip dispatch_f64: (name, sub-vector log size, LOGR, PRE); "small" below 2^10."""
+    """ntt_rings.h visit_ring, 64-bit column (ntt_lds_u64.hip launch_ntt_lds_u64): (name, sub-vector log size, LOGR,
+    PRE); "small" below 2^10."""
     if logn < 10:
         return "small", logn, 0, 0
     if logn >= 15:

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 
 from conftest import make_params, rand_matrix
+from mxx_amd import _ffi
+from mxx_amd.codeobj import kernel_base
 
 pytestmark = pytest.mark.gpu
 
@@ -443,6 +445,15 @@ def test_decompose_fused_with_ntt_at_2_14(gpu, oracle, hip_env, depth, bits, bas
     assert G * fused == gm.ensure_eval()
 
 
+def _fused_decompose_family(logn, bits):
+    """The launches of a digit-fused decompose of a COEFF source, in order (launch_ntt_digits_u32 / _u64)."""
+    if bits > 32:  # 51-bit limbs: the double-precision kernels
+        return ["nttf::fwd_digits_kernel"] if logn <= 14 else ["nttf::head_kernel", "nttf::fwd_kernel"]
+    if logn == 14:
+        return ["ntt14::fwd_digits_kernel"]
+    return ["ntt_fwd_lazy_digits_kernel"] if logn <= 15 else ["ntt_fwd_head_digits_kernel", "ntt_fwd_lazy_kernel"]
+
+
 @pytest.mark.parametrize("logn,depth,bits,base", [
     (14, 2, 28, 14), (16, 2, 24, 12), (16, 3, 28, 14), (17, 2, 28, 9), (16, 2, 24, 24), (17, 2, 24, 12),
     (10, 3, 24, 12), (11, 2, 28, 14), (12, 2, 24, 7), (12, 2, 24, 24), (13, 2, 28, 14), (15, 2, 24, 12), (15, 2, 28, 9),
@@ -460,7 +471,15 @@ def test_decompose_fused_with_ntt_tight_and_split_sizes(gpu, oracle, hip_env, lo
     M[0, 0, :, :3] = (np.asarray(moduli, dtype=np.uint64) - np.uint64(1)).reshape(-1, 1)
     gm = gpu.GpuDCRTPolyMatrix.from_rns(p, M, False)
     want = oracle.matrix_ntt(oracle.decompose(M, moduli, base), moduli)
+    gpu.gpu_device_sync()
+    _ffi.trace_begin()
     fused = gm.decompose()
+    gpu.gpu_device_sync()
+    ran = [kernel_base(t["kernel"]) for t in _ffi.trace_end()]
+    # the two-step fallback gives the same bits, so the values below cannot tell whether the fused launcher ran
+    assert "decompose_kernel" not in ran and "decompose_rows_kernel" not in ran, ran
+    family = _fused_decompose_family(logn, bits)
+    assert [k for k in ran if k in family] == family, (family, ran)
     assert fused.is_ntt and np.array_equal(fused.to_rns(), want)
     assert gm.ensure_eval().decompose() == fused
     small = gm.small_decompose()

@@ -128,7 +128,7 @@ def test_m3_preimage_relation_and_norm(gpu, oracle, depth):
 @pytest.mark.parametrize("logn,bits,polys", [(13, 24, 8192), (14, 24, 4096), (15, 28, 2048), (12, 51, 8192)])
 def test_ntt_batches_beyond_the_infinity_cache(gpu, oracle, logn, bits, polys):
     """Batches of at least 1 GiB take the non-temporal forms of the whole-vector LDS kernels and of the grouped 2^14
-    kernels (ntt_lds_dispatch.inc):
+    kernels (ntt_rings.h launch_lazy / launch_ntt14, ntt_lds_u64.hip launch_f64):
     round trip on the device, the first and last polynomials against the CPU restatement, both directions."""
     n = 1 << logn
     moduli = oracle.gen_crt_basis(n, 4, bits)

@@ -159,7 +159,7 @@ MULW_CELLS = [(25, 13), (24, 14), (25, 14), (28, 14), (26, 15), (28, 16), (25, 1
 
 
 def _mulw_kernels(bits, logn):
-    """The launches of the fused path (ntt_lds_dispatch.inc launch_mul_intt); the fallback (ntt.hip: point-wise product
+    """The launches of the fused path (ntt_lds_u32.hip launch_mul_intt_u32); the fallback (ntt.hip: point-wise product
     then the plain inverse) adds an elementwise_kernel launch in front."""
     if logn >= 16:
         return ["ntt_inv_lazy_kernel", "ntt_inv_tail_kernel"]  # launch_split_mulw
