@@ -276,6 +276,13 @@ int gpupoly_matrix_ntt_add_rows(GpuMatrix *out, size_t dst_row, GpuMatrix *coeff
 /* A matrix object over rows [row, row + rows) of m (contiguous in the row-major layout) that SHARES m's storage - an
  * operand without the copy a slice makes.  Destroy it with gpu_matrix_destroy (the storage stays m's) before m.  */
 int gpupoly_matrix_row_view(GpuMatrix *m, size_t row, size_t rows, GpuMatrix **out_view);
+/* The same for the whole of m under another shape (extension): a rows x cols matrix object over ALL of
+ * m's storage, rows * cols == m->rows * m->cols, entry (i, j) of the view = polynomial i * cols + j of m's row-major
+ * order.  Its rules are gpupoly_matrix_row_view's: it shares words (a PACKED24 m is unpacked first and stays in words
+ * while a view lives), carries its own format tag initialised from m's, and is destroyed with gpu_matrix_destroy before
+ * m.  The overlap rule sees it through its byte range: it is the same block as m, and overlaps every view of m.
+ * Refused, with nothing launched: a null argument; a polynomial count that differs.                               */
+int gpupoly_matrix_reshape_view(GpuMatrix *m, size_t rows, size_t cols, GpuMatrix **out_view);
 /* out = -src in one pass (the reference's wrapper: upload zeros, clone, subtract - gpu_dcrt_poly.rs:1890-1897). */
 int gpupoly_matrix_neg(GpuMatrix *out, const GpuMatrix *src);
 int gpupoly_matrix_fill_zero(GpuMatrix *out);
@@ -385,6 +392,34 @@ int gpupoly_matrix_sample_p1_full_cached_segments(const GpuP1CovarianceCache *ca
 int gpupoly_matrix_gauss_samp_gq_arb_base_segments(GpuMatrix *src, uint32_t base_bits, double c, double dgg_stddev,
                                                    const GpuRngSeed *seeds, const size_t *seg_cols, size_t nseg,
                                                    GpuMatrix *out);
+/* Uniform / bit / ternary samples of `nblk` independently seeded blocks in one call (extension): the
+ * tagged sample_hash loops of src/commit/wee25.rs:687-703,858-883, src/lookup/ggh15/pubkey_gpu.rs:924,1296 and
+ * src/lookup/lwe/pubkey_gpu.rs:559,616, which draw one small matrix per index.  nblk is 1..2^20, not bounded by the 64
+ * segments of the Gaussian entries: the sub-keys (nblk x limbs for the uniform distribution, nblk otherwise) and the
+ * segment starts live in a table from the context's allocator, released stream-ordered, and the number of launches
+ * (key derivation, sampling, transform or pack) does not depend on nblk.  `seeds` (nblk of them) are read before the
+ * call returns.  Every sample is the plain entry's: the default keying of gpu_matrix_sample_distribution, with the
+ * polynomial's index INSIDE its block as the stream id.
+ *   GPUPOLY_BLOCKS_STACKED (seg_cols == NULL): out is nblk x P; row t holds, bit for bit, the P polynomials
+ *       gpu_matrix_sample_distribution writes into any r x c matrix with r * c == P under seeds[t], in row-major
+ *       order (the local index is the column).  sum_t W_t o a_t is then the one-row product [a_0 .. a_(nblk-1)] * out.
+ *   GPUPOLY_BLOCKS_COLUMNS: out = [S_0 | S_1 | ...], S_j = out->rows x seg_cols[j] = what the plain entry writes for a
+ *       matrix of that shape under seeds[j] (the local index is row * seg_cols[j] + local column): the semantics of
+ *       gpupoly_matrix_sample_distribution_segments.
+ * `out` ends as the plain entry leaves it: tagged EVAL, at its own level, GPU_MATRIX_LAYOUT_PACKED24 where a uniform
+ * sample of the plain entry would be.  Enqueued on the context's stream; the host does not block.  An `out` without
+ * polynomials succeeds with nothing launched and is tagged EVAL.
+ * Overlap: the only matrix is `out`; nothing can overlap.
+ * Refused, with nothing launched and `out` (contents AND tag) untouched, the message naming this entry: a null `out` or
+ * `seeds`; nblk == 0 or above 2^20; an unknown layout; STACKED with seg_cols != NULL or out->rows != nblk; COLUMNS with
+ * a null seg_cols, a zero width or widths that do not sum to out->cols; an invalid dist_type; a block of 2^48
+ * polynomials or more (the 48-bit stream ids).  Refused likewise with an error containing "unsupported": the Gaussian
+ * distribution (gpupoly_matrix_sample_distribution_segments is its entry); a context created under
+ * MXX_HIP_RNG_COMPAT=reference (issue the requests one by one).                                                   */
+#define GPUPOLY_BLOCKS_STACKED 0
+#define GPUPOLY_BLOCKS_COLUMNS 1
+int gpupoly_matrix_sample_distribution_blocks(GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, size_t nblk,
+                                              int layout, const size_t *seg_cols);
 /* out = [blocks[0] | blocks[1] | ...] / blocks[j] = the next blocks[j]->cols columns of src, in one launch per 64
  * blocks (the wrapper's concat_columns / slice_columns are a gpu_matrix_copy_block launch per block,
  * src/matrix/gpu_dcrt_poly.rs:1216-1260).  Same rows, level and context everywhere; the written side takes the read

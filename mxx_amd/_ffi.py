@@ -20,6 +20,8 @@ GPU_MATRIX_DIST_UNIFORM = 0
 GPU_MATRIX_DIST_GAUSS = 1
 GPU_MATRIX_DIST_BIT = 2
 GPU_MATRIX_DIST_TERNARY = 3
+GPUPOLY_BLOCKS_STACKED = 0
+GPUPOLY_BLOCKS_COLUMNS = 1
 
 
 class GpuPolyError(RuntimeError):
@@ -115,6 +117,7 @@ SIGNATURES = {
     "gpupoly_matrix_add_rows": (C.c_int, [_vp, C.c_size_t, _vp, _vp]),
     "gpupoly_matrix_ntt_add_rows": (C.c_int, [_vp, C.c_size_t, _vp, _vp, C.c_int]),
     "gpupoly_matrix_row_view": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "gpupoly_matrix_reshape_view": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]),
     "gpupoly_matrix_neg": (C.c_int, [_vp, _vp]),
     "gpupoly_matrix_fill_zero": (C.c_int, [_vp]),
     "gpupoly_matrix_fill_identity": (C.c_int, [_vp, _vp]),
@@ -138,7 +141,8 @@ SIGNATURES = {
     "gpupoly_comm_backend": (C.c_char_p, [_vp]),
     "gpupoly_matrix_all_gather_columns": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "gpupoly_matrix_sample_distribution_segments": (C.c_int, [_vp, C.c_int, C.c_double, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz]),
-    "gpupoly_matrix_sample_p1_full_cached_segments": (C.c_int, [_vp, _vp, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz, _vp]),
+    "gpupoly_matrix_sample_distribution_blocks": (C.c_int, [_vp, C.c_int, C.POINTER(GpuRngSeed), _sz, C.c_int, C.POINTER(_sz)]),
+    "gpupoly_matrix_sample_p1_full_cached_segments":(C.c_int, [_vp, _vp, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz, _vp]),
     "gpupoly_matrix_gauss_samp_gq_arb_base_segments": (C.c_int, [_vp, C.c_uint32, C.c_double, C.c_double, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz, _vp]),
     "gpupoly_matrix_concat_columns": (C.c_int, [_vp, C.POINTER(C.c_void_p), _sz]),
     "gpupoly_matrix_split_columns": (C.c_int, [_vp, C.POINTER(C.c_void_p), _sz]),

@@ -308,6 +308,32 @@ extern "C" int gpupoly_matrix_row_view(GpuMatrix *m, size_t row, size_t rows, Gp
     ABI_GUARD_END
 }
 
+// Extension: the whole of `m` under another shape with the same polynomial count - the row-major order is the layout, so
+// only the object's rows / cols change.  A row view in every other respect: shared words, its own format tag, counted
+// in m->views, destroyed before m; the same block as m under the overlap rule (same start, same byte length).
+extern "C" int gpupoly_matrix_reshape_view(GpuMatrix *m, size_t rows, size_t cols, GpuMatrix **out_view) {
+    ABI_GUARD_BEGIN
+    if (!m || !out_view) return set_error("gpupoly_matrix_reshape_view: null argument");
+    const size_t polys = matrix_polys(m);
+    if (polys ? (rows == 0 || polys % rows || polys / rows != cols) : (rows != 0 && cols != 0))
+        return set_error("gpupoly_matrix_reshape_view: the view must hold the matrix's polynomial count");
+    void *base = words_ptr(m);  // a view shares words: a packed parent is unpacked first
+    GpuMatrix *v = new GpuMatrix(*m);
+    v->rows = rows;
+    v->cols = cols;
+    v->storage = polys ? base : nullptr;
+    v->borrowed = true;
+    v->views = 0;
+    v->parent = m;
+    {
+        std::lock_guard<std::mutex> lk(m->ctx->layout_mutex);
+        ++m->views;
+    }
+    *out_view = v;
+    return 0;
+    ABI_GUARD_END
+}
+
 extern "C" void gpu_matrix_destroy(GpuMatrix *mat) {
     if (!mat) return;
     if (mat->parent) {

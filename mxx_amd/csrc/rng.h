@@ -748,6 +748,49 @@ static inline bool rng_segments_build(RngSegments &out, const GpuRngSeed *seeds,
     return at == total_cols;
 }
 
+// ---- seeded blocks: any number of independent requests sampled by ONE launch (uniform / bit / ternary) ---------------
+// The fixed-position samplers of sampling.hip key a draw by (sub-key, polynomial index, limb, coefficient) alone, so
+// `nblk` requests with a seed each can share a launch as long as every polynomial finds ITS block's sub-key and ITS index
+// inside that block.  Unlike RngSegments the table is not a kernel argument (nblk goes up to 2^20): it lives in device
+// memory - keys [nblk][keys_per_block] (uniform: one per limb, sub-key (seed, limb + 1); bit / ternary: one, (seed, 0)),
+// then, for the columns layout, the first column of every block.  Two layouts of the output matrix:
+//   stacked (starts == nullptr): row t of the nblk x cols matrix is block t, the local index is the column - a division;
+//   columns: block j is columns [starts[j], starts[j + 1]) of every row, the local index row * width + local column -
+//            a binary search in `starts`.
+struct RngBlockTable {
+    const ChaChaKey *keys;
+    const uint64_t *starts;  // columns layout: [nblk + 1], starts[nblk] = cols
+    uint64_t cols;           // columns of the output matrix
+    uint32_t nblk, keys_per_block;
+};
+struct RngBlockRef {
+    uint32_t blk;    // the polynomial's block
+    uint64_t local;  // its index inside that block: stream (local + 1, .) under the block's sub-key
+};
+
+#if defined(__HIPCC__)
+// block and local index of polynomial p (row-major index in the output matrix)
+__device__ __forceinline__ RngBlockRef rng_block_of(const RngBlockTable &t, uint64_t p) {
+    const uint64_t row = p / t.cols, col = p - row * t.cols;
+    RngBlockRef r;
+    if (!t.starts) {
+        r.blk = static_cast<uint32_t>(row);
+        r.local = col;
+        return r;
+    }
+    uint32_t lo = 0, hi = t.nblk;  // starts[lo] <= col < starts[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (col >= t.starts[mid]) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t first = t.starts[lo];
+    r.blk = lo;
+    r.local = row * (t.starts[lo + 1] - first) + (col - first);
+    return r;
+}
+#endif
+
 static inline uint32_t sampler_per_lane(size_t total, const void *kernel, int device, int forced) {
     if (forced >= 1) return static_cast<uint32_t>(forced);
     int blocks_per_cu = 0, cus = 0;

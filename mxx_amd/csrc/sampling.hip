@@ -544,6 +544,199 @@ extern "C" int gpupoly_matrix_sample_distribution_segments(GpuMatrix *out, int d
     ABI_GUARD_END
 }
 
+// ---- seeded blocks: uniform / bit / ternary samples of many independently seeded requests in one call (rng.h,
+// RngBlockTable) -------------------------------------------------------------------------------
+// The plain kernels' shape - a thread owns eight consecutive coefficients of one (polynomial, limb) vector, one keystream
+// block in registers, 32 / 64 contiguous bytes stored per lane - with the sub-key and the stream id looked up per
+// polynomial.  The look-up (a division, or a binary search in the start table: dependent loads) would sit in front of
+// the block function of every thread; instead the first lanes of a workgroup resolve the few polynomials its 256 items
+// touch (at most 256, one at n >= 2048) into LDS, once, and every thread then reads its polynomial's block and local
+// index from there: the dependent chain in front of the generator is what the plain kernel has, a 32-byte key load.
+__global__ void derive_block_subkeys_kernel(ChaChaKey *__restrict__ keys, const GpuRngSeed *__restrict__ seeds, uint64_t tag, size_t nblk,
+                                            uint32_t per_block, uint32_t first_stream2) {
+    const size_t i = item_index();
+    if (i >= nblk * per_block) return;
+    const size_t t = i / per_block;
+    keys[i] = chacha_subkey(seeds[t], static_cast<uint64_t>(first_stream2) + (i - t * per_block), tag);
+}
+
+// the polynomials of this workgroup's items [base, base + 256) -> refs[p - *p_first]; false: no item (the whole workgroup leaves)
+__device__ __forceinline__ bool resolve_blocks(const RngBlockTable &table, size_t total, size_t per_poly, RngBlockRef *refs, size_t *p_first) {
+    const size_t base = item_index() - threadIdx.x;
+    if (base >= total) return false;
+    const size_t last = (total - base > blockDim.x ? base + blockDim.x : total) - 1;
+    *p_first = base / per_poly;
+    const size_t count = last / per_poly - *p_first + 1;  // <= blockDim.x: an item belongs to one polynomial
+    if (threadIdx.x < count) refs[threadIdx.x] = rng_block_of(table, *p_first + threadIdx.x);
+    __syncthreads();
+    return true;
+}
+
+template <typename W>
+__global__ void __launch_bounds__(256) sample_uniform_blocks_kernel(W *__restrict__ out, const LimbConst *__restrict__ limbs, RngBlockTable table,
+                                                                    size_t polys, uint32_t L, uint32_t N, uint32_t groups /* ceil(N / 8) */) {
+    __shared__ RngBlockRef refs[256];
+    const size_t total = polys * L * groups;
+    size_t p_first;
+    if (!resolve_blocks(table, total, static_cast<size_t>(L) * groups, refs, &p_first)) return;
+    const size_t idx = item_index();
+    if (idx >= total) return;
+    const size_t vec = idx / groups;  // (polynomial, limb) vector
+    const uint32_t g = static_cast<uint32_t>(idx - vec * groups);
+    const size_t p = vec / L;
+    const uint32_t l = static_cast<uint32_t>(vec - p * L);
+    const RngBlockRef ref = refs[p - p_first];
+    const ChaChaKey key = load_key(table.keys + static_cast<size_t>(ref.blk) * L, l);
+    const uint64_t q = limbs[l].q, mu64 = limbs[l].mu64;
+    const uint64_t threshold = mu64 * q;  // as in sample_uniform_kernel
+    uint64_t w[8];
+    chacha_block_words(key, ref.local + 1, 0, g, w);
+    const uint32_t count = min(8u, N - g * 8u);
+    W r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        uint64_t x = w[j];
+        if (x >= threshold && static_cast<uint32_t>(j) < count) x = uniform_overflow_draw(key, ref.local + 1, static_cast<uint64_t>(g) * 8u + j + 1, threshold);
+        uint64_t rem = x - __umul64hi(x, mu64) * q;
+        rem = rem >= q ? rem - q : rem;
+        r[j] = static_cast<W>(rem);
+    }
+    store_group<W, 1>(out + vec * N + static_cast<size_t>(g) * 8u, r, count);
+}
+
+template <typename W>
+__global__ void __launch_bounds__(256) sample_small_blocks_kernel(W *__restrict__ out, const LimbConst *__restrict__ limbs, RngBlockTable table,
+                                                                  size_t polys, uint32_t L, uint32_t N, uint32_t groups, int dist) {
+    __shared__ RngBlockRef refs[256];
+    const size_t total = polys * groups;
+    size_t p_first;
+    if (!resolve_blocks(table, total, groups, refs, &p_first)) return;
+    const size_t idx = item_index();
+    if (idx >= total) return;
+    const size_t p = idx / groups;
+    const uint32_t g = static_cast<uint32_t>(idx - p * groups);
+    const RngBlockRef ref = refs[p - p_first];
+    const ChaChaKey key = load_key(table.keys + ref.blk, 0);
+    uint64_t w[8];
+    chacha_block_words(key, ref.local + 1, 0, g, w);
+    const uint32_t count = min(8u, N - g * 8u);
+    int32_t z[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (dist == GPU_MATRIX_DIST_BIT) {
+            z[j] = static_cast<int32_t>(w[j] & 1ull);
+        } else {
+            const uint32_t pick = static_cast<uint32_t>(w[j] % 3ull);
+            z[j] = pick == 0 ? 0 : (pick == 1 ? 1 : -1);
+        }
+    }
+    for (uint32_t l = 0; l < L; ++l) {
+        const W q = static_cast<W>(limbs[l].q);
+        W r[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = z[j] < 0 ? q - 1 : static_cast<W>(z[j]);
+        store_group<W, 1>(out + (p * L + l) * N + static_cast<size_t>(g) * 8u, r, count);
+    }
+}
+
+extern "C" int gpupoly_matrix_sample_distribution_blocks(GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, size_t nblk, int layout,
+                                                         const size_t *seg_cols) {
+    ABI_GUARD_BEGIN
+    constexpr size_t kMaxBlocks = size_t(1) << 20, kStreamLimit = size_t(1) << 48;
+    if (!out) return set_error("gpupoly_matrix_sample_distribution_blocks: null matrix");
+    if (!seeds) return set_error("gpupoly_matrix_sample_distribution_blocks: null seeds");
+    if (nblk == 0 || nblk > kMaxBlocks) return set_error("gpupoly_matrix_sample_distribution_blocks: the block count must be 1..2^20");
+    if (layout != GPUPOLY_BLOCKS_STACKED && layout != GPUPOLY_BLOCKS_COLUMNS)
+        return set_error("gpupoly_matrix_sample_distribution_blocks: unknown layout");
+    if (dist_type == GPU_MATRIX_DIST_GAUSS)
+        return set_error("gpupoly_matrix_sample_distribution_blocks: unsupported: the Gaussian distribution goes through "
+                         "gpupoly_matrix_sample_distribution_segments");
+    if (dist_type < GPU_MATRIX_DIST_UNIFORM || dist_type > GPU_MATRIX_DIST_TERNARY)
+        return set_error("gpupoly_matrix_sample_distribution_blocks: invalid dist_type");
+    GpuContext *ctx = out->ctx;
+    if (ctx->env.rng_compat)
+        return set_error("gpupoly_matrix_sample_distribution_blocks: unsupported under MXX_HIP_RNG_COMPAT=reference");
+    const bool columns = layout == GPUPOLY_BLOCKS_COLUMNS;
+    if (!columns) {
+        if (seg_cols) return set_error("gpupoly_matrix_sample_distribution_blocks: the stacked layout takes no seg_cols");
+        if (out->rows != nblk) return set_error("gpupoly_matrix_sample_distribution_blocks: the stacked layout wants one row per block");
+        if (out->cols >= kStreamLimit)
+            return set_error("gpupoly_matrix_sample_distribution_blocks: block too large for the RNG's 48-bit stream ids");
+    } else {
+        if (!seg_cols) return set_error("gpupoly_matrix_sample_distribution_blocks: the columns layout needs seg_cols");
+        size_t at = 0, placed = 0;  // at <= out->cols
+        for (size_t j = 0; j < nblk; ++j) {
+            const size_t w = seg_cols[j];
+            if (w == 0) return set_error("gpupoly_matrix_sample_distribution_blocks: a block of zero columns");
+            if (out->rows && w > (kStreamLimit - 1) / out->rows)
+                return set_error("gpupoly_matrix_sample_distribution_blocks: block too large for the RNG's 48-bit stream ids");
+            if (w > out->cols - at) break;
+            at += w;
+            ++placed;
+        }
+        if (placed != nblk || at != out->cols)
+            return set_error("gpupoly_matrix_sample_distribution_blocks: the blocks' widths must sum to the matrix's columns");
+    }
+    const size_t polys = matrix_polys(out);
+    if (polys == 0) {
+        out->format = GPU_POLY_FORMAT_EVAL;
+        return 0;
+    }
+    if (ctx_activate(ctx)) return 1;
+    const bool uniform = dist_type == GPU_MATRIX_DIST_UNIFORM;
+    const uint32_t L = static_cast<uint32_t>(matrix_limbs(out)), N = static_cast<uint32_t>(ctx->N), groups = (N + 7) / 8;
+    const uint32_t per_block = uniform ? L : 1u;
+    // the table: [keys][seeds][starts]; seeds and starts go up in one copy out of a staging vector of this thread (the
+    // caller's arrays are not read after this call returns), the keys are derived from the seeds on the device
+    const size_t key_bytes = sizeof(ChaChaKey) * nblk * per_block, seed_words = 4 * nblk, start_words = columns ? nblk + 1 : 0;
+    CtxBlock block(ctx);
+    if (block.alloc(key_bytes + sizeof(uint64_t) * (seed_words + start_words))) return 1;
+    static thread_local std::vector<uint64_t> staging;
+    staging.resize(seed_words + start_words);
+    for (size_t j = 0; j < nblk; ++j)
+        for (int i = 0; i < 4; ++i) staging[4 * j + i] = seeds[j].words[i];
+    if (columns) {
+        uint64_t at = 0;
+        for (size_t j = 0; j < nblk; ++j) {
+            staging[seed_words + j] = at;
+            at += seg_cols[j];
+        }
+        staging[seed_words + nblk] = at;
+    }
+    char *base = static_cast<char *>(block.ptr);
+    ChaChaKey *d_keys = reinterpret_cast<ChaChaKey *>(base);
+    const GpuRngSeed *d_seeds = reinterpret_cast<const GpuRngSeed *>(base + key_bytes);
+    const uint64_t *d_starts = reinterpret_cast<const uint64_t *>(base + key_bytes) + seed_words;
+    void *words = words_ptr(out);
+    MXX_TRACED_COPY("seeded block table (host to device)", ctx->stream, sizeof(uint64_t) * staging.size(),
+                    HIP_TRY(hipMemcpyAsync(base + key_bytes, staging.data(), sizeof(uint64_t) * staging.size(), hipMemcpyHostToDevice, ctx->stream)));
+    const uint64_t tag = uniform ? kTagUniform : (dist_type == GPU_MATRIX_DIST_BIT ? kTagBit : kTagTernary);
+    MXX_LAUNCH(derive_block_subkeys_kernel, item_grid(nblk * per_block, 256), dim3(256), 0, ctx->stream, d_keys, d_seeds, tag, nblk, per_block,
+               uniform ? 1u : 0u);
+    HIP_TRY(hipGetLastError());
+    out->format = GPU_POLY_FORMAT_EVAL;
+    const RngBlockTable table{d_keys, columns ? d_starts : nullptr, out->cols, static_cast<uint32_t>(nblk), per_block};
+    const size_t threads = polys * per_block * groups;
+    const dim3 blocks = item_grid(threads, 256);
+    MXX_TRACE_BYTES(static_cast<double>(out->bytes));  // no input to speak of: the residues written once
+    if (uniform) {
+        if (ctx->wide)
+            MXX_LAUNCH(sample_uniform_blocks_kernel<uint64_t>, blocks, dim3(256), 0, ctx->stream, static_cast<uint64_t *>(words), ctx->d_limbs, table, polys, L, N, groups);
+        else
+            MXX_LAUNCH(sample_uniform_blocks_kernel<uint32_t>, blocks, dim3(256), 0, ctx->stream, static_cast<uint32_t *>(words), ctx->d_limbs, table, polys, L, N, groups);
+    } else {
+        if (ctx->wide)
+            MXX_LAUNCH(sample_small_blocks_kernel<uint64_t>, blocks, dim3(256), 0, ctx->stream, static_cast<uint64_t *>(words), ctx->d_limbs, table, polys, L, N, groups, dist_type);
+        else
+            MXX_LAUNCH(sample_small_blocks_kernel<uint32_t>, blocks, dim3(256), 0, ctx->stream, static_cast<uint32_t *>(words), ctx->d_limbs, table, polys, L, N, groups, dist_type);
+    }
+    HIP_TRY(hipGetLastError());
+    // as the plain entry finishes: samples are coefficients, callers get EVAL; a packable uniform sample is stored packed
+    if (uniform && pack24_eligible(out)) return pack24_store(out, true);
+    return launch_ntt(ctx, words, polys * L, static_cast<int>(L), false);
+    ABI_GUARD_END
+}
+
 // ---- detmath.h where it runs (extension, test instrument) ------------------------------------------------------
 // Box-Muller's log / cos(2 pi u) are fixed IEEE operation sequences compiled into the device code; this entry evaluates
 // them ON THE DEVICE for caller-supplied arguments so that a test can compare them with libm / extended precision

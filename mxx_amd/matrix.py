@@ -1144,6 +1144,20 @@ class GpuDCRTPolyMatrix:
         v._finalizer = weakref.finalize(v, _ffi.lib().gpu_matrix_destroy, raw)
         return v
 
+    def reshape_view(self, nrow, ncol) -> "GpuDCRTPolyMatrix":
+        """The whole matrix as nrow x ncol (nrow * ncol polynomials, as here) over the same storage, entry (i, j) =
+        polynomial i * ncol + j of the row-major order (gpupoly_matrix_reshape_view): no copy.  A row view in every
+        other respect - it keeps its parent alive, writes through either are seen by both, and the overlap rule treats
+        it as the parent's block.  Another polynomial count raises GpuPolyError."""
+        raw = C.c_void_p()
+        check_status(_ffi.lib().gpupoly_matrix_reshape_view(self.raw, nrow, ncol, C.byref(raw)), "gpupoly_matrix_reshape_view")
+        v = object.__new__(GpuDCRTPolyMatrix)
+        v.params, v.nrow, v.ncol, v.level, v.is_ntt, v.raw = self.params, nrow, ncol, self.level, self.is_ntt, raw
+        v._parent = self
+        v._version = 0
+        v._finalizer = weakref.finalize(v, _ffi.lib().gpu_matrix_destroy, raw)
+        return v
+
     def ntt_add_rows_from(self, dst_row, coeff, addend, consume: bool = False) -> None:
         """self[dst_row : dst_row + coeff.nrow] = NTT(coeff) + addend (gpupoly_matrix_ntt_add_rows): `coeff` holds
         coefficients, `addend` is EVAL; one pass where the fused kernel exists.  consume: the caller gives `coeff` up
@@ -2026,6 +2040,32 @@ class GpuDCRTPolyMatrix:
         arr, cols, n = cls._segment_args(seeds, seg_cols)
         check_status(_ffi.lib().gpupoly_matrix_sample_distribution_segments(out.raw, dist, sigma, arr, cols, n),
                      "gpupoly_matrix_sample_distribution_segments")
+        return out
+
+    @classmethod
+    def sample_distribution_blocks(cls, params, seeds, dist: int, *, block_polys=None, nrow=None, seg_cols=None) -> "GpuDCRTPolyMatrix":
+        """Uniform / bit / ternary samples of len(seeds) independently seeded blocks in one call
+        (gpupoly_matrix_sample_distribution_blocks), any number of blocks up to 2^20, the launches not depending on it.
+        Stacked layout, `block_polys=P`: the len(seeds) x P matrix whose row t holds the P polynomials of
+        `sample_distribution(params, r, c, dist, 0, seeds[t])`, r * c == P, in row-major order.
+        Columns layout, `nrow=r, seg_cols=[c_0, ...]`: [S_0 | S_1 | ...] with S_j == sample_distribution(params, r, c_j,
+        dist, 0, seeds[j]).  Raises GpuPolyError (text contains "unsupported") for the
+        Gaussian distribution - `sample_distribution_segments` is its entry - and under MXX_HIP_RNG_COMPAT=reference."""
+        seeds = list(seeds)
+        level = params.crt_depth() - 1
+        arr = (GpuRngSeed * max(len(seeds), 1))(*seeds)
+        if seg_cols is None:
+            assert block_polys is not None and nrow is None, "sample_distribution_blocks: block_polys (stacked) or nrow and seg_cols (columns)"
+            out = cls(params, len(seeds), block_polys, level, True)
+            layout, cols = _ffi.GPUPOLY_BLOCKS_STACKED, None
+        else:
+            assert block_polys is None and nrow is not None, "sample_distribution_blocks: block_polys (stacked) or nrow and seg_cols (columns)"
+            seg_cols = list(seg_cols)
+            assert len(seg_cols) == len(seeds), "sample_distribution_blocks: one seed per block"
+            out = cls(params, nrow, sum(seg_cols), level, True)
+            layout, cols = _ffi.GPUPOLY_BLOCKS_COLUMNS, (C.c_size_t * max(len(seg_cols), 1))(*seg_cols)
+        check_status(_ffi.lib().gpupoly_matrix_sample_distribution_blocks(out.raw, dist, arr, len(seeds), layout, cols),
+                     "gpupoly_matrix_sample_distribution_blocks")
         return out
 
     @staticmethod

@@ -197,3 +197,104 @@ class GpuDCRTPolyHashSampler:
         seed = hash_seed_for_matrix(key, tag, self.hash_name)
         return GpuDCRTPolyMatrix.sample_distribution_decomposed_window(
             params, nrow, total_ncol, col_start, col_len, dist.as_ffi(), dist.sigma, seed, True, row_start, row_end)
+
+    # ---- many tags in one call (gpupoly_matrix_sample_distribution_blocks) ----------------------
+    def _seeds(self, key, tags):
+        return [hash_seed_for_matrix(key, tag, self.hash_name) for tag in tags]
+
+    def sample_hash_many(self, params, key: bytes, tags, nrow, ncol, dist: DistType) -> list:
+        """== [sample_hash(params, key, tag, nrow, ncol, dist) for tag in tags] - the tagged loops of
+        src/commit/wee25.rs:687-703, src/lookup/ggh15/pubkey_gpu.rs:924,1296 and src/lookup/lwe/pubkey_gpu.rs:559,616 -
+        with one columns-layout sample and one split_columns per 64 tags instead of a sample per tag (Gaussian requests
+        through the Gaussian segments).  Where the library answers "unsupported" (MXX_HIP_RNG_COMPAT=reference, rings the
+        Gaussian segments do not cover) the tags are sampled one by one: the same matrices either way."""
+        tags = list(tags)
+        if nrow == 0 or ncol == 0:
+            return [GpuDCRTPolyMatrix.zero(params, nrow, ncol) for _ in tags]
+        seeds = self._seeds(key, tags)
+        outs = []
+        for lo in range(0, len(tags), 64):
+            chunk = seeds[lo : lo + 64]
+            widths = [ncol] * len(chunk)
+            try:
+                if dist.kind == "gauss":
+                    wide = GpuDCRTPolyMatrix.sample_distribution_segments(params, nrow, widths, dist.as_ffi(), dist.sigma, chunk)
+                else:
+                    wide = GpuDCRTPolyMatrix.sample_distribution_blocks(params, chunk, dist.as_ffi(), nrow=nrow, seg_cols=widths)
+            except _ffi.GpuPolyError as e:
+                if "unsupported" not in str(e):
+                    raise
+                outs.extend(sample_gpu_matrix_with_seed(params, nrow, ncol, dist, s) for s in chunk)
+                continue
+            outs.extend(wide.split_columns(widths))
+        return outs
+
+    def sample_hash_stacked(self, params, key: bytes, tags, nrow, ncol, dist: DistType) -> GpuDCRTPolyMatrix:
+        """The len(tags) x (nrow * ncol) matrix whose row t is sample_hash(params, key, tags[t], nrow, ncol, dist) in
+        row-major order, sampled in one stacked-layout call; where the library answers "unsupported" (the Gaussian
+        distribution, MXX_HIP_RNG_COMPAT=reference) the rows are sampled one by one and copied in."""
+        tags = list(tags)
+        seeds = self._seeds(key, tags)
+        polys = nrow * ncol
+        if not tags or polys == 0:
+            return GpuDCRTPolyMatrix.zero(params, len(tags), polys)
+        try:
+            return GpuDCRTPolyMatrix.sample_distribution_blocks(params, seeds, dist.as_ffi(), block_polys=polys)
+        except _ffi.GpuPolyError as e:
+            if "unsupported" not in str(e):
+                raise
+        out = GpuDCRTPolyMatrix.new_empty(params, len(tags), polys)
+        for t, seed in enumerate(seeds):
+            block = sample_gpu_matrix_with_seed(params, nrow, ncol, dist, seed)
+            out.copy_block_from(block.reshape_view(1, polys), t, 0, 0, 0, 1, polys)
+        return out
+
+    def sample_hash_weighted_sum(self, params, key: bytes, tags, weights, nrow, ncol, addend=None, negate: bool = False,
+                                 max_stack_bytes: int = 1 << 30) -> GpuDCRTPolyMatrix:
+        """addend +- sum_t sample_hash(params, key, tags[t], nrow, ncol, FinRingDist) o weights[0, t]: every sampled
+        nrow x ncol matrix multiplied by one polynomial and summed.  `weights` is a 1 x len(tags) EVAL matrix, `addend`
+        None or an nrow x ncol EVAL matrix (left as it is).
+
+        This is `commit_base` of src/commit/wee25.rs:858-883, `acc += sample_hash(tag(j * m_g + r)) * a_{j,r}` over the
+        columns j of the message and the digit rows r of G^-1(msg[:, j]), in three calls:
+            D = msg.decompose()                                          # m_g x cols
+            weights = D.transpose().reshape_view(1, cols * m_g)          # a_{j,r} at column j * m_g + r
+            sampler.sample_hash_weighted_sum(params, key, tags, weights, secret_size, m_b)
+        The tags' matrices are sampled straight into one stacked T x (nrow * ncol) matrix (sample_hash_stacked), so the
+        sum is the one-row product weights * stack - the shape the packed skinny kernel streams at 3 bytes per residue
+        where the moduli fit - instead of a sample, a scalar product, an addition and a temporary per term.  The tags go
+        in chunks whose stack stays within max_stack_bytes (in 4- or 8-byte words; at least one tag per chunk): per chunk
+        one stacked sample, one product, one accumulation into a 1 x (nrow * ncol) row.  The result is that row seen as
+        nrow x ncol (reshape_view): no copy."""
+        tags = list(tags)
+        polys = nrow * ncol
+        assert weights.is_ntt and (weights.nrow, weights.ncol) == (1, len(tags)), "sample_hash_weighted_sum: weights is a 1 x len(tags) EVAL matrix"
+        if addend is not None:
+            assert addend.is_ntt and (addend.nrow, addend.ncol) == (nrow, ncol) and addend.level == weights.level, \
+                "sample_hash_weighted_sum: the addend is an nrow x ncol EVAL matrix at the weights' level"
+        assert weights.level == params.crt_depth() - 1, "sample_hash_weighted_sum: full level"
+        acc = None if addend is None else addend.reshape_view(1, polys)
+        own = False  # acc is still the caller's addend: read only, the first sum goes into a fresh row
+        if polys:
+            poly_bytes = (weights.level + 1) * params.ring_dimension() * params.ctx().word_bytes()
+            step = max(1, int(max_stack_bytes) // (polys * poly_bytes))
+            dist = DistType.FinRingDist()
+            for lo in range(0, len(tags), step):
+                hi = min(lo + step, len(tags))
+                stack = self.sample_hash_stacked(params, key, tags[lo:hi], nrow, ncol, dist)
+                w = weights if (lo, hi) == (0, len(tags)) else weights.slice_columns(lo, hi)
+                term = w * stack  # 1 x polys; a packed stack is read as it lies
+                if acc is None:
+                    acc = -term if negate else term
+                elif not own:
+                    acc = acc - term if negate else acc + term
+                elif negate:
+                    acc.sub_in_place(term)
+                else:
+                    acc.add_in_place(term)
+                own = True
+        if acc is None:
+            acc = GpuDCRTPolyMatrix.zero(params, 1, polys)
+        elif not own:  # no term: the result must not share the addend's storage
+            acc = acc.clone()
+        return acc.reshape_view(nrow, ncol)
