@@ -415,11 +415,63 @@ int gpupoly_matrix_gauss_samp_gq_arb_base_segments(GpuMatrix *src, uint32_t base
  * a null seg_cols, a zero width or widths that do not sum to out->cols; an invalid dist_type; a block of 2^48
  * polynomials or more (the 48-bit stream ids).  Refused likewise with an error containing "unsupported": the Gaussian
  * distribution (gpupoly_matrix_sample_distribution_segments is its entry); a context created under
- * MXX_HIP_RNG_COMPAT=reference (issue the requests one by one).                                                   */
+ * MXX_HIP_RNG_COMPAT=reference (issue the requests one by one).
+ * gpupoly_matrix_sample_hash_blocks is this entry with the seeds hashed from (key, tags) on the device.          */
 #define GPUPOLY_BLOCKS_STACKED 0
 #define GPUPOLY_BLOCKS_COLUMNS 1
 int gpupoly_matrix_sample_distribution_blocks(GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, size_t nblk,
                                               int layout, const size_t *seg_cols);
+/* ---- tags to seeds on the device (extension).  The tagged loops above begin on the host with one hash
+ * per tag: hash_seed_for_matrix (src/sampler/gpu.rs:118-136) is H("GpuDCRTPolyHashSampler/v2" || key || tag || ctr_le32),
+ * H = Keccak-256 (the original 0x01 padding) in every instantiation of the reference, its 32-byte digest read as four
+ * little-endian words (GpuRngSeed::from_bytes); the counter loop runs once, with counter 0.  A GpuHashTags names the hash,
+ * the 32-byte key and the tags t = 0 .. count - 1 (the count is the entry's argument) in one of three forms:
+ *   GPUPOLY_TAGS_TABLE            tag t = tags[tag_offsets[t] .. tag_offsets[t + 1]): any bytes, any lengths, empty tags
+ *                                 included; tag_offsets has count + 1 entries, starts at 0 and does not decrease.  `tags`
+ *                                 may be NULL when every tag is empty.  Bytes and offsets go up in one staged copy and are
+ *                                 not read after the call returns.
+ *   GPUPOLY_TAGS_INDEXED_LE64     tag t = tags[0 .. prefix_len) || (first_index + t) as 8 little-endian bytes: the
+ *                                 b"wee25_w_block_" || idx.to_le_bytes() of src/commit/wee25.rs:687-703,858-883.
+ *   GPUPOLY_TAGS_INDEXED_DECIMAL  tag t = the prefix || first_index + t in ASCII decimal without leading zeros (1 to 20
+ *                                 digits): the format!("ggh15_lut_v_idx_{}_{}", lut_id, idx) of
+ *                                 src/lookup/ggh15/pubkey_gpu.rs:398-401,924,1296 and src/lookup/lwe/pubkey_gpu.rs:559,616
+ *                                 with "ggh15_lut_v_idx_<lut_id>_" as the prefix.
+ * In the indexed forms prefix_len is at most 64, tag_offsets is NULL, first_index + count - 1 must not wrap, the prefix
+ * travels by value with the launch and the tags are generated on the device: O(1) host work, nothing uploaded.       */
+#define GPUPOLY_HASH_KECCAK256 0 /* padding byte 0x01: keccak_asm::Keccak256 */
+#define GPUPOLY_HASH_SHA3_256 1  /* padding byte 0x06: FIPS 202 */
+#define GPUPOLY_TAGS_TABLE 0
+#define GPUPOLY_TAGS_INDEXED_LE64 1
+#define GPUPOLY_TAGS_INDEXED_DECIMAL 2
+typedef struct GpuHashTags {
+    int hash; /* GPUPOLY_HASH_* */
+    int form; /* GPUPOLY_TAGS_* */
+    uint8_t key[32];
+    const uint8_t *tags;       /* TABLE: the packed tag bytes; INDEXED: the prefix */
+    const size_t *tag_offsets; /* TABLE only */
+    size_t prefix_len;         /* INDEXED only */
+    uint64_t first_index;      /* INDEXED only */
+} GpuHashTags;
+/* seeds_out[t] = hash_seed_for_matrix(key, tag_t) for t < ntags (1..2^20), one device lane per tag; blocks until the
+ * seeds are in host memory.  The entry behind the mirror's single-tag calls, and the instrument the tests read the device
+ * hash with.  No state of the context is involved: any context of a device gives the same seeds.
+ * Refused, the message naming this entry and nothing launched: a null ctx, tags or seeds_out; ntags == 0 or above 2^20;
+ * an unknown hash or form; TABLE with a null tag_offsets, tag_offsets[0] != 0, decreasing offsets, or null tags unless all
+ * tags are empty; INDEXED with prefix_len > 64, a null prefix of non-zero length, a non-null tag_offsets or a wrapping
+ * index range.                                                                                                     */
+int gpupoly_hash_seeds(GpuContext *ctx, const GpuHashTags *tags, size_t ntags, GpuRngSeed *seeds_out);
+/* gpupoly_matrix_sample_distribution_blocks with seeds[t] = hash_seed_for_matrix(key, tag_t), t < nblk, derived on the
+ * device by one launch in front of the same key-derivation, sampling and transform / pack launches: the seeds never exist
+ * on the host.  `out` ends bit for bit as that entry leaves it for the host-derived seeds (same tag, same level, same
+ * PACKED24 rule); layout and seg_cols mean what they mean there.  In the TABLE form tag bytes, offsets and the columns
+ * layout's starts go up in one staged copy; in the indexed forms only the columns layout's starts go up, the stacked layout
+ * copies nothing.  Enqueued on the context's stream; the host does not block.
+ * Overlap: the only matrix is `out`; nothing can overlap.
+ * Refused, with nothing launched and `out` (contents AND tag) untouched, the message naming this entry: everything
+ * gpupoly_matrix_sample_distribution_blocks refuses (the Gaussian distribution and MXX_HIP_RNG_COMPAT=reference with
+ * "unsupported") and everything gpupoly_hash_seeds refuses of `tags`.                                                 */
+int gpupoly_matrix_sample_hash_blocks(GpuMatrix *out, int dist_type, const GpuHashTags *tags, size_t nblk, int layout,
+                                      const size_t *seg_cols);
 /* out = [blocks[0] | blocks[1] | ...] / blocks[j] = the next blocks[j]->cols columns of src, in one launch per 64
  * blocks (the wrapper's concat_columns / slice_columns are a gpu_matrix_copy_block launch per block,
  * src/matrix/gpu_dcrt_poly.rs:1216-1260).  Same rows, level and context everywhere; the written side takes the read

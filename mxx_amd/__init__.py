@@ -34,6 +34,7 @@ from .sampler import (  # noqa: F401
     DistType,
     GpuDCRTPolyHashSampler,
     GpuDCRTPolyUniformSampler,
+    IndexedTags,
     hash_seed_for_matrix,
     keccak256,
     random_gpu_rng_seed,

@@ -22,6 +22,11 @@ GPU_MATRIX_DIST_BIT = 2
 GPU_MATRIX_DIST_TERNARY = 3
 GPUPOLY_BLOCKS_STACKED = 0
 GPUPOLY_BLOCKS_COLUMNS = 1
+GPUPOLY_HASH_KECCAK256 = 0
+GPUPOLY_HASH_SHA3_256 = 1
+GPUPOLY_TAGS_TABLE = 0
+GPUPOLY_TAGS_INDEXED_LE64 = 1
+GPUPOLY_TAGS_INDEXED_DECIMAL = 2
 
 
 class GpuPolyError(RuntimeError):
@@ -44,6 +49,13 @@ class GpuRngSeed(C.Structure):
 
     def to_bytes(self) -> bytes:
         return b"".join(int(w).to_bytes(8, "little") for w in self.words)
+
+
+class GpuHashTags(C.Structure):
+    """`struct GpuHashTags` (include/gpupoly.h): hash, key and the tags of a device-side hash_seed_for_matrix."""
+
+    _fields_ = [("hash", C.c_int), ("form", C.c_int), ("key", C.c_uint8 * 32), ("tags", C.c_void_p),
+                ("tag_offsets", C.POINTER(C.c_size_t)), ("prefix_len", C.c_size_t), ("first_index", C.c_uint64)]
 
 
 class GpuBatchOp(C.Structure):
@@ -142,6 +154,8 @@ SIGNATURES = {
     "gpupoly_matrix_all_gather_columns": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "gpupoly_matrix_sample_distribution_segments": (C.c_int, [_vp, C.c_int, C.c_double, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz]),
     "gpupoly_matrix_sample_distribution_blocks": (C.c_int, [_vp, C.c_int, C.POINTER(GpuRngSeed), _sz, C.c_int, C.POINTER(_sz)]),
+    "gpupoly_hash_seeds": (C.c_int, [_vp, C.POINTER(GpuHashTags), _sz, C.POINTER(GpuRngSeed)]),
+    "gpupoly_matrix_sample_hash_blocks": (C.c_int, [_vp, C.c_int, C.POINTER(GpuHashTags), _sz, C.c_int, C.POINTER(_sz)]),
     "gpupoly_matrix_sample_p1_full_cached_segments":(C.c_int, [_vp, _vp, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz, _vp]),
     "gpupoly_matrix_gauss_samp_gq_arb_base_segments": (C.c_int, [_vp, C.c_uint32, C.c_double, C.c_double, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz, _vp]),
     "gpupoly_matrix_concat_columns": (C.c_int, [_vp, C.POINTER(C.c_void_p), _sz]),

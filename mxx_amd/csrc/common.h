@@ -325,6 +325,14 @@ int pack24_store(GpuMatrix *m, bool ntt);
 int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t full_ncol, size_t col_offset, bool keep_coeff,
                 size_t row_offset = 0, uint32_t tower_first = 0, uint32_t tower_count = 0);
 
+// hash_seed.hip: tags to seeds on the device.  hash_tags_check refuses a malformed GpuHashTags in `entry`'s name and tells
+// the TABLE form's byte count; the TABLE form's offsets and bytes are staged as hash_tags_staged_words 8-byte words (none in
+// the indexed forms) which the caller copies to `d_staged` on the stream before launch_hash_seeds writes d_seeds[0 .. ntags)
+int hash_tags_check(const char *entry, const GpuHashTags *tags, size_t ntags, size_t *table_bytes);
+size_t hash_tags_staged_words(const GpuHashTags *tags, size_t ntags, size_t table_bytes);
+void hash_tags_stage(const GpuHashTags *tags, size_t ntags, size_t table_bytes, uint64_t *staging);
+int launch_hash_seeds(GpuContext *ctx, GpuRngSeed *d_seeds, const GpuHashTags *tags, size_t ntags, const uint64_t *d_staged);
+
 int ctx_activate(const GpuContext *ctx);                   // hipSetDevice
 bool ctx_is_registered(const GpuContext *ctx);             // still a live context of this process (runtime.hip's registry)
 int ctx_alloc(GpuContext *ctx, size_t bytes, void **out);  // stream-ordered

@@ -639,44 +639,43 @@ __global__ void __launch_bounds__(256) sample_small_blocks_kernel(W *__restrict_
     }
 }
 
-extern "C" int gpupoly_matrix_sample_distribution_blocks(GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, size_t nblk, int layout,
-                                                         const size_t *seg_cols) {
-    ABI_GUARD_BEGIN
+// Both block entries: the argument checks in `entry`'s name, then the table, the launches and the finish.  The seeds of
+// the table come either from the caller (`seeds`: staged and copied with the starts) or from (key, tags) on the device
+// (`tags`: hash_seeds_kernel writes them, hash_seed.hip; the TABLE form's offsets and bytes are staged with the starts,
+// the indexed forms stage nothing).  `hashed` says which of the two the entry takes; the other is null.
+static int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, const GpuHashTags *tags,
+                              size_t nblk, int layout, const size_t *seg_cols) {
     constexpr size_t kMaxBlocks = size_t(1) << 20, kStreamLimit = size_t(1) << 48;
-    if (!out) return set_error("gpupoly_matrix_sample_distribution_blocks: null matrix");
-    if (!seeds) return set_error("gpupoly_matrix_sample_distribution_blocks: null seeds");
-    if (nblk == 0 || nblk > kMaxBlocks) return set_error("gpupoly_matrix_sample_distribution_blocks: the block count must be 1..2^20");
-    if (layout != GPUPOLY_BLOCKS_STACKED && layout != GPUPOLY_BLOCKS_COLUMNS)
-        return set_error("gpupoly_matrix_sample_distribution_blocks: unknown layout");
+    const auto refuse = [entry](const char *what) { return set_error(std::string(entry) + what); };
+    if (!out) return refuse(": null matrix");
+    if (!seeds && !tags) return refuse(hashed ? ": null tags" : ": null seeds");
+    if (nblk == 0 || nblk > kMaxBlocks) return refuse(": the block count must be 1..2^20");
+    if (layout != GPUPOLY_BLOCKS_STACKED && layout != GPUPOLY_BLOCKS_COLUMNS) return refuse(": unknown layout");
     if (dist_type == GPU_MATRIX_DIST_GAUSS)
-        return set_error("gpupoly_matrix_sample_distribution_blocks: unsupported: the Gaussian distribution goes through "
-                         "gpupoly_matrix_sample_distribution_segments");
-    if (dist_type < GPU_MATRIX_DIST_UNIFORM || dist_type > GPU_MATRIX_DIST_TERNARY)
-        return set_error("gpupoly_matrix_sample_distribution_blocks: invalid dist_type");
+        return refuse(": unsupported: the Gaussian distribution goes through gpupoly_matrix_sample_distribution_segments");
+    if (dist_type < GPU_MATRIX_DIST_UNIFORM || dist_type > GPU_MATRIX_DIST_TERNARY) return refuse(": invalid dist_type");
     GpuContext *ctx = out->ctx;
-    if (ctx->env.rng_compat)
-        return set_error("gpupoly_matrix_sample_distribution_blocks: unsupported under MXX_HIP_RNG_COMPAT=reference");
+    if (ctx->env.rng_compat) return refuse(": unsupported under MXX_HIP_RNG_COMPAT=reference");
     const bool columns = layout == GPUPOLY_BLOCKS_COLUMNS;
     if (!columns) {
-        if (seg_cols) return set_error("gpupoly_matrix_sample_distribution_blocks: the stacked layout takes no seg_cols");
-        if (out->rows != nblk) return set_error("gpupoly_matrix_sample_distribution_blocks: the stacked layout wants one row per block");
-        if (out->cols >= kStreamLimit)
-            return set_error("gpupoly_matrix_sample_distribution_blocks: block too large for the RNG's 48-bit stream ids");
+        if (seg_cols) return refuse(": the stacked layout takes no seg_cols");
+        if (out->rows != nblk) return refuse(": the stacked layout wants one row per block");
+        if (out->cols >= kStreamLimit) return refuse(": block too large for the RNG's 48-bit stream ids");
     } else {
-        if (!seg_cols) return set_error("gpupoly_matrix_sample_distribution_blocks: the columns layout needs seg_cols");
+        if (!seg_cols) return refuse(": the columns layout needs seg_cols");
         size_t at = 0, placed = 0;  // at <= out->cols
         for (size_t j = 0; j < nblk; ++j) {
             const size_t w = seg_cols[j];
-            if (w == 0) return set_error("gpupoly_matrix_sample_distribution_blocks: a block of zero columns");
-            if (out->rows && w > (kStreamLimit - 1) / out->rows)
-                return set_error("gpupoly_matrix_sample_distribution_blocks: block too large for the RNG's 48-bit stream ids");
+            if (w == 0) return refuse(": a block of zero columns");
+            if (out->rows && w > (kStreamLimit - 1) / out->rows) return refuse(": block too large for the RNG's 48-bit stream ids");
             if (w > out->cols - at) break;
             at += w;
             ++placed;
         }
-        if (placed != nblk || at != out->cols)
-            return set_error("gpupoly_matrix_sample_distribution_blocks: the blocks' widths must sum to the matrix's columns");
+        if (placed != nblk || at != out->cols) return refuse(": the blocks' widths must sum to the matrix's columns");
     }
+    size_t tag_bytes = 0;
+    if (tags && hash_tags_check(entry, tags, nblk, &tag_bytes)) return 1;
     const size_t polys = matrix_polys(out);
     if (polys == 0) {
         out->format = GPU_POLY_FORMAT_EVAL;
@@ -686,30 +685,39 @@ extern "C" int gpupoly_matrix_sample_distribution_blocks(GpuMatrix *out, int dis
     const bool uniform = dist_type == GPU_MATRIX_DIST_UNIFORM;
     const uint32_t L = static_cast<uint32_t>(matrix_limbs(out)), N = static_cast<uint32_t>(ctx->N), groups = (N + 7) / 8;
     const uint32_t per_block = uniform ? L : 1u;
-    // the table: [keys][seeds][starts]; seeds and starts go up in one copy out of a staging vector of this thread (the
-    // caller's arrays are not read after this call returns), the keys are derived from the seeds on the device
+    // the table: [keys][seeds][starts][tag offsets and bytes]; what the host knows of it goes up in one copy out of a staging
+    // vector of this thread (the caller's arrays are not read after this call returns) - seeds and starts, or starts and
+    // tags, in which case the seeds are hashed on the device -, the keys are derived from the seeds on the device
     const size_t key_bytes = sizeof(ChaChaKey) * nblk * per_block, seed_words = 4 * nblk, start_words = columns ? nblk + 1 : 0;
+    const size_t tag_words = tags ? hash_tags_staged_words(tags, nblk, tag_bytes) : 0;
     CtxBlock block(ctx);
-    if (block.alloc(key_bytes + sizeof(uint64_t) * (seed_words + start_words))) return 1;
+    if (block.alloc(key_bytes + sizeof(uint64_t) * (seed_words + start_words + tag_words))) return 1;
+    const size_t given_words = seeds ? seed_words : 0;  // the staged words begin with the seeds, or right after them
     static thread_local std::vector<uint64_t> staging;
-    staging.resize(seed_words + start_words);
-    for (size_t j = 0; j < nblk; ++j)
-        for (int i = 0; i < 4; ++i) staging[4 * j + i] = seeds[j].words[i];
+    staging.resize(given_words + start_words + tag_words);
+    if (seeds)
+        for (size_t j = 0; j < nblk; ++j)
+            for (int i = 0; i < 4; ++i) staging[4 * j + i] = seeds[j].words[i];
     if (columns) {
         uint64_t at = 0;
         for (size_t j = 0; j < nblk; ++j) {
-            staging[seed_words + j] = at;
+            staging[given_words + j] = at;
             at += seg_cols[j];
         }
-        staging[seed_words + nblk] = at;
+        staging[given_words + nblk] = at;
     }
+    if (tag_words) hash_tags_stage(tags, nblk, tag_bytes, staging.data() + given_words + start_words);
     char *base = static_cast<char *>(block.ptr);
     ChaChaKey *d_keys = reinterpret_cast<ChaChaKey *>(base);
-    const GpuRngSeed *d_seeds = reinterpret_cast<const GpuRngSeed *>(base + key_bytes);
-    const uint64_t *d_starts = reinterpret_cast<const uint64_t *>(base + key_bytes) + seed_words;
+    uint64_t *d_words = reinterpret_cast<uint64_t *>(base + key_bytes);
+    GpuRngSeed *d_seeds = reinterpret_cast<GpuRngSeed *>(d_words);
+    const uint64_t *d_starts = d_words + seed_words;
     void *words = words_ptr(out);
-    MXX_TRACED_COPY("seeded block table (host to device)", ctx->stream, sizeof(uint64_t) * staging.size(),
-                    HIP_TRY(hipMemcpyAsync(base + key_bytes, staging.data(), sizeof(uint64_t) * staging.size(), hipMemcpyHostToDevice, ctx->stream)));
+    if (!staging.empty())
+        MXX_TRACED_COPY("seeded block table (host to device)", ctx->stream, sizeof(uint64_t) * staging.size(),
+                        HIP_TRY(hipMemcpyAsync(d_words + (seed_words - given_words), staging.data(), sizeof(uint64_t) * staging.size(),
+                                               hipMemcpyHostToDevice, ctx->stream)));
+    if (tags && launch_hash_seeds(ctx, d_seeds, tags, nblk, d_starts + start_words)) return 1;
     const uint64_t tag = uniform ? kTagUniform : (dist_type == GPU_MATRIX_DIST_BIT ? kTagBit : kTagTernary);
     MXX_LAUNCH(derive_block_subkeys_kernel, item_grid(nblk * per_block, 256), dim3(256), 0, ctx->stream, d_keys, d_seeds, tag, nblk, per_block,
                uniform ? 1u : 0u);
@@ -734,6 +742,19 @@ extern "C" int gpupoly_matrix_sample_distribution_blocks(GpuMatrix *out, int dis
     // as the plain entry finishes: samples are coefficients, callers get EVAL; a packable uniform sample is stored packed
     if (uniform && pack24_eligible(out)) return pack24_store(out, true);
     return launch_ntt(ctx, words, polys * L, static_cast<int>(L), false);
+}
+
+extern "C" int gpupoly_matrix_sample_distribution_blocks(GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, size_t nblk, int layout,
+                                                         const size_t *seg_cols) {
+    ABI_GUARD_BEGIN
+    return sample_blocks_impl("gpupoly_matrix_sample_distribution_blocks", false, out, dist_type, seeds, nullptr, nblk, layout, seg_cols);
+    ABI_GUARD_END
+}
+
+extern "C" int gpupoly_matrix_sample_hash_blocks(GpuMatrix *out, int dist_type, const GpuHashTags *tags, size_t nblk, int layout,
+                                                 const size_t *seg_cols) {
+    ABI_GUARD_BEGIN
+    return sample_blocks_impl("gpupoly_matrix_sample_hash_blocks", true, out, dist_type, nullptr, tags, nblk, layout, seg_cols);
     ABI_GUARD_END
 }
 

@@ -216,6 +216,96 @@ def _max_along(entries, axis, nrow, ncol):
     raise ValueError(f"axis must be None, 0, 1 or 'entries' (got {axis!r})")
 
 
+DEVICE_HASHES = {"keccak256": _ffi.GPUPOLY_HASH_KECCAK256, "keccak_256": _ffi.GPUPOLY_HASH_KECCAK256, "sha3_256": _ffi.GPUPOLY_HASH_SHA3_256}
+
+
+class IndexedTags:
+    """The tags prefix || encoding(first + t), t < count, of the reference's indexed loops: the index as 8 little-endian
+    bytes (`b"wee25_w_block_" || idx.to_le_bytes()`, src/commit/wee25.rs:687-703) or, with `decimal`, in ASCII decimal
+    (`format!("ggh15_lut_v_idx_{}_{}", lut_id, idx)`, src/lookup/ggh15/pubkey_gpu.rs:398-401).  A sequence of the literal
+    tags - len, iteration, indexing, slicing (a slice of step 1 is an IndexedTags again) - which the device-side hash
+    entries take as it is: the tags are then generated on the device (GPUPOLY_TAGS_INDEXED_*), prefix at most 64 bytes."""
+
+    __slots__ = ("prefix", "first", "count", "decimal")
+
+    def __init__(self, prefix: bytes, first: int, count: int, decimal: bool = False):
+        prefix, first, count = bytes(prefix), int(first), int(count)
+        if first < 0 or count < 0 or (count and first + count - 1 >= 1 << 64):
+            raise ValueError("IndexedTags: the indices must stay within 64 bits")
+        self.prefix, self.first, self.count, self.decimal = prefix, first, count, bool(decimal)
+
+    def __len__(self) -> int:
+        return self.count
+
+    def tag(self, t: int) -> bytes:
+        idx = self.first + t
+        return self.prefix + (str(idx).encode("ascii") if self.decimal else idx.to_bytes(8, "little"))
+
+    def __iter__(self):
+        return (self.tag(t) for t in range(self.count))
+
+    def __getitem__(self, item):
+        if isinstance(item, slice):
+            lo, hi, step = item.indices(self.count)
+            if step == 1:
+                return IndexedTags(self.prefix, self.first + lo, max(hi - lo, 0), self.decimal)
+            return [self.tag(t) for t in range(lo, hi, step)]
+        t = item + self.count if item < 0 else item
+        if not 0 <= t < self.count:
+            raise IndexError("IndexedTags index out of range")
+        return self.tag(t)
+
+    def __repr__(self):
+        return f"IndexedTags({self.prefix!r}, {self.first}, {self.count}, decimal={self.decimal})"
+
+
+def hash_tags_arg(key: bytes, tags, hash_name: str = "keccak256"):
+    """(GpuHashTags, the buffers it points into, number of tags) for `tags`: an IndexedTags whose prefix fits goes in an
+    indexed form, anything else as a table of its literal tags."""
+    if hash_name not in DEVICE_HASHES:
+        raise ValueError(f"no device-side hash {hash_name!r}")
+    key = bytes(key)
+    assert len(key) == 32
+    arg = _ffi.GpuHashTags()
+    arg.hash = DEVICE_HASHES[hash_name]
+    arg.key[:] = key
+    if isinstance(tags, IndexedTags) and len(tags.prefix) <= 64:
+        buf = C.create_string_buffer(tags.prefix, max(len(tags.prefix), 1))
+        arg.form = _ffi.GPUPOLY_TAGS_INDEXED_DECIMAL if tags.decimal else _ffi.GPUPOLY_TAGS_INDEXED_LE64
+        arg.tags = C.cast(buf, C.c_void_p)
+        arg.tag_offsets = None
+        arg.prefix_len, arg.first_index = len(tags.prefix), tags.first
+        return arg, (buf,), len(tags)
+    literal = [bytes(t) for t in tags]
+    offsets = (C.c_size_t * (len(literal) + 1))()
+    at = 0
+    for t, tag in enumerate(literal):
+        at += len(tag)
+        offsets[t + 1] = at
+    packed = b"".join(literal)
+    buf = C.create_string_buffer(packed, max(len(packed), 1))
+    arg.form = _ffi.GPUPOLY_TAGS_TABLE
+    arg.tags = C.cast(buf, C.c_void_p)
+    arg.tag_offsets = offsets
+    return arg, (buf, offsets), len(literal)
+
+
+def device_hash_seeds(params, key: bytes, tags, hash_name: str = "keccak256") -> list:
+    """[hash_seed_for_matrix(key, tag, hash_name) for tag in tags], hashed on the device (gpupoly_hash_seeds)."""
+    arg, keep, count = hash_tags_arg(key, tags, hash_name)
+    if count == 0:
+        return []
+    seeds = (GpuRngSeed * count)()
+    check_status(_ffi.lib().gpupoly_hash_seeds(params.ctx().raw, C.byref(arg), count, seeds), "gpupoly_hash_seeds")
+    del keep
+    out = []
+    for s in seeds:  # copies: the array's elements are views of its memory
+        c = GpuRngSeed()
+        c.words[:] = s.words[:]
+        out.append(c)
+    return out
+
+
 class GpuDCRTPolyMatrix:
     __slots__ = ("params", "nrow", "ncol", "level", "is_ntt", "raw", "_finalizer", "_parent", "_version", "__weakref__")
 
@@ -2066,6 +2156,31 @@ class GpuDCRTPolyMatrix:
             layout, cols = _ffi.GPUPOLY_BLOCKS_COLUMNS, (C.c_size_t * max(len(seg_cols), 1))(*seg_cols)
         check_status(_ffi.lib().gpupoly_matrix_sample_distribution_blocks(out.raw, dist, arr, len(seeds), layout, cols),
                      "gpupoly_matrix_sample_distribution_blocks")
+        return out
+
+    @classmethod
+    def sample_hash_blocks(cls, params, key: bytes, tags, dist: int, *, hash_name: str = "keccak256", block_polys=None, nrow=None,
+                           seg_cols=None) -> "GpuDCRTPolyMatrix":
+        """`sample_distribution_blocks` with seeds[t] = hash_seed_for_matrix(key, tags[t], hash_name) derived on the device
+        (gpupoly_matrix_sample_hash_blocks): tags in, no seeds on the host.  `tags` is an `IndexedTags`
+        (generated on the device: nothing is uploaded for them) or any sequence of byte strings (uploaded as one table);
+        `hash_name` is keccak256 / keccak_256 or sha3_256.  Layouts, result and the "unsupported" answers are those of
+        `sample_distribution_blocks`."""
+        arg, keep, count = hash_tags_arg(key, tags, hash_name)
+        level = params.crt_depth() - 1
+        if seg_cols is None:
+            assert block_polys is not None and nrow is None, "sample_hash_blocks: block_polys (stacked) or nrow and seg_cols (columns)"
+            out = cls(params, count, block_polys, level, True)
+            layout, cols = _ffi.GPUPOLY_BLOCKS_STACKED, None
+        else:
+            assert block_polys is None and nrow is not None, "sample_hash_blocks: block_polys (stacked) or nrow and seg_cols (columns)"
+            seg_cols = list(seg_cols)
+            assert len(seg_cols) == count, "sample_hash_blocks: one tag per block"
+            out = cls(params, nrow, sum(seg_cols), level, True)
+            layout, cols = _ffi.GPUPOLY_BLOCKS_COLUMNS, (C.c_size_t * max(len(seg_cols), 1))(*seg_cols)
+        check_status(_ffi.lib().gpupoly_matrix_sample_hash_blocks(out.raw, dist, C.byref(arg), count, layout, cols),
+                     "gpupoly_matrix_sample_hash_blocks")
+        del keep
         return out
 
     @staticmethod

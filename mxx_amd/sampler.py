@@ -7,7 +7,7 @@ from dataclasses import dataclass
 
 from . import _ffi
 from ._ffi import GpuRngSeed
-from .matrix import GpuDCRTPolyMatrix
+from .matrix import DEVICE_HASHES, GpuDCRTPolyMatrix, IndexedTags, device_hash_seeds  # noqa: F401
 from .poly import GpuDCRTPoly
 
 
@@ -165,21 +165,29 @@ class GpuDCRTPolyHashSampler:
     def __init__(self, hash_name: str = "keccak256"):
         self.hash_name = hash_name
 
+    def _on_device(self) -> bool:
+        """whether tags are hashed on the device (gpupoly_hash_seeds, gpupoly_matrix_sample_hash_blocks; DESIGN.md section
+        5q): the two Keccak paddings.  Any other hashlib name is hashed on the host - the same seeds either way."""
+        return self.hash_name in DEVICE_HASHES
+
+    def _seed(self, params, key, tag) -> GpuRngSeed:
+        return self._seeds(key, [tag], params)[0]
+
     def sample_hash(self, params, key: bytes, tag: bytes, nrow, ncol, dist: DistType) -> GpuDCRTPolyMatrix:
-        return sample_gpu_matrix_with_seed(params, nrow, ncol, dist, hash_seed_for_matrix(key, tag, self.hash_name))
+        return sample_gpu_matrix_with_seed(params, nrow, ncol, dist, self._seed(params, key, tag))
 
     def sample_hash_columns(self, params, key, tag, nrow, total_ncol, col_start, col_len, dist):
-        seed = hash_seed_for_matrix(key, tag, self.hash_name)
+        seed = self._seed(params, key, tag)
         return sample_gpu_matrix_with_seed_columns(params, nrow, total_ncol, col_start, col_len, dist, seed)
 
     def sample_hash_decomposed(self, params, key, tag, nrow, ncol, dist):
         """== sample_hash(...).decompose() (src/sampler/gpu.rs:91-103), in one extension call."""
-        seed = hash_seed_for_matrix(key, tag, self.hash_name)
+        seed = self._seed(params, key, tag)
         return GpuDCRTPolyMatrix.sample_distribution_decomposed(params, nrow, ncol, dist.as_ffi(), dist.sigma, seed)
 
     def sample_hash_small_decomposed(self, params, key, tag, nrow, ncol, dist):
         """== sample_hash(...).small_decompose() (src/sampler/gpu.rs:104-115), in one extension call."""
-        seed = hash_seed_for_matrix(key, tag, self.hash_name)
+        seed = self._seed(params, key, tag)
         return GpuDCRTPolyMatrix.sample_distribution_decomposed(params, nrow, ncol, dist.as_ffi(), dist.sigma, seed, True)
 
     def sample_hash_decomposed_columns(self, params, key, tag, nrow, total_ncol, col_start, col_len, dist,
@@ -187,32 +195,67 @@ class GpuDCRTPolyHashSampler:
         """== sample_hash_columns(...).decompose() (the trait default, src/sampler/mod.rs:84-97), in one extension call;
         with row_start / row_end, its rows [row_start, row_end) - the `rhs_full.slice(inner_start, ..)` of
         src/lookup/ggh15/poly_encoding_gpu.rs:515,566 - of which only those are computed."""
-        seed = hash_seed_for_matrix(key, tag, self.hash_name)
+        seed = self._seed(params, key, tag)
         return GpuDCRTPolyMatrix.sample_distribution_decomposed_window(
             params, nrow, total_ncol, col_start, col_len, dist.as_ffi(), dist.sigma, seed, False, row_start, row_end)
 
     def sample_hash_small_decomposed_columns(self, params, key, tag, nrow, total_ncol, col_start, col_len, dist,
                                              row_start=0, row_end=None):
         """== sample_hash_columns(...).small_decompose() (the trait default, src/sampler/mod.rs:111-124), likewise"""
-        seed = hash_seed_for_matrix(key, tag, self.hash_name)
+        seed = self._seed(params, key, tag)
         return GpuDCRTPolyMatrix.sample_distribution_decomposed_window(
             params, nrow, total_ncol, col_start, col_len, dist.as_ffi(), dist.sigma, seed, True, row_start, row_end)
 
-    # ---- many tags in one call (gpupoly_matrix_sample_distribution_blocks; DESIGN.md section 5p) ----------------------
-    def _seeds(self, key, tags):
+    # ---- many tags in one call (gpupoly_matrix_sample_distribution_blocks, gpupoly_matrix_sample_hash_blocks; DESIGN.md
+    # sections 5p, 5q) ------------------------------------------------------------------------------------------------
+    def _seeds(self, key, tags, params=None):
+        """[hash_seed_for_matrix(key, tag) for tag in tags]: one gpupoly_hash_seeds call per 2^20 tags on `params`' context
+        where the hash has a device form, the host definition otherwise"""
+        if params is not None and self._on_device():
+            tags = tags if isinstance(tags, IndexedTags) else list(tags)
+            seeds = []
+            for lo in range(0, len(tags), 1 << 20):
+                seeds += device_hash_seeds(params, key, tags[lo : lo + (1 << 20)], self.hash_name)
+            return seeds
         return [hash_seed_for_matrix(key, tag, self.hash_name) for tag in tags]
+
+    def _hash_blocks(self, params, key, tags, dist, **shape):
+        """sample_hash_blocks where the hash has a device form and the library does not answer "unsupported"; else None"""
+        if not self._on_device():
+            return None
+        try:
+            return GpuDCRTPolyMatrix.sample_hash_blocks(params, key, tags, dist.as_ffi(), hash_name=self.hash_name, **shape)
+        except _ffi.GpuPolyError as e:
+            if "unsupported" not in str(e):
+                raise
+        return None
 
     def sample_hash_many(self, params, key: bytes, tags, nrow, ncol, dist: DistType) -> list:
         """== [sample_hash(params, key, tag, nrow, ncol, dist) for tag in tags] - the tagged loops of
-        src/commit/wee25.rs:687-703, src/lookup/ggh15/pubkey_gpu.rs:924,1296 and src/lookup/lwe/pubkey_gpu.rs:559,616 -
-        with one columns-layout sample and one split_columns per 64 tags instead of a sample per tag (Gaussian requests
+        src/commit/wee25.rs:687-703, src/lookup/ggh15/pubkey_gpu.rs:924,1296 and src/lookup/lwe/pubkey_gpu.rs:559,616.
+        Uniform / bit / ternary under a Keccak hash: ONE columns-layout sample with the tags hashed on the device (no seeds
+        on the host; an `IndexedTags` is not even uploaded) per 2^20 tags, and one split_columns per 64 of them.  Otherwise
+        one columns-layout sample and one split_columns per 64 tags over host- or device-derived seeds (Gaussian requests
         through the Gaussian segments).  Where the library answers "unsupported" (MXX_HIP_RNG_COMPAT=reference, rings the
         Gaussian segments do not cover) the tags are sampled one by one: the same matrices either way."""
-        tags = list(tags)
+        tags = tags if isinstance(tags, IndexedTags) else list(tags)
         if nrow == 0 or ncol == 0:
-            return [GpuDCRTPolyMatrix.zero(params, nrow, ncol) for _ in tags]
-        seeds = self._seeds(key, tags)
+            return [GpuDCRTPolyMatrix.zero(params, nrow, ncol) for _ in range(len(tags))]
         outs = []
+        if dist.kind != "gauss":
+            for lo in range(0, len(tags), 1 << 20):  # the entry's block limit; "unsupported" is the first call's answer or nobody's
+                part = tags[lo : lo + (1 << 20)]
+                wide = self._hash_blocks(params, key, part, dist, nrow=nrow, seg_cols=[ncol] * len(part))
+                if wide is None:
+                    break
+                for at in range(0, len(part), 64):
+                    width = min(64, len(part) - at)
+                    piece = wide if width == len(part) else wide.slice_columns(at * ncol, (at + width) * ncol)
+                    outs.extend(piece.split_columns([ncol] * width))
+            if len(outs) == len(tags):
+                return outs
+            outs = []
+        seeds = self._seeds(key, tags, params)
         for lo in range(0, len(tags), 64):
             chunk = seeds[lo : lo + 64]
             widths = [ncol] * len(chunk)
@@ -231,13 +274,18 @@ class GpuDCRTPolyHashSampler:
 
     def sample_hash_stacked(self, params, key: bytes, tags, nrow, ncol, dist: DistType) -> GpuDCRTPolyMatrix:
         """The len(tags) x (nrow * ncol) matrix whose row t is sample_hash(params, key, tags[t], nrow, ncol, dist) in
-        row-major order, sampled in one stacked-layout call; where the library answers "unsupported" (the Gaussian
-        distribution, MXX_HIP_RNG_COMPAT=reference) the rows are sampled one by one and copied in."""
-        tags = list(tags)
-        seeds = self._seeds(key, tags)
+        row-major order, sampled in one stacked-layout call - under a Keccak hash with the tags hashed on the device, no seeds
+        on the host; where the library answers "unsupported" (the Gaussian distribution, MXX_HIP_RNG_COMPAT=reference) the
+        rows are sampled one by one and copied in."""
+        tags = tags if isinstance(tags, IndexedTags) else list(tags)
         polys = nrow * ncol
-        if not tags or polys == 0:
+        if not len(tags) or polys == 0:
             return GpuDCRTPolyMatrix.zero(params, len(tags), polys)
+        if dist.kind != "gauss" and len(tags) <= 1 << 20:
+            out = self._hash_blocks(params, key, tags, dist, block_polys=polys)
+            if out is not None:
+                return out
+        seeds = self._seeds(key, tags, params)
         try:
             return GpuDCRTPolyMatrix.sample_distribution_blocks(params, seeds, dist.as_ffi(), block_polys=polys)
         except _ffi.GpuPolyError as e:
@@ -266,7 +314,7 @@ class GpuDCRTPolyHashSampler:
         in chunks whose stack stays within max_stack_bytes (in 4- or 8-byte words; at least one tag per chunk): per chunk
         one stacked sample, one product, one accumulation into a 1 x (nrow * ncol) row.  The result is that row seen as
         nrow x ncol (reshape_view): no copy."""
-        tags = list(tags)
+        tags = tags if isinstance(tags, IndexedTags) else list(tags)
         polys = nrow * ncol
         assert weights.is_ntt and (weights.nrow, weights.ncol) == (1, len(tags)), "sample_hash_weighted_sum: weights is a 1 x len(tags) EVAL matrix"
         if addend is not None:
