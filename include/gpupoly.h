@@ -499,6 +499,32 @@ int gpupoly_matrix_split_columns(const GpuMatrix *src, GpuMatrix *const *blocks,
 int gpupoly_trapdoor_preimage_many(const GpuMatrix *re, const GpuP1CovarianceCache *cache, const GpuMatrix *public_matrix,
                                    uint32_t base_bits, const GpuMatrix *const *targets, size_t n, const GpuRngSeed *seeds,
                                    GpuMatrix *const *outs);
+/* The same for requests that do NOT all share a trapdoor: request j belongs to key key_of[j] < nkeys and outs[j] is, bit for
+ * bit, what gpupoly_trapdoor_preimage_many writes for targets[j] alone with (res[k], caches[k], public_matrices[k]),
+ * k = key_of[j], under the seeds seeds[3j], seeds[3j+1], seeds[3j+2] - whatever the spread of the requests over the keys,
+ * their order, or what else is in the call.  Replaces the body of preimage_batched_sharded (gpu.rs:371-397) for one
+ * context: its requests each carry their own (trapdoor, public matrix, target).
+ *   res[k], caches[k], public_matrices[k]   key k, each as in gpupoly_trapdoor_preimage_many; all keys in one context,
+ *                 at one level, with one d, and all caches with the same (sigma, s, dgg_stddev) - keys of one parameter set
+ *   key_of[j], targets[j], outs[j]          request j; shapes, formats and tags as in gpupoly_trapdoor_preimage_many
+ * Only the linear algebra and the perturbation's conditional Gaussians depend on the key, so the requests - ordered by
+ * key (stable), cut into the same groups of up to 64 (p2 capped at 1 GiB; a boundary may fall inside a key's requests) -
+ * share that entry's sequence of launches: p2 and the G-sampler as they are, p1 by a form of its sampler that finds each
+ * segment's covariance cache in a device table (from the context's allocator, filled by one staged copy, released
+ * stream-ordered), the three products as one launch each that takes a left operand per column range.  The number of
+ * launches of a group does not depend on the number of keys.  Enqueued on the context's stream; the host does not block.
+ * A key may have no requests; zero-column requests give zero-column outputs; n = 0 launches nothing; nkeys = 1 gives
+ * what gpupoly_trapdoor_preimage_many gives.
+ * A refused call launches nothing and writes no output, not even a format tag; every condition is checked for every key
+ * and every request before the first launch: everything gpupoly_trapdoor_preimage_many refuses, per key and per
+ * request; a null array with nkeys > 0 or n > 0; nkeys = 0 with n > 0; key_of[j] >= nkeys; keys that differ in d, level
+ * or context; an output that aliases any key's [R; E] or A, any target or another output.  Refused with "unsupported" in
+ * the text - issue one gpupoly_trapdoor_preimage_many per key then: everything that entry answers so, and caches whose
+ * three widths are not all equal.                                                                                    */
+int gpupoly_trapdoor_preimage_keyed(const GpuMatrix *const *res, const GpuP1CovarianceCache *const *caches,
+                                    const GpuMatrix *const *public_matrices, size_t nkeys, uint32_t base_bits,
+                                    const uint32_t *key_of, const GpuMatrix *const *targets, size_t n,
+                                    const GpuRngSeed *seeds, GpuMatrix *const *outs);
 /* Exact scale-and-round of every coefficient (extension): coefficient k of out[i][j] becomes
  *   floor((t * c + h) / Q) mod t,   h = round_half ? floor(Q/2) : 0,
  * c the coefficient of in[i][j] as coeffs() gives it (in [0, Q)), Q the context's FULL modulus; written as its residue

@@ -161,6 +161,8 @@ SIGNATURES = {
     "gpupoly_matrix_concat_columns": (C.c_int, [_vp, C.POINTER(C.c_void_p), _sz]),
     "gpupoly_matrix_split_columns": (C.c_int, [_vp, C.POINTER(C.c_void_p), _sz]),
     "gpupoly_trapdoor_preimage_many": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(C.c_void_p), _sz, C.POINTER(GpuRngSeed), C.POINTER(C.c_void_p)]),
+    "gpupoly_trapdoor_preimage_keyed": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, C.c_uint32,
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), _sz, C.POINTER(GpuRngSeed), C.POINTER(C.c_void_p)]),
     "gpupoly_launch_count": (C.c_uint64, []),
     "gpupoly_matrix_scale_round": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int]),
     "gpupoly_matrix_crt_recompose_rounded": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int), _sz, _sz]),

@@ -170,6 +170,13 @@ struct GpuP1CovarianceCache {
     void *karney_div = nullptr;      // [coeff][row] KarneyDivisor of sqrt_var (rng.h)
 };
 
+// one covariance cache's arrays as the keyed p1 sampler reads them from its device table (trapdoor.hip)
+struct P1KeyEntry {
+    const double *sqrt_var;
+    const double *update_coeff;
+    const void *karney_div;
+};
+
 // ---- one thread per item -----------------------------------------------------------------------
 // HIP rejects launches with gridDim.x * blockDim.x >= 2^32 ("invalid configuration argument"), which a
 // 64x1024 gadget matrix at n = 2^14 already exceeds: such kernels use item_grid() / item_index().
@@ -384,4 +391,7 @@ int launch_matmul_dma32_u32(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatri
 int launch_matmul_mfma_u32(GpuMatrix *out, const GpuMatrix *lhs, const GpuMatrix *rhs);  // -1: shape / moduli not supported
 int launch_copy_block(GpuMatrix *out, const GpuMatrix *src, size_t dst_row, size_t dst_col, size_t src_row,
                       size_t src_col, size_t rows, size_t cols, bool add);
+// trapdoor.hip: gpupoly_matrix_sample_p1_full_cached_segments with segment j's cache arrays in d_keys[j] (device memory)
+int sample_p1_keyed_segments(const GpuP1CovarianceCache *cache, const P1KeyEntry *d_keys, const GpuMatrix *tp2,
+                             const GpuRngSeed *seeds, const size_t *seg_cols, size_t nseg, GpuMatrix *out);
 int launch_scatter_i64(GpuMatrix *out, const int64_t *vals);  // int64 [poly][N] -> residues in every limb

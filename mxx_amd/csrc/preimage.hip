@@ -1,4 +1,5 @@
-// preimage.hip — several preimage requests against ONE trapdoor in one ABI call (gpupoly_trapdoor_preimage_many).
+// preimage.hip — several preimage requests in one ABI call: against ONE trapdoor (gpupoly_trapdoor_preimage_many) or
+// each against one of several (gpupoly_trapdoor_preimage_keyed, at the end of this file).
 //
 // The body of `preimage` (src/sampler/trapdoor/gpu.rs:228-369, :423-474) over the column-wise concatenation of up to 64
 // requests per group, each with its own seed triple (the gpupoly_*_segments samplers key every element by its position
@@ -11,8 +12,7 @@
 //   outs[j]            scatter-assemble: [P_top + [R;E] z ; P_bottom + z], written straight into each caller's output
 // The mirror's sequence (mxx_amd/trapdoor.py, `_preimage_segments`) adds a concatenation of the targets, two
 // drop-padding passes, two products for the image, a sum, a difference, two row-block sums and a split.
-#include "common.h"
-#include "modarith.h"
+#include "matmul_tile.h"
 #include "rng.h"
 
 #include <algorithm>
@@ -157,6 +157,141 @@ static int launch_scatter(GpuContext *ctx, const RequestTable &req, const GpuMat
     return 0;
 }
 
+// ---- the keyed few-row product: out[:, c] = lhs_k(c) * rhs[:, c] -------------------------------------------------------
+// The columns of rhs (inner x cols) and out (rows x cols, rows <= 4) fall into runs; run k owns columns
+// [col_start[k], col_start[k + 1]) and has a left operand of its own (rows x inner): the requests of one trapdoor.  A
+// column tile never crosses a run, so a workgroup has ONE left operand and the shared register-tile loop (matmul_tile.h)
+// with its lazy-accumulation rule serves as it stands; run k owns the column tiles [tile_start[k], tile_start[k + 1]).
+// The residues are canonical, so every run's columns equal gpu_matrix_mul's for that run alone, bit for bit.
+struct KeyedLhs {
+    uint32_t count;                      // runs with columns
+    uint32_t col_start[kGroupMax + 1];   // col_start[count] = cols
+    uint32_t tile_start[kGroupMax + 1];  // tile_start[count] = all column tiles
+    const void *lhs[kGroupMax];          // words, rows x inner
+};
+static_assert(sizeof(KeyedLhs) <= 4096 - 128, "the run table must fit the kernel-argument segment");
+
+// blockIdx.y = column tile * row_tiles + row tile, x: slots (SV per lane), z: limbs - matmul_group_kernel's grid
+template <typename W, int TR, int TC, int SV>
+__global__ void __launch_bounds__(256)
+    matmul_keyed_kernel(KeyedLhs keys, W *__restrict__ C, const W *__restrict__ B, const LimbConst *__restrict__ limbs, uint32_t rows,
+                        uint32_t inner, uint32_t cols, uint32_t L, uint32_t N, uint32_t row_tiles) {
+    constexpr bool NTB = false;  // few columns: B is never beyond the Infinity Cache
+    const uint32_t limb = blockIdx.z;
+    const uint32_t ct = blockIdx.y / row_tiles, rt = blockIdx.y - ct * row_tiles;
+    const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) * SV;
+    if (i >= N) return;
+    uint32_t lo = 0, hi = keys.count;  // tile_start[lo] <= ct < tile_start[hi]: request_of's search, wave-uniform
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (ct >= keys.tile_start[mid]) lo = mid;
+        else hi = mid;
+    }
+    const uint32_t r0 = rt * TR, c0 = keys.col_start[lo] + (ct - keys.tile_start[lo]) * TC, cend = keys.col_start[lo + 1];
+    const LimbConst lc = limbs[limb];
+    const W q = static_cast<W>(lc.q);
+    typedef typename TileTypes<W, SV>::VT VT;
+    typedef typename TileTypes<W, SV>::wxs wxs;
+    typedef typename TileTypes<W, SV>::D D;
+
+    const size_t poly = static_cast<size_t>(L) * N;  // words per polynomial
+    const size_t in_poly = static_cast<size_t>(limb) * N + i;
+    // rows past the end repeat the last row, columns past the run's end its last column: computed, never stored
+    const W *a_ptr[TR];
+#pragma unroll
+    for (int r = 0; r < TR; ++r)
+        a_ptr[r] = static_cast<const W *>(keys.lhs[lo]) + static_cast<size_t>(min(r0 + r, rows - 1)) * inner * poly + in_poly;
+    size_t b_off[TC];
+#pragma unroll
+    for (int c = 0; c < TC; ++c) b_off[c] = static_cast<size_t>(min(c0 + c, cend - 1)) * poly + in_poly;
+    const size_t strideBk = static_cast<size_t>(cols) * poly;
+
+    D acc[TR][TC][SV];
+    MXX_TILE_CLEAR(acc);
+    const uint32_t lazy = lc.lazy_terms;
+    uint32_t pending = 0;
+#define MXX_TILE_A(r, k) (a_ptr[r] + (k) * poly)
+#define MXX_TILE_B(c, k) (B + b_off[c] + (k) * strideBk)
+#include "matmul_tile_loop.inc"
+#pragma unroll
+    for (int r = 0; r < TR; ++r) {
+        if (r0 + r >= rows) continue;
+#pragma unroll
+        for (int c = 0; c < TC; ++c) {
+            if (c0 + c >= cend) continue;
+            W o[SV];
+#pragma unroll
+            for (int s = 0; s < SV; ++s) o[s] = tile_reduce<W>(acc[r][c][s], q, lc);
+            *reinterpret_cast<VT *>(C + (static_cast<size_t>(r0 + r) * cols + c0 + c) * poly + in_poly) = *reinterpret_cast<const VT *>(o);
+        }
+    }
+}
+
+// the key runs of one group of requests, host side: run k = the group's adjacent requests of one key
+struct KeyRuns {
+    size_t count = 0;
+    uint32_t start[kGroupMax + 1];      // first column of run k in the target-shaped matrices
+    uint32_t pad_start[kGroupMax + 1];  // ... in the padded ones
+    const GpuMatrix *re[kGroupMax], *a[kGroupMax];
+};
+
+static uint64_t keyed_col_tiles(const uint32_t *col_start, size_t runs, uint32_t tc) {
+    uint64_t tiles = 0;
+    for (size_t k = 0; k < runs; ++k) tiles += (col_start[k + 1] - col_start[k] + tc - 1) / tc;
+    return tiles;
+}
+
+// whether the grid of the keyed product of `rows` rows over these runs fits (checked before a call's first launch)
+static bool keyed_grid_fits(const GpuContext *ctx, size_t rows, const uint32_t *col_start, size_t runs, size_t L) {
+    const TileShape t = stacked_tile(ctx, rows, col_start[runs], L);
+    return (rows + t.tr - 1) / t.tr * keyed_col_tiles(col_start, runs, t.tc) <= 65535;
+}
+
+template <typename W, int TR, int TC, int SV>
+static int launch_keyed_cfg(GpuContext *ctx, GpuMatrix *out, const GpuMatrix *const *lhs, const uint32_t *col_start, size_t runs,
+                            const GpuMatrix *rhs) {
+    const uint32_t rows = static_cast<uint32_t>(out->rows), inner = static_cast<uint32_t>(rhs->rows),
+                   cols = static_cast<uint32_t>(rhs->cols), L = static_cast<uint32_t>(matrix_limbs(out));
+    KeyedLhs keys{};
+    keys.count = static_cast<uint32_t>(runs);
+    uint32_t tiles = 0;
+    double lhs_bytes = 0.0;
+    for (size_t k = 0; k < runs; ++k) {
+        keys.col_start[k] = col_start[k];
+        keys.tile_start[k] = tiles;
+        keys.lhs[k] = words_ptr(lhs[k]);
+        tiles += (col_start[k + 1] - col_start[k] + TC - 1) / TC;
+        lhs_bytes += static_cast<double>(lhs[k]->bytes);
+    }
+    for (size_t k = runs; k <= kGroupMax; ++k) {
+        keys.col_start[k] = cols;
+        keys.tile_start[k] = tiles;
+    }
+    TileGrid g = tile_grid<TR, TC, SV>(ctx, rows, cols, L, rhs->bytes);
+    g.grid.y = g.row_tiles * tiles;
+    if (g.grid.y > 65535) return set_error("gpupoly_trapdoor_preimage_keyed: matrix too large");
+    static const std::string name = std::string("matmul_keyed_kernel<") + (sizeof(W) == 4 ? "u32," : "u64,") + std::to_string(TR) + "," +
+                                    std::to_string(TC) + "," + std::to_string(SV) + "> (a left operand per column run, few rows)";
+    ctx->last_kernel = name.c_str();
+    MXX_TRACE_BYTES(lhs_bytes + static_cast<double>(rhs->bytes) + static_cast<double>(out->bytes));
+    MXX_LAUNCH((matmul_keyed_kernel<W, TR, TC, SV>), g.grid, dim3(g.threads), 0, ctx->stream, keys, static_cast<W *>(words_ptr(out)),
+               static_cast<const W *>(words_ptr(rhs)), ctx->d_limbs, rows, inner, cols, L, static_cast<uint32_t>(ctx->N), g.row_tiles);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// out (rows x cols) = per run k: lhs[k] (rows x inner) * rhs[:, col_start[k] .. col_start[k + 1]); every run has columns
+static int launch_matmul_keyed(GpuContext *ctx, GpuMatrix *out, const GpuMatrix *const *lhs, const uint32_t *col_start, size_t runs,
+                               const GpuMatrix *rhs) {
+    const int rc = dispatch_stacked_tile(ctx, stacked_tile(ctx, out->rows, rhs->cols, matrix_limbs(out)), [&](auto cfg) {
+        typedef decltype(cfg) T;
+        if constexpr (T::TR > 4) return set_error("gpupoly_trapdoor_preimage_keyed: more than four rows");  // stacked_tile: never for rows <= 4
+        else return launch_keyed_cfg<typename T::W, T::TR, T::TC, T::SV>(ctx, out, lhs, col_start, runs, rhs);
+    });
+    if (rc == 0) out->format = GPU_POLY_FORMAT_EVAL;
+    return rc;
+}
+
 // a temporary of the context's allocator, released stream-ordered when the scope ends (error paths included)
 struct TempMatrix {
     GpuMatrix *m = nullptr;
@@ -197,11 +332,20 @@ struct PreimageCall {
     uint32_t base_bits;
     double sigma_large;
     size_t d, dk;
+    const char *entry = "gpupoly_trapdoor_preimage_many";  // named in this call's errors
+};
+
+// gpupoly_trapdoor_preimage_keyed: what one group adds - its key runs, and the device table of its segments' caches
+struct KeyedGroup {
+    KeyRuns runs;
+    const P1KeyEntry *d_keys;
 };
 
 // one group of requests (all with columns): the sequence of launches described at the top of this file
+// `keyed`: the group's requests belong to several trapdoors - the three products take a left operand per key run and the
+// p1 sampler a covariance cache per segment; call.re, call.a and call.cache then stand for what all keys share
 static int preimage_group(const PreimageCall &call, const GpuMatrix *const *targets, const GpuRngSeed *seeds,
-                          GpuMatrix *const *outs, const std::vector<size_t> &group) {
+                          GpuMatrix *const *outs, const std::vector<size_t> &group, const KeyedGroup *keyed = nullptr) {
     GpuContext *ctx = call.ctx;
     const int level = call.re->level;
     const size_t top = 2 * call.d, ng = group.size();
@@ -224,7 +368,7 @@ static int preimage_group(const PreimageCall &call, const GpuMatrix *const *targ
         at += cols[g];
         pad_at += pads[g];
     }
-    if (pad_at >> 32) return fail("a group of requests wider than 2^32 columns");
+    if (pad_at >> 32) return set_error(std::string(call.entry) + ": a group of requests wider than 2^32 columns");
     for (size_t g = ng; g <= kGroupMax; ++g) gather.start[g] = scatter.start[g] = static_cast<uint32_t>(at);
     for (size_t g = ng; g < kGroupMax; ++g) {
         gather.pad_start[g] = scatter.pad_start[g] = static_cast<uint32_t>(pad_at);
@@ -237,14 +381,19 @@ static int preimage_group(const PreimageCall &call, const GpuMatrix *const *targ
     GpuMatrix p1 = row_block(p.m, 0, top), p2 = row_block(p.m, top, call.dk);
     rc = gpupoly_matrix_sample_distribution_segments(&p2, GPU_MATRIX_DIST_GAUSS, call.sigma_large, seed_p2.data(), pads.data(), ng);
     if (rc) return rc;
-    if ((rc = tp2.make(ctx, level, top, pad_at)) || (rc = gpu_matrix_mul(tp2.m, call.re, &p2)) || (rc = gpu_matrix_intt_all(tp2.m)))
-        return rc;
-    rc = gpupoly_matrix_sample_p1_full_cached_segments(call.cache, tp2.m, seed_p1.data(), pads.data(), ng, &p1);
+    if ((rc = tp2.make(ctx, level, top, pad_at))) return rc;
+    rc = keyed ? launch_matmul_keyed(ctx, tp2.m, keyed->runs.re, keyed->runs.pad_start, keyed->runs.count, &p2)
+               : gpu_matrix_mul(tp2.m, call.re, &p2);
+    if (rc || (rc = gpu_matrix_intt_all(tp2.m))) return rc;
+    rc = keyed ? sample_p1_keyed_segments(call.cache, keyed->d_keys, tp2.m, seed_p1.data(), pads.data(), ng, &p1)
+               : gpupoly_matrix_sample_p1_full_cached_segments(call.cache, tp2.m, seed_p1.data(), pads.data(), ng, &p1);
     if (rc) return rc;
     tp2.release();
     p.m->format = GPU_POLY_FORMAT_EVAL;  // both row blocks were written in EVAL form
     // the image A P in one product, then u - A P over the targets' columns only
-    if ((rc = ap.make(ctx, level, call.d, pad_at)) || (rc = gpu_matrix_mul(ap.m, call.a, p.m))) return rc;
+    if ((rc = ap.make(ctx, level, call.d, pad_at))) return rc;
+    rc = keyed ? launch_matmul_keyed(ctx, ap.m, keyed->runs.a, keyed->runs.pad_start, keyed->runs.count, p.m) : gpu_matrix_mul(ap.m, call.a, p.m);
+    if (rc) return rc;
     if ((rc = perturbed.make(ctx, level, call.d, at))) return rc;
     rc = ctx->wide ? launch_gather_sub<uint64_t>(ctx, perturbed.m, ap.m, gather) : launch_gather_sub<uint32_t>(ctx, perturbed.m, ap.m, gather);
     if (rc) return rc;
@@ -255,7 +404,9 @@ static int preimage_group(const PreimageCall &call, const GpuMatrix *const *targ
                                                         seed_z.data(), cols.data(), ng, z.m);
     if (rc) return rc;
     perturbed.release();
-    if ((rc = rez.make(ctx, level, top, at)) || (rc = gpu_matrix_mul(rez.m, call.re, z.m))) return rc;
+    if ((rc = rez.make(ctx, level, top, at))) return rc;
+    rc = keyed ? launch_matmul_keyed(ctx, rez.m, keyed->runs.re, keyed->runs.start, keyed->runs.count, z.m) : gpu_matrix_mul(rez.m, call.re, z.m);
+    if (rc) return rc;
     // x_j = [p1 + [R;E] z ; p2 + z], straight into the callers' outputs
     return ctx->wide ? launch_scatter<uint64_t>(ctx, scatter, p.m, rez.m, z.m) : launch_scatter<uint32_t>(ctx, scatter, p.m, rez.m, z.m);
 }
@@ -329,6 +480,148 @@ extern "C" int gpupoly_trapdoor_preimage_many(const GpuMatrix *re, const GpuP1Co
     }
     if (!group.empty()) {
         const int rc = preimage_group(call, targets, seeds, outs, group);
+        if (rc) return rc;
+    }
+    for (size_t j = 0; j < n; ++j) outs[j]->format = GPU_POLY_FORMAT_EVAL;
+    return 0;
+    ABI_GUARD_END
+}
+
+// ---- requests of several trapdoors in one call ---------------------------------------------------------------------------
+// Only the linear algebra and the perturbation's conditional Gaussians depend on the key: p2 and the G-sampler do not read
+// it, the p1 sampler reads it through the three arrays of its covariance cache, the three products through [R;E] and A.
+// So the requests are ordered by key (stable) and cut into groups exactly as above - a boundary may fall inside a key's
+// run - and a group runs preimage_group's sequence once, whatever the number of keys in it: the products as
+// matmul_keyed_kernel over the group's key runs, p1 as the sampler's KEYED form, which finds segment j's cache in a
+// device table.  That table (one P1KeyEntry per segment, 64 per group, all groups of the call in one block from the
+// context's allocator) is filled by one staged copy before the first group and released stream-ordered.
+extern "C" int gpupoly_trapdoor_preimage_keyed(const GpuMatrix *const *res, const GpuP1CovarianceCache *const *caches,
+                                               const GpuMatrix *const *public_matrices, size_t nkeys, uint32_t base_bits,
+                                               const uint32_t *key_of, const GpuMatrix *const *targets, size_t n,
+                                               const GpuRngSeed *seeds, GpuMatrix *const *outs) {
+    ABI_GUARD_BEGIN
+    static const char *const who = "gpupoly_trapdoor_preimage_keyed";
+    auto refuse = [&](const std::string &what) { return set_error(std::string(who) + ": " + what); };
+    // ---- every check, for every key and every request, before the first launch
+    if (nkeys > 0 && (!res || !caches || !public_matrices)) return refuse("null array of trapdoors, covariance caches or public matrices");
+    if (n > 0 && (!key_of || !targets || !seeds || !outs)) return refuse("null key_of, targets, seeds or outputs");
+    if (nkeys == 0 && n > 0) return refuse("requests without keys");
+    if (base_bits == 0 || base_bits >= 63) return refuse("invalid base_bits");
+    for (size_t k = 0; k < nkeys; ++k)
+        if (!res[k] || !caches[k] || !public_matrices[k])
+            return refuse("null trapdoor, covariance cache or public matrix in key " + std::to_string(k));
+    if (nkeys == 0) return 0;
+    GpuContext *ctx = res[0]->ctx;
+    const int level = res[0]->level;
+    const size_t d = public_matrices[0]->rows, L = matrix_limbs(res[0]);
+    const uint32_t dpt = (ctx->crt_bits + base_bits - 1) / base_bits;
+    const size_t top = 2 * d, dk = d * dpt * L;
+    for (size_t k = 0; k < nkeys; ++k) {
+        const GpuMatrix *re = res[k], *a = public_matrices[k];
+        const GpuP1CovarianceCache *cache = caches[k];
+        const std::string at = " in key " + std::to_string(k);
+        if (re->ctx != ctx || cache->ctx != ctx || a->ctx != ctx) return refuse("context mismatch" + at);
+        if (re->level != level || cache->level != level || a->level != level) return refuse("level mismatch" + at);
+        if (a->rows != d) return refuse("keys of different trapdoor dimension d" + at);
+        if (d == 0 || re->rows != top || re->cols != dk || a->cols != top + dk || cache->d != d || cache->m != top)
+            return refuse("shape mismatch" + at + ": needs [R; E] 2d x dk, A d x (2d + dk) and a covariance cache of dimension d");
+        if (re->format != GPU_POLY_FORMAT_EVAL || a->format != GPU_POLY_FORMAT_EVAL)
+            return refuse("[R; E] and the public matrix must be in EVAL form" + at);
+    }
+    for (size_t j = 0; j < n; ++j) {
+        const GpuMatrix *t = targets[j], *o = outs[j];
+        const std::string js = std::to_string(j);
+        if (key_of[j] >= nkeys) return refuse("key_of[" + js + "] out of range");
+        if (!t || !o) return refuse("null target or output " + js);
+        if (t->ctx != ctx || o->ctx != ctx) return refuse("context mismatch in request " + js);
+        if (t->level != level || o->level != level) return refuse("level mismatch in request " + js);
+    }
+    // shared storage is named as such, whatever shape the overlapping view has: before the shape checks
+    for (size_t j = 0; j < n; ++j) {
+        const GpuMatrix *o = outs[j];
+        bool alias = false;
+        for (size_t k = 0; k < nkeys && !alias; ++k) alias = words_overlap(o, res[k]) || words_overlap(o, public_matrices[k]);
+        for (size_t i = 0; i < n && !alias; ++i) alias = words_overlap(o, targets[i]) || (i != j && words_overlap(o, outs[i]));
+        if (alias) return refuse("output " + std::to_string(j) + " aliases a key's [R; E] or A, a target or another output");
+    }
+    for (size_t j = 0; j < n; ++j) {
+        const GpuMatrix *t = targets[j], *o = outs[j];
+        const std::string js = std::to_string(j);
+        if (t->rows != d) return refuse("target " + js + " must have d rows");
+        if (o->rows != top + dk || o->cols != t->cols) return refuse("output " + js + " must be (2d + dk) x its target's columns");
+        if (t->format != GPU_POLY_FORMAT_EVAL) return refuse("target " + js + " must be in EVAL form");
+        if (t->cols >> 31) return refuse("target " + js + " too wide");
+    }
+    // what the segmented samplers cover, as in the one-key entry; the caller then issues one call per key
+    if ((static_cast<size_t>(ctx->N) >> 1) % SAMPLER_THREADS)
+        return refuse("unsupported: ring dimension not a multiple of 128 (segmented samplers)");
+    if (top > 4 || ctx->env.p1_simple) return refuse("unsupported: trapdoor dimension above 2 or MXX_HIP_P1=simple (no p1 lane kernel)");
+    if (dpt > 4) return refuse("unsupported: more than four digits per tower (G-sampler lane kernel)");
+    if (ctx->env.rng_compat) return refuse("unsupported under MXX_HIP_RNG_COMPAT=reference");
+    for (size_t k = 1; k < nkeys; ++k)  // sigma_large and c_scale are single launch scalars
+        if (caches[k]->sigma != caches[0]->sigma || caches[k]->s != caches[0]->s || caches[k]->dgg_stddev != caches[0]->dgg_stddev)
+            return refuse("unsupported: the covariance caches of key 0 and key " + std::to_string(k) + " carry different widths");
+    const GpuP1CovarianceCache *cache0 = caches[0];
+    const double sigma_large = std::sqrt(cache0->s * cache0->s - cache0->sigma * cache0->sigma);
+    if (!(sigma_large > 0.0) || !(cache0->sigma > 0.0)) return refuse("invalid Gaussian widths in the covariance caches");
+    // ---- by key (stable), then groups as in the one-key entry: at most 64 requests with columns, p2 capped at 1 GiB
+    std::vector<size_t> order;
+    for (size_t j = 0; j < n; ++j)
+        if (targets[j]->cols) order.push_back(j);  // a zero-column request: a zero-column output, nothing to launch
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return key_of[x] < key_of[y]; });
+    const size_t poly_bytes = L * static_cast<size_t>(ctx->N) * ctx->word_bytes;
+    std::vector<std::vector<size_t>> groups;
+    size_t group_bytes = 0;
+    for (size_t j : order) {
+        const size_t bytes = dk * ((targets[j]->cols + d - 1) / d * d) * poly_bytes;
+        if (groups.empty() || groups.back().size() == kGroupMax || group_bytes + bytes > kGroupBytes) {
+            groups.emplace_back();
+            group_bytes = 0;
+        }
+        groups.back().push_back(j);
+        group_bytes += bytes;
+    }
+    // a group's key runs and, per segment, its cache; the grids of the three products must fit
+    std::vector<KeyedGroup> keyed(groups.size());
+    std::vector<P1KeyEntry> table(groups.size() * kGroupMax, P1KeyEntry{nullptr, nullptr, nullptr});
+    for (size_t g = 0; g < groups.size(); ++g) {
+        KeyRuns &runs = keyed[g].runs;
+        uint64_t at = 0, pad_at = 0;
+        for (size_t m = 0; m < groups[g].size(); ++m) {
+            const size_t j = groups[g][m];
+            const uint32_t key = key_of[j];
+            if (m == 0 || key != key_of[groups[g][m - 1]]) {
+                runs.start[runs.count] = static_cast<uint32_t>(at);
+                runs.pad_start[runs.count] = static_cast<uint32_t>(pad_at);
+                runs.re[runs.count] = res[key];
+                runs.a[runs.count] = public_matrices[key];
+                ++runs.count;
+            }
+            table[g * kGroupMax + m] = P1KeyEntry{caches[key]->sqrt_var, caches[key]->update_coeff, caches[key]->karney_div};
+            at += targets[j]->cols;
+            pad_at += (targets[j]->cols + d - 1) / d * d;
+        }
+        if (pad_at >> 32) return refuse("a group of requests wider than 2^32 columns");
+        runs.start[runs.count] = static_cast<uint32_t>(at);
+        runs.pad_start[runs.count] = static_cast<uint32_t>(pad_at);
+        if (!keyed_grid_fits(ctx, top, runs.pad_start, runs.count, L) || !keyed_grid_fits(ctx, d, runs.pad_start, runs.count, L) ||
+            !keyed_grid_fits(ctx, top, runs.start, runs.count, L))
+            return refuse("matrix too large");
+    }
+    if (groups.empty()) {
+        for (size_t j = 0; j < n; ++j) outs[j]->format = GPU_POLY_FORMAT_EVAL;
+        return 0;
+    }
+    if (ctx_activate(ctx)) return 1;
+    CtxBlock d_table(ctx);
+    if (d_table.alloc(table.size() * sizeof(P1KeyEntry))) return 1;
+    MXX_TRACED_COPY("covariance cache table (host to device)", ctx->stream, table.size() * sizeof(P1KeyEntry),
+                    HIP_TRY(hipMemcpyAsync(d_table.ptr, table.data(), table.size() * sizeof(P1KeyEntry), hipMemcpyHostToDevice, ctx->stream)));
+    PreimageCall call{ctx, res[0], public_matrices[0], cache0, base_bits, sigma_large, d, dk};
+    call.entry = who;
+    for (size_t g = 0; g < groups.size(); ++g) {
+        keyed[g].d_keys = static_cast<const P1KeyEntry *>(d_table.ptr) + g * kGroupMax;
+        const int rc = preimage_group(call, targets, seeds, outs, groups[g], &keyed[g]);
         if (rc) return rc;
     }
     for (size_t j = 0; j < n; ++j) outs[j]->format = GPU_POLY_FORMAT_EVAL;

@@ -622,6 +622,11 @@ static int gauss_samp_impl(GpuMatrix *src, uint32_t base_bits, double c, GpuRngS
 }
 
 // ---- p1 perturbation sampler -------------------------------------------------------------------
+// the segment table plus, per segment, the covariance cache of that segment's trapdoor (p1_sample_lanes_kernel, KEYED)
+struct P1KeyedSegments {
+    RngSegments segs;
+    const P1KeyEntry *keys;  // device memory, [segs.count]
+};
 template <typename W>
 __global__ void p1_covariance_kernel(const W *__restrict__ a_mat, const W *__restrict__ b_mat,
                                      const W *__restrict__ d_mat, uint32_t d, uint32_t L, uint32_t N, uint64_t q0,
@@ -731,16 +736,39 @@ __global__ void p1_divisor_kernel(KarneyDivisor *__restrict__ div, const double 
 // SEG: the columns are independently seeded segments (rng.h, RngSegments).  The launcher picks a lane count that keeps
 // every wave's chunk inside one column (64 * per_lane divides n), so the segment's sub-key and the column's index inside
 // its segment - the stream's first word - are per-wave scalars.
-template <typename W, int MAXM, int SV, bool SEG = false>
+// KEYED (with SEG): every segment also names its own covariance cache (gpupoly_trapdoor_preimage_keyed: the requests of
+// one launch belong to several trapdoors).  The three cache arrays of segment j come from a table in device memory
+// (P1KeyEntry, common.h) - one wave-uniform 24-byte read per wave - and replace the kernel's three pointer arguments,
+// which are not read in this form.
+template <bool SEG, bool KEYED>
+using P1SegArg = typename std::conditional<KEYED, P1KeyedSegments, SegArg<SEG>>::type;
+template <typename T>
+__device__ __forceinline__ const T *wave_uniform_ptr(const void *p) {
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
+    return reinterpret_cast<const T *>((static_cast<uint64_t>(hi) << 32) | lo);
+}
+template <typename W, int MAXM, int SV, bool SEG = false, bool KEYED = false>
 __global__ void __launch_bounds__(SAMPLER_THREADS) p1_sample_lanes_kernel(int64_t *__restrict__ stage, const W *__restrict__ tp2,
                                        const double *__restrict__ sqrt_var_base, const double *__restrict__ update_base,
                                        const KarneyDivisor *__restrict__ div_base, uint32_t m, uint32_t cols, uint32_t L,
                                        uint32_t logN, uint64_t q0, double c_scale, ChaChaKey key, size_t total,
-                                       uint32_t per_lane, uint32_t fill_every, SegArg<SEG> segs) {
+                                       uint32_t per_lane, uint32_t fill_every, P1SegArg<SEG, KEYED> segs) {
+    static_assert(SEG || !KEYED, "the keyed form is a form of the segment path");
     __shared__ uint32_t ring[SAMPLER_THREADS * RNG_RING_SLOTS];  // 128 bytes per lane: 8 KB per one-wave workgroup
     WaveChunk chunk = wave_chunk(total, per_lane);
     uint32_t seg_col0 = 0;  // SEG: first column of the chunk's segment
-    if constexpr (SEG) {
+    if constexpr (KEYED) {
+        const uint32_t col_u = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(chunk.base >> logN)));
+        const uint32_t j = rng_segment_of(segs.segs, col_u < cols ? col_u : cols - 1);
+        key = segs.segs.key[j];
+        seg_col0 = segs.segs.start[j];
+        const P1KeyEntry e = segs.keys[j];  // segment j's trapdoor: its cache arrays, wave-uniform
+        sqrt_var_base = wave_uniform_ptr<double>(e.sqrt_var);
+        update_base = wave_uniform_ptr<double>(e.update_coeff);
+        div_base = wave_uniform_ptr<KarneyDivisor>(e.karney_div);
+    } else if constexpr (SEG) {
         const uint32_t col_u = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(chunk.base >> logN)));
         const uint32_t j = rng_segment_of(segs, col_u < cols ? col_u : cols - 1);
         key = segs.key[j];
@@ -920,7 +948,8 @@ extern "C" void gpu_matrix_destroy_p1_covariance_cache(GpuP1CovarianceCache *cac
     delete cache;
 }
 
-static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp2, GpuRngSeed seed, GpuMatrix *out, const RngSegments *segs);
+static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp2, GpuRngSeed seed, GpuMatrix *out, const RngSegments *segs,
+                          const P1KeyEntry *d_keys = nullptr);
 
 extern "C" int gpu_matrix_sample_p1_full_cached(const GpuP1CovarianceCache *cache, const GpuMatrix *tp2,
                                                 GpuRngSeed seed, GpuMatrix *out) {
@@ -947,8 +976,25 @@ extern "C" int gpupoly_matrix_sample_p1_full_cached_segments(const GpuP1Covarian
     ABI_GUARD_END
 }
 
+// The segments entry with a covariance cache per segment (preimage.hip, gpupoly_trapdoor_preimage_keyed): `d_keys` is a
+// device table of nseg entries, entry j the three arrays of segment j's cache; `cache` is any one of them and stands for
+// what they share (context, level, dimension, widths - the caller has checked that they do).  Not an ABI entry: the table's
+// lifetime is the caller's, stream-ordered.
+int sample_p1_keyed_segments(const GpuP1CovarianceCache *cache, const P1KeyEntry *d_keys, const GpuMatrix *tp2,
+                             const GpuRngSeed *seeds, const size_t *seg_cols, size_t nseg, GpuMatrix *out) {
+    if (!cache || !d_keys || !tp2 || !out) return set_error("invalid sample_p1_keyed_segments arguments");
+    if (cache->m > 4 || cache->ctx->env.p1_simple)
+        return set_error("sample_p1_keyed_segments: unsupported: trapdoor dimension above 2 (no lane kernel)");
+    if (static_cast<size_t>(cache->ctx->N) % SAMPLER_THREADS)
+        return set_error("sample_p1_keyed_segments: unsupported: ring too small for a wave per column chunk");
+    RngSegments segs;
+    if (!rng_segments_build(segs, seeds, seg_cols, nseg, kTagP1, tp2->cols))
+        return set_error("sample_p1_keyed_segments: segments must be 1..64, non-empty and cover tp2's columns");
+    return sample_p1_impl(cache, tp2, GpuRngSeed{}, out, &segs, d_keys);
+}
+
 static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp2, GpuRngSeed seed, GpuMatrix *out,
-                          const RngSegments *segs) {
+                          const RngSegments *segs, const P1KeyEntry *d_keys) {
     {
     if (!cache || !tp2 || !out) return set_error("invalid gpu_matrix_sample_p1_full_cached arguments");
     GpuContext *ctx = cache->ctx;
@@ -986,6 +1032,12 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
                cache->update_coeff, static_cast<const KarneyDivisor *>(cache->karney_div), (uint32_t)m,           \
                (uint32_t)cols, L, ctx->logN, ctx->moduli[0], c_scale, key, total, per_lane,                       \
                static_cast<uint32_t>(ctx->env.sampler_fill_every ? ctx->env.sampler_fill_every : 2), SEGARG)
+#define LAUNCH_P1KEYED(WT, MAXM, SV) /* the cache arrays come from the table: the three pointer arguments are not read */ \
+    MXX_LAUNCH((p1_sample_lanes_kernel<WT, MAXM, SV, true, true>), dim3(lblocks), dim3(SAMPLER_THREADS), 0, ctx->stream, \
+               static_cast<int64_t *>(stage), static_cast<const WT *>(words_ptr(tp2)), static_cast<const double *>(nullptr), \
+               static_cast<const double *>(nullptr), static_cast<const KarneyDivisor *>(nullptr), (uint32_t)m,   \
+               (uint32_t)cols, L, ctx->logN, ctx->moduli[0], c_scale, key, total, per_lane,                       \
+               static_cast<uint32_t>(ctx->env.sampler_fill_every ? ctx->env.sampler_fill_every : 2), keyed_segs)
 #define LAUNCH_P1L(WT, MAXM)                                                                                      \
     do {                                                                                                          \
         uint32_t per_lane =                                                                                       \
@@ -993,7 +1045,11 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
         if (segs) /* a divisor of n / 64: every wave's chunk inside one column, i.e. inside one segment */        \
             while ((static_cast<size_t>(N) / SAMPLER_THREADS) % per_lane) --per_lane;                             \
         const unsigned lblocks = static_cast<unsigned>((total + SAMPLER_THREADS * per_lane - 1) / (SAMPLER_THREADS * per_lane)); \
-        if (segs) {                                                                                               \
+        if (segs && d_keys) {                                                                                     \
+            const P1KeyedSegments keyed_segs{*segs, d_keys};                                                      \
+            if (per_lane == 1) LAUNCH_P1KEYED(WT, MAXM, 1);                                                       \
+            else LAUNCH_P1KEYED(WT, MAXM, KARNEY_SERVICES);                                                       \
+        } else if (segs) {                                                                                        \
             if (per_lane == 1) LAUNCH_P1K(WT, MAXM, 1, true, *segs);                                              \
             else LAUNCH_P1K(WT, MAXM, KARNEY_SERVICES, true, *segs);                                              \
         } else if (per_lane == 1) {                                                                               \
@@ -1010,6 +1066,7 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
             else LAUNCH_P1L(uint32_t, 4);
         }
 #undef LAUNCH_P1L
+#undef LAUNCH_P1KEYED
 #undef LAUNCH_P1K
         const hipError_t le = hipGetLastError();
         int lrc = le == hipSuccess ? launch_scatter_i64(out, static_cast<const int64_t *>(stage)) : 0;

@@ -503,6 +503,47 @@ class GpuDCRTPolyTrapdoorSampler:
             raise _ffi.GpuPolyError(f"gpupoly_trapdoor_preimage_many failed: {msg}")
         return outs
 
+    keyed_calls = 0  # calls that reached gpupoly_trapdoor_preimage_keyed (tests: the default path never does)
+
+    def preimage_many_keys(self, params, keys, key_of, targets, _seeds=None) -> list:
+        """Requests that do not all share a trapdoor through ONE library call (`gpupoly_trapdoor_preimage_keyed`):
+        `keys` = [(trapdoor, public matrix), ...] of `params`' context, request j = (keys[key_of[j]], targets[j]).  Every
+        request gets the matrix `preimage` gives it alone under its seed triple (drawn here request by request in the
+        order given, as the one-by-one loop would), whatever the spread over the keys: one sequence of launches for all
+        keys, no worker contexts, no replicas, no copies.  On the entry's "unsupported" error (a shape the segmented
+        samplers do not cover, keys of different Gaussian widths) every key's requests go through `preimage_many_abi`
+        with the seeds already drawn."""
+        from . import _ffi
+
+        keys, key_of, targets = list(keys), [int(k) for k in key_of], list(targets)
+        assert len(key_of) == len(targets), "one key index per target"
+        seeds = list(_seeds) if _seeds is not None else [self._draw_seeds() for _ in targets]
+        if not targets:
+            return []
+        assert keys and all(0 <= k < len(keys) for k in key_of), "key_of must index keys"
+        n, k_digits = params.ring_dimension(), params.modulus_digits()
+        caches = []
+        for td, a in keys:
+            s = preimage_smoothing_parameter(self.base, self.sigma, a.row_size(), n, k_digits)
+            caches.append(td.p1_covariance_cache(self.c, s, self.sigma))
+        outs = [GpuDCRTPolyMatrix(params, keys[k][0].re.row_size() + keys[k][0].re.col_size(), t.col_size(), keys[k][1].level, True)
+                for k, t in zip(key_of, targets)]
+        flat = (_ffi.GpuRngSeed * (3 * len(seeds)))(*[x for triple in seeds for x in triple])
+        raw = GpuDCRTPolyMatrix._raw_array
+        type(self).keyed_calls += 1
+        st = _ffi.lib().gpupoly_trapdoor_preimage_keyed(raw([td.re for td, _ in keys]), raw(caches), raw([a for _, a in keys]), len(keys),
+                                                        params.base_bits(), (_ffi.C.c_uint32 * len(key_of))(*key_of), raw(targets),
+                                                        len(targets), flat, raw(outs))
+        if st != 0:
+            msg = _ffi.last_error_string()
+            if "unsupported" not in msg:
+                raise _ffi.GpuPolyError(f"gpupoly_trapdoor_preimage_keyed failed: {msg}")
+            for k, (td, a) in enumerate(keys):
+                mine = [j for j, kk in enumerate(key_of) if kk == k]
+                for j, x in zip(mine, self.preimage_many_abi(params, td, a, [targets[j] for j in mine], _seeds=[seeds[j] for j in mine])):
+                    outs[j] = x
+        return outs
+
     def preimage_batched_sharded(self, requests):
         """`preimage_batched_sharded` (gpu.rs:371-397): requests = [(entry_idx, params, trapdoor, A, target)];
         every request runs on the device context its params name, and the contexts work concurrently - the
@@ -511,6 +552,7 @@ class GpuDCRTPolyTrapdoorSampler:
         parallel), and within a context the requests that share a trapdoor and a public matrix are sampled TOGETHER
         (`preimage_many`): same outputs as one by one, one sequence of launches.  Results come back in request order,
         like rayon's collect."""
+        import os
         from concurrent.futures import ThreadPoolExecutor
 
         groups: dict = {}
@@ -527,6 +569,16 @@ class GpuDCRTPolyTrapdoorSampler:
             for pos, (idx, p, td, a, t) in items:
                 by_key.setdefault((id(td), id(a)), []).append((pos, idx, p, td, a, t))
             groups_ = list(by_key.values())
+            if len(groups_) > 1 and os.environ.get("MXX_PREIMAGE_MIXED", "") == "abi":
+                # all key groups of this context in ONE library call (`preimage_many_keys`) instead of worker contexts
+                p = groups_[0][0][2]
+                members = [m for g in groups_ for m in g]
+                key_of = [k for k, g in enumerate(groups_) for _ in g]
+                outs = self.preimage_many_keys(p, [(g[0][3], g[0][4]) for g in groups_], key_of, [m[5] for m in members],
+                                               _seeds=[drawn[m[0]] for m in members])
+                for (pos, idx, *_), x in zip(members, outs):
+                    results[pos] = (idx, x)
+                return
             nworkers = min(preimage_workers(), len(groups_))
             if nworkers <= 1:
                 for members in groups_:
