@@ -525,6 +525,78 @@ int gpupoly_trapdoor_preimage_keyed(const GpuMatrix *const *res, const GpuP1Cova
                                     const GpuMatrix *const *public_matrices, size_t nkeys, uint32_t base_bits,
                                     const uint32_t *key_of, const GpuMatrix *const *targets, size_t n,
                                     const GpuRngSeed *seeds, GpuMatrix *const *outs);
+/* ---- the producer of those requests (extension).  The GGH15 LUT preprocessing asks for one preimage per LUT
+ * row and column chunk (sample_lut_preimages_gpu, src/lookup/ggh15/pubkey_gpu.rs:540-640; CPU twin pubkey.rs:241-275,441-460)
+ * and builds every target with build_lut_preimage_target_chunk_gpu (pubkey_gpu.rs:379-415): a slice, a large-scalar product,
+ * a tag hash, a decomposed hash sample, two products with their adds and a mul_scalar - per row.
+ *
+ * Decomposed blocks: G^-1 of nblk independently seeded samples in one call.  Replaces the per-tag
+ * sample_hash_decomposed_columns of pubkey_gpu.rs:398-407 (and :495-504, poly_encoding_gpu.rs:453-462) for callers that
+ * hold many tags.  out is (src_rows * k) x (nblk * c), c = out->cols / nblk, k as for gpupoly_matrix_decompose_rows, and
+ *   out = [D_0 | D_1 | ... | D_(nblk-1)],
+ * D_t being, bit for bit, what gpupoly_matrix_sample_decomposed_window(seeds[t], base_bits, small, src_rows, full_ncol,
+ * col_offset, row_start = 0) writes into a (src_rows * k) x c matrix: every block is the window [col_offset, col_offset + c)
+ * of its own conceptual src_rows x full_ncol matrix, a polynomial's stream id its position there (row * full_ncol +
+ * col_offset + local column).  `out` keeps the format it was created with, EVAL or COEFF.  The seeded-blocks sampler
+ * (gpupoly_matrix_sample_distribution_blocks, whose table gains the window) writes the coefficients into scratch from the
+ * context's allocator - no transform, no pack - and, G^-1 working column by column, ONE digit transform over the wide
+ * scratch gives every block: sub-keys, samples, digits; no launch count depends on nblk.  `seeds` are read before the call
+ * returns.  Enqueued on the context's stream; the host does not block.  An `out` without polynomials succeeds with nothing
+ * launched and is tagged EVAL.
+ * Overlap: the only matrix is `out`; nothing can overlap.
+ * Refused, with nothing launched and `out` (contents AND tag) untouched, the message naming this entry: a null `out` or
+ * `seeds`; nblk == 0 or above 2^20; an invalid dist_type; base_bits of 0 or >= 63; out->cols not a multiple of nblk; a window
+ * past full_ncol; out->rows != src_rows * k; src_rows * full_ncol beyond the samplers' 48-bit stream ids.  Refused likewise
+ * with "unsupported" in the text: the Gaussian distribution; a context created under MXX_HIP_RNG_COMPAT=reference.        */
+int gpupoly_matrix_sample_decomposed_blocks(GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, size_t nblk,
+                                            uint32_t base_bits, int small, size_t src_rows, size_t full_ncol,
+                                            size_t col_offset);
+/* The same with seeds[t] = hash_seed_for_matrix(key, tag_t) derived on the device by one launch in front, as
+ * gpupoly_matrix_sample_hash_blocks does: the seeds never reach the host.  Refused likewise, plus everything
+ * gpupoly_hash_seeds refuses of `tags`.                                                                              */
+int gpupoly_matrix_sample_hash_decomposed_blocks(GpuMatrix *out, int dist_type, const GpuHashTags *tags, size_t nblk,
+                                                 uint32_t base_bits, int small, size_t src_rows, size_t full_ncol,
+                                                 size_t col_offset);
+/* The preimage targets of T LUT rows of ONE column chunk: replaces build_lut_preimage_target_chunk_gpu
+ * (src/lookup/ggh15/pubkey_gpu.rs:379-415) for the rows of a wave (the loop body of :590-613); the outputs are the `targets`
+ * of gpupoly_trapdoor_preimage_many.  With c = outs[0]->cols, c0 = col_start, m = d * k, k = dpt * (level + 1):
+ *   outs[t] = W_id[:, c0..c0+c) + W_gy * G^-1(G_d[:, c0..c0+c) o y_t) + (W_v + idx_t * W_vx) * G^-1(U_t[:, c0..c0+c)),
+ * U_t the d x m uniform matrix under hash_seed_for_matrix(key, tag_t), y_t and idx_t constant polynomials.
+ *   w_identity, w_gy, w_v, w_vx   d x m, EVAL, one context and one level (it may be below the top)
+ *   outs[t]      d x c, made by the caller, tagged EVAL on success
+ *   y_words      host memory: T integers of words_per_y little-endian 64-bit words each, reduced mod every q_l
+ *                (gpupoly_matrix_load_coeff_words's rule; from_elem_to_constant of the reference)
+ *   idx          host memory: T row indices, reduced likewise (from_usize_to_constant)
+ *   tags         T tags (GpuHashTags above), e.g. the DECIMAL form with prefix "ggh15_lut_v_idx_<lut_id>_"
+ * Everything is exact arithmetic on canonical residues, so the result equals the reference's sequence - slice,
+ * gpu_matrix_fill_gadget, gpu_matrix_mul_scalar, decompose, the decomposed hash sample, the products and adds - bit for
+ * bit.  Column c0 + cc of G_d is (j, tw, e); its product with the constant y_t has one non-zero residue, whose digits are
+ * constants, so the large-scalar term is sum_{e' < dpt} weight(t, cc, e') * W_gy[i, (j, tw, e')] in every limb, weight = digit
+ * e' of (y_t mod q_tw) * B^e mod q_tw; and the constant idx_t commutes with the product.  The rows go in groups whose digit
+ * scratch m x (Tg * c) stays under 1 GiB (gpupoly_trapdoor_preimage_many's rule for p2); per group: one staged copy of the
+ * rows' table (output pointers, idx_t and y_t mod q_l), the decomposed-blocks sample [V_0 | V_1 | ...], ONE product of the
+ * stacked [W_v; W_vx] (2d x m, copied once per call) against it, one kernel for the T*c*L*dpt weights, one combine kernel
+ * that forms every word with one lazy accumulator (dpt + 1 products, reduced once) and writes it straight into its output.
+ * The launches of a group do not depend on T: no per-row upload, launch or synchronisation.  Scratch comes from the context's
+ * allocator and is released stream-ordered; the host does not block; PACKED24 operands are unpacked first; T = 0 succeeds
+ * with nothing launched.
+ * Overlap: an outs[t] must overlap no operand and no other output, row views included (the message contains "overlap").
+ * Refused, with nothing launched and every output (residues AND tag) untouched, everything checked for every t before the
+ * first launch, the message naming this entry: a null array with T > 0, a null operand or outs[t]; a context, level or
+ * shape mismatch (operands d x m, outputs d x c); an operand not in EVAL form; col_start + c > m; outputs of different
+ * widths; words_per_y == 0; base_bits of 0 or >= 63; everything gpupoly_hash_seeds refuses of `tags`; the overlaps above.
+ * Refused likewise with "unsupported" in the text: a context created under MXX_HIP_RNG_COMPAT=reference.              */
+int gpupoly_matrix_lut_targets(GpuMatrix *const *outs, size_t nrows_T, const GpuMatrix *w_identity, const GpuMatrix *w_gy,
+                               const GpuMatrix *w_v, const GpuMatrix *w_vx, size_t col_start, uint32_t base_bits,
+                               const uint64_t *y_words, size_t words_per_y, const uint64_t *idx, const GpuHashTags *tags);
+/* Test instrument: the weights and the combine kernel of gpupoly_matrix_lut_targets alone, with [top; bottom] GIVEN -
+ * `product` is 2d x (T * c), EVAL, row t's columns at t * c - instead of sampled and multiplied:
+ *   outs[t] = W_id[:, c0..c0+c) + W_gy * G^-1(G_d[:, c0..c0+c) o y_t) + product[0..d, t*c..) + idx_t * product[d..2d, t*c..).
+ * It lets a test reach the lazy accumulator's bound with operands no sampler produces (every residue q - 1).  One group
+ * whatever T; arguments, overlap rule and refusals as above (`product` counts as an operand; no tags, any keying).     */
+int gpupoly_matrix_lut_targets_combine(GpuMatrix *const *outs, size_t nrows_T, const GpuMatrix *w_identity,
+                                       const GpuMatrix *w_gy, const GpuMatrix *product, size_t col_start, uint32_t base_bits,
+                                       const uint64_t *y_words, size_t words_per_y, const uint64_t *idx);
 /* Exact scale-and-round of every coefficient (extension): coefficient k of out[i][j] becomes
  *   floor((t * c + h) / Q) mod t,   h = round_half ? floor(Q/2) : 0,
  * c the coefficient of in[i][j] as coeffs() gives it (in [0, Q)), Q the context's FULL modulus; written as its residue

@@ -52,3 +52,4 @@ from .trapdoor import (  # noqa: F401
     preimage_c,
     preimage_smoothing_parameter,
 )
+from . import lookup  # noqa: F401,E402

@@ -332,6 +332,20 @@ int pack24_store(GpuMatrix *m, bool ntt);
 int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t full_ncol, size_t col_offset, bool keep_coeff,
                 size_t row_offset = 0, uint32_t tower_first = 0, uint32_t tower_count = 0);
 
+// sampling.hip: the seeded-blocks sampler behind gpupoly_matrix_sample_distribution_blocks / _hash_blocks (seeds or tags,
+// the other null).  With `win` it fills a caller's coefficient scratch for the decomposed blocks (decompose.hip): `out` is
+// rows x (nblk * cols), block j columns [j cols, (j + 1) cols) = the window [col_offset, col_offset + cols) of a rows x
+// full_ncol matrix under block j's seed; left in the coefficient domain, in words
+struct RngBlockWindow {
+    size_t cols, full_ncol, col_offset;
+};
+int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, const GpuHashTags *tags,
+                       size_t nblk, int layout, const size_t *seg_cols, const RngBlockWindow *win);
+// decompose.hip: both decomposed-blocks entries in `entry`'s name (seeds or tags, the other null)
+int sample_decomposed_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_type, const GpuRngSeed *seeds,
+                                  const GpuHashTags *tags, size_t nblk, uint32_t base_bits, int small, size_t src_rows, size_t full_ncol,
+                                  size_t col_offset);
+
 // hash_seed.hip: tags to seeds on the device.  hash_tags_check refuses a malformed GpuHashTags in `entry`'s name and tells
 // the TABLE form's byte count; the TABLE form's offsets and bytes are staged as hash_tags_staged_words 8-byte words (none in
 // the indexed forms) which the caller copies to `d_staged` on the stream before launch_hash_seeds writes d_seeds[0 .. ntags)

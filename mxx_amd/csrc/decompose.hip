@@ -448,3 +448,64 @@ extern "C" int gpupoly_matrix_sample_decomposed_window(GpuMatrix *out, int dist_
     return rc;
     ABI_GUARD_END
 }
+
+// ---- decomposed blocks: G^-1 of many independently seeded samples in one call -------------------
+// out = [D_0 | D_1 | ...], D_t = what gpupoly_matrix_sample_decomposed_window writes for the whole decomposition (row_start
+// 0) of the window [col_offset, col_offset + c) under block t's seed.  The seeded-blocks sampler (sampling.hip) writes the
+// src_rows x (nblk c) coefficients into scratch, its table resolving a polynomial to (block, position in the block's
+// conceptual src_rows x full_ncol matrix); G^-1 works column by column, so one decompose_core over the wide scratch gives
+// every block.  The launches are the sampler's (hash, sub-keys, samples) and the digit transform's: none depends on nblk.
+int sample_decomposed_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_type, const GpuRngSeed *seeds,
+                                  const GpuHashTags *tags, size_t nblk, uint32_t base_bits, int small, size_t src_rows, size_t full_ncol,
+                                  size_t col_offset) {
+    const auto refuse = [entry](const char *what) { return set_error(std::string(entry) + what); };
+    if (!out) return refuse(": null matrix");
+    if (base_bits == 0 || base_bits >= 63) return refuse(": base_bits must be in 1..62");
+    if (nblk == 0 || nblk > (size_t(1) << 20)) return refuse(": the block count must be 1..2^20");
+    if (out->cols % nblk) return refuse(": the matrix's columns are not a multiple of the block count");
+    const size_t c = out->cols / nblk;
+    if (col_offset > full_ncol || c > full_ncol - col_offset) return refuse(": column window past full_ncol");
+    const size_t k = window_digit_count(out, base_bits, small);
+    if (src_rows > ~size_t(0) / k || out->rows != src_rows * k) return refuse(": the matrix's rows must be src_rows times the digit count");
+    // the stream ids of a block's whole conceptual matrix (sample_impl's rule)
+    if (full_ncol && src_rows > ((size_t(1) << 48) - 2) / full_ncol) return refuse(": matrix too large for the RNG's 48-bit stream ids");
+    GpuContext *ctx = out->ctx;
+    GpuMatrix src;
+    src.ctx = ctx;
+    src.level = out->level;
+    src.rows = src_rows;
+    src.cols = out->cols;
+    src.bytes = src.rows * src.cols * matrix_limbs(out) * static_cast<size_t>(ctx->N) * static_cast<size_t>(ctx->word_bytes);
+    src.borrowed = true;  // the block below is this scope's: never swapped for packed storage
+    const RngBlockWindow win{c, full_ncol, col_offset};
+    CtxBlock block(ctx);
+    if (matrix_polys(&src)) {  // an empty output still goes through the sampler's refusals, which launch nothing
+        if (ctx_activate(ctx)) return 1;
+        if (block.alloc(src.bytes)) return 1;
+        src.storage = block.ptr;
+    }
+    if (int rc = sample_blocks_impl(entry, hashed, &src, dist_type, seeds, tags, nblk, 0, nullptr, &win)) return rc;
+    if (matrix_polys(&src) == 0) {
+        out->format = GPU_POLY_FORMAT_EVAL;
+        return 0;
+    }
+    return decompose_core(&src, base_bits, small != 0, 0, out);
+}
+
+extern "C" int gpupoly_matrix_sample_decomposed_blocks(GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, size_t nblk,
+                                                       uint32_t base_bits, int small, size_t src_rows, size_t full_ncol,
+                                                       size_t col_offset) {
+    ABI_GUARD_BEGIN
+    return sample_decomposed_blocks_impl("gpupoly_matrix_sample_decomposed_blocks", false, out, dist_type, seeds, nullptr, nblk, base_bits, small,
+                                         src_rows, full_ncol, col_offset);
+    ABI_GUARD_END
+}
+
+extern "C" int gpupoly_matrix_sample_hash_decomposed_blocks(GpuMatrix *out, int dist_type, const GpuHashTags *tags, size_t nblk,
+                                                            uint32_t base_bits, int small, size_t src_rows, size_t full_ncol,
+                                                            size_t col_offset) {
+    ABI_GUARD_BEGIN
+    return sample_decomposed_blocks_impl("gpupoly_matrix_sample_hash_decomposed_blocks", true, out, dist_type, nullptr, tags, nblk, base_bits,
+                                         small, src_rows, full_ncol, col_offset);
+    ABI_GUARD_END
+}

@@ -757,11 +757,16 @@ static inline bool rng_segments_build(RngSegments &out, const GpuRngSeed *seeds,
 //   stacked (starts == nullptr): row t of the nblk x cols matrix is block t, the local index is the column - a division;
 //   columns: block j is columns [starts[j], starts[j + 1]) of every row, the local index row * width + local column -
 //            a binary search in `starts`.
+// A third form serves the decomposed blocks (win_cols > 0, starts == nullptr): every block is the SAME column window
+// [col_offset, col_offset + win_cols) of its own conceptual rows x full_ncol matrix, block j being columns
+// [j win_cols, (j + 1) win_cols) of every row, and the local index is the polynomial's position in that conceptual matrix,
+// row * full_ncol + col_offset + local column - sample_impl's rule for gpu_matrix_sample_distribution_columns: two divisions.
 struct RngBlockTable {
     const ChaChaKey *keys;
     const uint64_t *starts;  // columns layout: [nblk + 1], starts[nblk] = cols
     uint64_t cols;           // columns of the output matrix
     uint32_t nblk, keys_per_block;
+    uint64_t win_cols = 0, full_ncol = 0, col_offset = 0;  // the windowed form
 };
 struct RngBlockRef {
     uint32_t blk;    // the polynomial's block
@@ -773,6 +778,12 @@ struct RngBlockRef {
 __device__ __forceinline__ RngBlockRef rng_block_of(const RngBlockTable &t, uint64_t p) {
     const uint64_t row = p / t.cols, col = p - row * t.cols;
     RngBlockRef r;
+    if (t.win_cols) {
+        const uint64_t blk = col / t.win_cols;
+        r.blk = static_cast<uint32_t>(blk);
+        r.local = row * t.full_ncol + t.col_offset + (col - blk * t.win_cols);
+        return r;
+    }
     if (!t.starts) {
         r.blk = static_cast<uint32_t>(row);
         r.local = col;

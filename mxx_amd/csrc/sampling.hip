@@ -643,25 +643,26 @@ __global__ void __launch_bounds__(256) sample_small_blocks_kernel(W *__restrict_
 // the table come either from the caller (`seeds`: staged and copied with the starts) or from (key, tags) on the device
 // (`tags`: hash_seeds_kernel writes them, hash_seed.hip; the TABLE form's offsets and bytes are staged with the starts,
 // the indexed forms stage nothing).  `hashed` says which of the two the entry takes; the other is null.
-static int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, const GpuHashTags *tags,
-                              size_t nblk, int layout, const size_t *seg_cols) {
+// `win` (the decomposed blocks, decompose.hip): `out` is the caller's coefficient scratch, rows x (nblk * win->cols), every
+// block the window [col_offset, col_offset + cols) of its own rows x full_ncol matrix (the caller has checked the window);
+// `layout` and `seg_cols` are not read, and the samples stay coefficients in words: no transform, no pack, tagged COEFF.
+int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, const GpuHashTags *tags,
+                       size_t nblk, int layout, const size_t *seg_cols, const RngBlockWindow *win) {
     constexpr size_t kMaxBlocks = size_t(1) << 20, kStreamLimit = size_t(1) << 48;
     const auto refuse = [entry](const char *what) { return set_error(std::string(entry) + what); };
     if (!out) return refuse(": null matrix");
     if (!seeds && !tags) return refuse(hashed ? ": null tags" : ": null seeds");
     if (nblk == 0 || nblk > kMaxBlocks) return refuse(": the block count must be 1..2^20");
-    if (layout != GPUPOLY_BLOCKS_STACKED && layout != GPUPOLY_BLOCKS_COLUMNS) return refuse(": unknown layout");
+    if (!win && layout != GPUPOLY_BLOCKS_STACKED && layout != GPUPOLY_BLOCKS_COLUMNS) return refuse(": unknown layout");
     if (dist_type == GPU_MATRIX_DIST_GAUSS)
-        return refuse(": unsupported: the Gaussian distribution goes through gpupoly_matrix_sample_distribution_segments");
+        return refuse(win ? ": unsupported: the Gaussian distribution has no block form"
+                          : ": unsupported: the Gaussian distribution goes through gpupoly_matrix_sample_distribution_segments");
     if (dist_type < GPU_MATRIX_DIST_UNIFORM || dist_type > GPU_MATRIX_DIST_TERNARY) return refuse(": invalid dist_type");
     GpuContext *ctx = out->ctx;
     if (ctx->env.rng_compat) return refuse(": unsupported under MXX_HIP_RNG_COMPAT=reference");
-    const bool columns = layout == GPUPOLY_BLOCKS_COLUMNS;
-    if (!columns) {
-        if (seg_cols) return refuse(": the stacked layout takes no seg_cols");
-        if (out->rows != nblk) return refuse(": the stacked layout wants one row per block");
-        if (out->cols >= kStreamLimit) return refuse(": block too large for the RNG's 48-bit stream ids");
-    } else {
+    const bool columns = !win && layout == GPUPOLY_BLOCKS_COLUMNS;
+    // a window's shape, its place inside full_ncol and the stream ids of the conceptual matrix are the caller's checks
+    if (columns) {
         if (!seg_cols) return refuse(": the columns layout needs seg_cols");
         size_t at = 0, placed = 0;  // at <= out->cols
         for (size_t j = 0; j < nblk; ++j) {
@@ -673,6 +674,10 @@ static int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, in
             ++placed;
         }
         if (placed != nblk || at != out->cols) return refuse(": the blocks' widths must sum to the matrix's columns");
+    } else if (!win) {
+        if (seg_cols) return refuse(": the stacked layout takes no seg_cols");
+        if (out->rows != nblk) return refuse(": the stacked layout wants one row per block");
+        if (out->cols >= kStreamLimit) return refuse(": block too large for the RNG's 48-bit stream ids");
     }
     size_t tag_bytes = 0;
     if (tags && hash_tags_check(entry, tags, nblk, &tag_bytes)) return 1;
@@ -722,8 +727,13 @@ static int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, in
     MXX_LAUNCH(derive_block_subkeys_kernel, item_grid(nblk * per_block, 256), dim3(256), 0, ctx->stream, d_keys, d_seeds, tag, nblk, per_block,
                uniform ? 1u : 0u);
     HIP_TRY(hipGetLastError());
-    out->format = GPU_POLY_FORMAT_EVAL;
-    const RngBlockTable table{d_keys, columns ? d_starts : nullptr, out->cols, static_cast<uint32_t>(nblk), per_block};
+    out->format = win ? GPU_POLY_FORMAT_COEFF : GPU_POLY_FORMAT_EVAL;
+    RngBlockTable table{d_keys, columns ? d_starts : nullptr, out->cols, static_cast<uint32_t>(nblk), per_block};
+    if (win) {
+        table.win_cols = win->cols;
+        table.full_ncol = win->full_ncol;
+        table.col_offset = win->col_offset;
+    }
     const size_t threads = polys * per_block * groups;
     const dim3 blocks = item_grid(threads, 256);
     MXX_TRACE_BYTES(static_cast<double>(out->bytes));  // no input to speak of: the residues written once
@@ -739,6 +749,7 @@ static int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, in
             MXX_LAUNCH(sample_small_blocks_kernel<uint32_t>, blocks, dim3(256), 0, ctx->stream, static_cast<uint32_t *>(words), ctx->d_limbs, table, polys, L, N, groups, dist_type);
     }
     HIP_TRY(hipGetLastError());
+    if (win) return 0;
     // as the plain entry finishes: samples are coefficients, callers get EVAL; a packable uniform sample is stored packed
     if (uniform && pack24_eligible(out)) return pack24_store(out, true);
     return launch_ntt(ctx, words, polys * L, static_cast<int>(L), false);
@@ -747,14 +758,14 @@ static int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, in
 extern "C" int gpupoly_matrix_sample_distribution_blocks(GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, size_t nblk, int layout,
                                                          const size_t *seg_cols) {
     ABI_GUARD_BEGIN
-    return sample_blocks_impl("gpupoly_matrix_sample_distribution_blocks", false, out, dist_type, seeds, nullptr, nblk, layout, seg_cols);
+    return sample_blocks_impl("gpupoly_matrix_sample_distribution_blocks", false, out, dist_type, seeds, nullptr, nblk, layout, seg_cols, nullptr);
     ABI_GUARD_END
 }
 
 extern "C" int gpupoly_matrix_sample_hash_blocks(GpuMatrix *out, int dist_type, const GpuHashTags *tags, size_t nblk, int layout,
                                                  const size_t *seg_cols) {
     ABI_GUARD_BEGIN
-    return sample_blocks_impl("gpupoly_matrix_sample_hash_blocks", true, out, dist_type, nullptr, tags, nblk, layout, seg_cols);
+    return sample_blocks_impl("gpupoly_matrix_sample_hash_blocks", true, out, dist_type, nullptr, tags, nblk, layout, seg_cols, nullptr);
     ABI_GUARD_END
 }
 

@@ -2183,6 +2183,75 @@ class GpuDCRTPolyMatrix:
         del keep
         return out
 
+    @classmethod
+    def _decomposed_blocks_out(cls, params, nblk, nrow, col_len, small, is_ntt, level):
+        level = params.crt_depth() - 1 if level is None else level
+        dpt = -(-params.crt_bits() // params.base_bits())
+        k = dpt if small else dpt * (level + 1)
+        return cls(params, nrow * k, nblk * col_len, level, is_ntt)
+
+    @classmethod
+    def sample_decomposed_blocks(cls, params, seeds, nrow, total_ncol, col_start, col_len, dist: int, small=False, is_ntt=True,
+                                 level=None) -> "GpuDCRTPolyMatrix":
+        """[D_0 | D_1 | ...] with D_t == sample_distribution_decomposed_window(params, nrow, total_ncol, col_start, col_len, dist,
+        0, seeds[t], small, is_ntt=is_ntt, level=level): G^-1 of the same column window of len(seeds) independently seeded
+        nrow x total_ncol matrices in one call (gpupoly_matrix_sample_decomposed_blocks), the launches
+        not depending on len(seeds).  Uniform / bit / ternary; raises GpuPolyError (text contains "unsupported") for the
+        Gaussian distribution and under MXX_HIP_RNG_COMPAT=reference."""
+        seeds = list(seeds)
+        out = cls._decomposed_blocks_out(params, len(seeds), nrow, col_len, small, is_ntt, level)
+        arr = (GpuRngSeed * max(len(seeds), 1))(*seeds)
+        st = _ffi.lib().gpupoly_matrix_sample_decomposed_blocks(out.raw, dist, arr, len(seeds), params.base_bits(), 1 if small else 0, nrow,
+                                                                total_ncol, col_start)
+        check_status(st, "gpupoly_matrix_sample_decomposed_blocks")
+        if out.nrow == 0 or out.ncol == 0:
+            out.is_ntt = True  # an empty result is tagged EVAL
+        return out
+
+    @classmethod
+    def sample_hash_decomposed_blocks(cls, params, key: bytes, tags, nrow, total_ncol, col_start, col_len, dist: int, small=False,
+                                      is_ntt=True, level=None, hash_name: str = "keccak256") -> "GpuDCRTPolyMatrix":
+        """`sample_decomposed_blocks` with seeds[t] = hash_seed_for_matrix(key, tags[t], hash_name) derived on the device
+        (gpupoly_matrix_sample_hash_decomposed_blocks): tags in (an `IndexedTags` or byte strings, as `sample_hash_blocks`
+        takes them), no seeds on the host."""
+        arg, keep, count = hash_tags_arg(key, tags, hash_name)
+        out = cls._decomposed_blocks_out(params, count, nrow, col_len, small, is_ntt, level)
+        st = _ffi.lib().gpupoly_matrix_sample_hash_decomposed_blocks(out.raw, dist, C.byref(arg), count, params.base_bits(), 1 if small else 0,
+                                                                     nrow, total_ncol, col_start)
+        check_status(st, "gpupoly_matrix_sample_hash_decomposed_blocks")
+        del keep
+        if out.nrow == 0 or out.ncol == 0:
+            out.is_ntt = True
+        return out
+
+    @staticmethod
+    def lut_targets(w_identity, w_gy, w_v, w_vx, col_start, col_len, ys, idxs, key: bytes, tags, hash_name: str = "keccak256") -> list:
+        """The preimage targets of len(ys) LUT rows of the column chunk [col_start, col_start + col_len) in one call
+        (gpupoly_matrix_lut_targets):
+            W_id[:, chunk] + W_gy G^-1(G_d[:, chunk] o ys[t]) + (W_v + idxs[t] W_vx) G^-1(U_t[:, chunk]),
+        U_t the d x m uniform matrix under hash_seed_for_matrix(key, tags[t]); ys[t], idxs[t] non-negative integers (ys of any
+        size, idxs below 2^64).  The four operands are d x m EVAL matrices of one level."""
+        ys, idxs = [int(y) for y in ys], [int(i) for i in idxs]
+        arg, keep, count = hash_tags_arg(key, tags, hash_name)
+        assert len(ys) == len(idxs) == count, "lut_targets: one y, one index and one tag per row"
+        p = w_identity.params
+        outs = [GpuDCRTPolyMatrix(p, w_identity.nrow, col_len, w_identity.level, True) for _ in range(count)]
+        if count == 0:
+            return outs
+        words = [GpuDCRTPolyMatrix._int_words(y) for y in ys]
+        wpy = max(len(w) for w in words)
+        y_arr = np.zeros((count, wpy), dtype=np.uint64)
+        for t, w in enumerate(words):
+            y_arr[t, : len(w)] = w
+        i_arr = np.array(idxs, dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        st = _ffi.lib().gpupoly_matrix_lut_targets(GpuDCRTPolyMatrix._raw_array(outs), count, w_identity.raw, w_gy.raw, w_v.raw, w_vx.raw,
+                                                   col_start, p.base_bits(), y_arr.ctypes.data_as(u64p), wpy, i_arr.ctypes.data_as(u64p),
+                                                   C.byref(arg))
+        check_status(st, "gpupoly_matrix_lut_targets")
+        del keep
+        return outs
+
     @staticmethod
     def sample_p1_full_cached_segments(cache: GpuP1CovarianceCache, tp2, seeds, seg_cols) -> "GpuDCRTPolyMatrix":
         """`sample_p1_full_cached` over column segments with a seed each (tp2 is taken to the coefficient domain in place)."""

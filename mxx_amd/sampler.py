@@ -272,6 +272,32 @@ class GpuDCRTPolyHashSampler:
             outs.extend(wide.split_columns(widths))
         return outs
 
+    def sample_hash_decomposed_columns_many(self, params, key: bytes, tags, nrow, total_ncol, col_start, col_len, dist: DistType) -> list:
+        """== [sample_hash_decomposed_columns(params, key, tag, nrow, total_ncol, col_start, col_len, dist) for tag in tags]:
+        the same column chunk of many tags' decomposed matrices - the V of every LUT row of a wave
+        (src/lookup/ggh15/pubkey_gpu.rs:398-407).  Uniform / bit / ternary under a Keccak hash: ONE
+        gpupoly_matrix_sample_hash_decomposed_blocks call per 2^20 tags and one split_columns per 64
+        of them.  The Gaussian distribution, other hashes and the library's "unsupported" answer (MXX_HIP_RNG_COMPAT=reference) go tag by tag:
+        the same matrices either way."""
+        tags = tags if isinstance(tags, IndexedTags) else list(tags)
+        count = len(tags)
+        if dist.kind != "gauss" and self._on_device() and 0 < count <= 1 << 20:
+            try:
+                out = GpuDCRTPolyMatrix.sample_hash_decomposed_blocks(params, key, tags, nrow, total_ncol, col_start, col_len, dist.as_ffi(),
+                                                                      hash_name=self.hash_name)
+            except _ffi.GpuPolyError as e:
+                if "unsupported" not in str(e):
+                    raise
+                out = None
+            if out is not None:
+                parts = []
+                for at in range(0, count, 64):
+                    width = min(64, count - at)
+                    piece = out if width == count else out.slice_columns(at * col_len, (at + width) * col_len)
+                    parts.extend(piece.split_columns([col_len] * width))
+                return parts
+        return [self.sample_hash_decomposed_columns(params, key, tag, nrow, total_ncol, col_start, col_len, dist) for tag in tags]
+
     def sample_hash_stacked(self, params, key: bytes, tags, nrow, ncol, dist: DistType) -> GpuDCRTPolyMatrix:
         """The len(tags) x (nrow * ncol) matrix whose row t is sample_hash(params, key, tags[t], nrow, ncol, dist) in
         row-major order, sampled in one stacked-layout call - under a Keccak hash with the tags hashed on the device, no seeds
