@@ -381,7 +381,7 @@ int gpupoly_matrix_all_gather_columns(GpuComm *comm, const GpuMatrix *const *loc
  * few-column targets against one trapdoor).  A matrix is read as the column-wise concatenation of `nseg` segments
  * (1..64), segment j = the next seg_cols[j] columns, with its own seed seeds[j]; the columns of segment j come out
  * bit for bit as the plain entry point writes them for a matrix made of those columns alone under seeds[j] (every
- * element's stream is keyed by its position inside its segment).  Gaussian distribution / trapdoor dimension <= 2 /
+ * element's stream is keyed by its position inside its segment).  Gaussian distribution / trapdoor dimension <= 4 /
  * at most four digits per tower / n a multiple of 64 (128 for _sample_distribution_segments); anything else returns
  * an error whose text contains "unsupported" and the caller issues the requests one by one.                      */
 int gpupoly_matrix_sample_distribution_segments(GpuMatrix *out, int dist_type, double sigma, const GpuRngSeed *seeds,
@@ -494,7 +494,7 @@ int gpupoly_matrix_split_columns(const GpuMatrix *src, GpuMatrix *const *blocks,
  * stream-ordered; the host does not block.  Zero-column requests give zero-column outputs; n = 0 does nothing.
  * A refused call launches nothing and writes no output, not even a format tag: context or level mismatch, wrong
  * shapes, a target not in EVAL form, an output that aliases an input or another output.  Shapes the segmented
- * samplers do not cover (n not a multiple of 128, d > 2, more than four digits per tower, MXX_HIP_RNG_COMPAT=reference,
+ * samplers do not cover (n not a multiple of 128, d > 4, more than four digits per tower, MXX_HIP_RNG_COMPAT=reference,
  * MXX_HIP_P1=simple) are refused with an error whose text contains "unsupported": issue those requests one by one. */
 int gpupoly_trapdoor_preimage_many(const GpuMatrix *re, const GpuP1CovarianceCache *cache, const GpuMatrix *public_matrix,
                                    uint32_t base_bits, const GpuMatrix *const *targets, size_t n, const GpuRngSeed *seeds,

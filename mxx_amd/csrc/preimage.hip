@@ -158,7 +158,7 @@ static int launch_scatter(GpuContext *ctx, const RequestTable &req, const GpuMat
 }
 
 // ---- the keyed few-row product: out[:, c] = lhs_k(c) * rhs[:, c] -------------------------------------------------------
-// The columns of rhs (inner x cols) and out (rows x cols, rows <= 4) fall into runs; run k owns columns
+// The columns of rhs (inner x cols) and out (rows x cols, rows <= 8: d or 2d) fall into runs; run k owns columns
 // [col_start[k], col_start[k + 1]) and has a left operand of its own (rows x inner): the requests of one trapdoor.  A
 // column tile never crosses a run, so a workgroup has ONE left operand and the shared register-tile loop (matmul_tile.h)
 // with its lazy-accumulation rule serves as it stands; run k owns the column tiles [tile_start[k], tile_start[k + 1]).
@@ -284,9 +284,8 @@ static int launch_keyed_cfg(GpuContext *ctx, GpuMatrix *out, const GpuMatrix *co
 static int launch_matmul_keyed(GpuContext *ctx, GpuMatrix *out, const GpuMatrix *const *lhs, const uint32_t *col_start, size_t runs,
                                const GpuMatrix *rhs) {
     const int rc = dispatch_stacked_tile(ctx, stacked_tile(ctx, out->rows, rhs->cols, matrix_limbs(out)), [&](auto cfg) {
-        typedef decltype(cfg) T;
-        if constexpr (T::TR > 4) return set_error("gpupoly_trapdoor_preimage_keyed: more than four rows");  // stacked_tile: never for rows <= 4
-        else return launch_keyed_cfg<typename T::W, T::TR, T::TC, T::SV>(ctx, out, lhs, col_start, runs, rhs);
+        typedef decltype(cfg) T;  // u32 words take the 8-row tile from 5 rows on (2d rows at d = 3, 4)
+        return launch_keyed_cfg<typename T::W, T::TR, T::TC, T::SV>(ctx, out, lhs, col_start, runs, rhs);
     });
     if (rc == 0) out->format = GPU_POLY_FORMAT_EVAL;
     return rc;
@@ -454,7 +453,8 @@ extern "C" int gpupoly_trapdoor_preimage_many(const GpuMatrix *re, const GpuP1Co
     // what the segmented samplers cover (include/gpupoly.h); the caller issues such requests one by one
     if ((static_cast<size_t>(ctx->N) >> 1) % SAMPLER_THREADS)
         return fail("unsupported: ring dimension not a multiple of 128 (segmented samplers)");
-    if (cache->m > 4 || ctx->env.p1_simple) return fail("unsupported: trapdoor dimension above 2 or MXX_HIP_P1=simple (no p1 lane kernel)");
+    if (cache->m > 8) return fail("unsupported: trapdoor dimension above 4 (no p1 lane kernel)");
+    if (ctx->env.p1_simple) return fail("unsupported under MXX_HIP_P1=simple (the p1 lane kernel is switched off)");
     if (dpt > 4) return fail("unsupported: more than four digits per tower (G-sampler lane kernel)");
     if (ctx->env.rng_compat) return fail("unsupported under MXX_HIP_RNG_COMPAT=reference");
     // the widths as trapdoor.py evaluates them: c = cache->sigma, s = cache->s, large = sqrt(s^2 - c^2)
@@ -555,7 +555,8 @@ extern "C" int gpupoly_trapdoor_preimage_keyed(const GpuMatrix *const *res, cons
     // what the segmented samplers cover, as in the one-key entry; the caller then issues one call per key
     if ((static_cast<size_t>(ctx->N) >> 1) % SAMPLER_THREADS)
         return refuse("unsupported: ring dimension not a multiple of 128 (segmented samplers)");
-    if (top > 4 || ctx->env.p1_simple) return refuse("unsupported: trapdoor dimension above 2 or MXX_HIP_P1=simple (no p1 lane kernel)");
+    if (top > 8) return refuse("unsupported: trapdoor dimension above 4 (no p1 lane kernel)");
+    if (ctx->env.p1_simple) return refuse("unsupported under MXX_HIP_P1=simple (the p1 lane kernel is switched off)");
     if (dpt > 4) return refuse("unsupported: more than four digits per tower (G-sampler lane kernel)");
     if (ctx->env.rng_compat) return refuse("unsupported under MXX_HIP_RNG_COMPAT=reference");
     for (size_t k = 1; k < nkeys; ++k)  // sigma_large and c_scale are single launch scalars

@@ -730,7 +730,7 @@ __global__ void p1_divisor_kernel(KarneyDivisor *__restrict__ div, const double 
     if (idx < count) div[idx] = karney_divisor(sqrt_var[idx]);
 }
 
-// persistent-lane form for m <= 4 (rng.h): element = (column, coefficient), m dependent Karney
+// persistent-lane form for m <= 8 (rng.h): element = (column, coefficient), m dependent Karney
 // integers each (rows m-1 .. 0); integers go to the int64 staging array [row][col][N].  Keystream refills every
 // second checkpoint (fill_every; M3A: 0.47 -> 0.445 ms, every third 0.447)
 // SEG: the columns are independently seeded segments (rng.h, RngSegments).  The launcher picks a lane count that keeps
@@ -815,11 +815,15 @@ __global__ void __launch_bounds__(SAMPLER_THREADS) p1_sample_lanes_kernel(int64_
                 const size_t idx = chunk.base + e;
                 col = static_cast<uint32_t>(idx >> logN);
                 i = static_cast<uint32_t>(idx & ((1u << logN) - 1));
+                // limb 0 of rows 0 .. m-1 of this column: one running pointer (a product r * cols per row is loop-invariant,
+                // gets hoisted into scalar registers and, at MAXM = 8, spills them)
+                const W *row = tp2 + ((static_cast<size_t>(col) * L) << logN) + i;
 #pragma unroll
                 for (int r = 0; r < MAXM; ++r)
-                    if (r < (int)m)
-                        mean[r] = c_scale * static_cast<double>(centered_residue(
-                                                tp2[(((static_cast<size_t>(r) * cols + col) * L) << logN) + i], q0));
+                    if (r < (int)m) {
+                        mean[r] = c_scale * static_cast<double>(centered_residue(*row, q0));
+                        row += (static_cast<size_t>(cols) * L) << logN;
+                    }
                 rng_reopen(rng, static_cast<uint64_t>(col - seg_col0) + 1, static_cast<uint64_t>(i) + 1);
                 t = m - 1;
 #pragma unroll
@@ -965,8 +969,10 @@ extern "C" int gpupoly_matrix_sample_p1_full_cached_segments(const GpuP1Covarian
                                                              GpuMatrix *out) {
     ABI_GUARD_BEGIN
     if (!cache || !tp2 || !out) return set_error("invalid gpupoly_matrix_sample_p1_full_cached_segments arguments");
-    if (cache->m > 4 || cache->ctx->env.p1_simple)
-        return set_error("gpupoly_matrix_sample_p1_full_cached_segments: unsupported: trapdoor dimension above 2 (no lane kernel)");
+    if (cache->m > 8)
+        return set_error("gpupoly_matrix_sample_p1_full_cached_segments: unsupported: trapdoor dimension above 4 (no lane kernel)");
+    if (cache->ctx->env.p1_simple)
+        return set_error("gpupoly_matrix_sample_p1_full_cached_segments: unsupported under MXX_HIP_P1=simple (the lane kernel is switched off)");
     if (static_cast<size_t>(cache->ctx->N) % SAMPLER_THREADS)
         return set_error("gpupoly_matrix_sample_p1_full_cached_segments: unsupported: ring too small for a wave per column chunk");
     RngSegments segs;
@@ -983,8 +989,10 @@ extern "C" int gpupoly_matrix_sample_p1_full_cached_segments(const GpuP1Covarian
 int sample_p1_keyed_segments(const GpuP1CovarianceCache *cache, const P1KeyEntry *d_keys, const GpuMatrix *tp2,
                              const GpuRngSeed *seeds, const size_t *seg_cols, size_t nseg, GpuMatrix *out) {
     if (!cache || !d_keys || !tp2 || !out) return set_error("invalid sample_p1_keyed_segments arguments");
-    if (cache->m > 4 || cache->ctx->env.p1_simple)
-        return set_error("sample_p1_keyed_segments: unsupported: trapdoor dimension above 2 (no lane kernel)");
+    if (cache->m > 8)
+        return set_error("sample_p1_keyed_segments: unsupported: trapdoor dimension above 4 (no lane kernel)");
+    if (cache->ctx->env.p1_simple)
+        return set_error("sample_p1_keyed_segments: unsupported under MXX_HIP_P1=simple (the lane kernel is switched off)");
     if (static_cast<size_t>(cache->ctx->N) % SAMPLER_THREADS)
         return set_error("sample_p1_keyed_segments: unsupported: ring too small for a wave per column chunk");
     RngSegments segs;
@@ -1017,8 +1025,9 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
     if (ctx_activate(ctx)) return 1;
     const uint32_t L = static_cast<uint32_t>(matrix_limbs(out)), N = static_cast<uint32_t>(ctx->N);
     const size_t total = cols * static_cast<size_t>(N);
-    // MXX_HIP_P1=simple keeps the one-thread-per-element kernel for every m (A/B runs, tests)
-    if (m <= 4 && !ctx->env.p1_simple) {
+    // MXX_HIP_P1=simple keeps the one-thread-per-element kernel for every m (A/B runs, tests): the same bytes from either.
+    // At 4 < m <= 8 the lane kernel is the default because it measured 2.1 - 2.8x faster
+    if (m <= 8 && !ctx->env.p1_simple) {
         void *stage = nullptr;
         if (ctx_alloc(ctx, total * m * sizeof(int64_t), &stage)) return 1;
         const ChaChaKey key = chacha_subkey(seed, 0, kTagP1);
@@ -1060,10 +1069,12 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
     } while (0)
         if (ctx->wide) {
             if (m <= 2) LAUNCH_P1L(uint64_t, 2);
-            else LAUNCH_P1L(uint64_t, 4);
+            else if (m <= 4) LAUNCH_P1L(uint64_t, 4);
+            else LAUNCH_P1L(uint64_t, 8);
         } else {
             if (m <= 2) LAUNCH_P1L(uint32_t, 2);
-            else LAUNCH_P1L(uint32_t, 4);
+            else if (m <= 4) LAUNCH_P1L(uint32_t, 4);
+            else LAUNCH_P1L(uint32_t, 8);
         }
 #undef LAUNCH_P1L
 #undef LAUNCH_P1KEYED

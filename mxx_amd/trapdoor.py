@@ -388,11 +388,11 @@ class GpuDCRTPolyTrapdoorSampler:
     @staticmethod
     def _segments_supported(params, td: GpuDCRTTrapdoor) -> bool:
         """what the library's *_segments entry points cover (include/gpupoly.h): n a multiple of 128, trapdoor dimension
-        <= 2 (the p1 lane kernel), at most four digits per tower (the G-sampler's lane kernel), default RNG keying"""
+        <= 4 (the p1 lane kernel), at most four digits per tower (the G-sampler's lane kernel), default RNG keying"""
         import os
 
         dpt = -(-params.crt_bits() // params.base_bits())
-        return (params.ring_dimension() % 128 == 0 and td.r.row_size() <= 2 and dpt <= 4
+        return (params.ring_dimension() % 128 == 0 and td.r.row_size() <= 4 and dpt <= 4
                 and not os.environ.get("MXX_HIP_RNG_COMPAT", "").startswith("r")
                 and not os.environ.get("MXX_HIP_P1", "").startswith("s")
                 and os.environ.get("MXX_PREIMAGE_BATCH", "1") != "0")
