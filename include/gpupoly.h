@@ -414,7 +414,7 @@ int gpupoly_matrix_gauss_samp_gq_arb_base_segments(GpuMatrix *src, uint32_t base
  * `seeds`; nblk == 0 or above 2^20; an unknown layout; STACKED with seg_cols != NULL or out->rows != nblk; COLUMNS with
  * a null seg_cols, a zero width or widths that do not sum to out->cols; an invalid dist_type; a block of 2^48
  * polynomials or more (the 48-bit stream ids).  Refused likewise with an error containing "unsupported": the Gaussian
- * distribution (gpupoly_matrix_sample_distribution_segments is its entry); a context created under
+ * distribution (gpupoly_matrix_sample_gauss_blocks, below, is its entry); a context created under
  * MXX_HIP_RNG_COMPAT=reference (issue the requests one by one).
  * gpupoly_matrix_sample_hash_blocks is this entry with the seeds hashed from (key, tags) on the device.          */
 #define GPUPOLY_BLOCKS_STACKED 0
@@ -472,6 +472,27 @@ int gpupoly_hash_seeds(GpuContext *ctx, const GpuHashTags *tags, size_t ntags, G
  * "unsupported") and everything gpupoly_hash_seeds refuses of `tags`.                                                 */
 int gpupoly_matrix_sample_hash_blocks(GpuMatrix *out, int dist_type, const GpuHashTags *tags, size_t nblk, int layout,
                                       const size_t *seg_cols);
+/* ---- Gaussian seeded blocks (extension).  Replaces the per-request `sample_error_matrix`
+ * (src/lookup/ggh15/pubkey.rs:227-239; its calls at pubkey_gpu.rs:428,457,476,507,535: one freshly seeded Gaussian matrix
+ * per gate, stage and column chunk) and the GaussDist calls of `US::sample_uniform` in the gate stages and in
+ * src/bgg/sampler_gpu.rs:125-135, one derive / sample / scatter / transform sequence each.
+ * out = the blocks of gpupoly_matrix_sample_distribution_blocks (same layouts, same nblk 1..2^20, same seg_cols rules),
+ * block t bit for bit what gpu_matrix_sample_distribution(GAUSS, sigma, seeds[t]) writes for that block alone; ends EVAL,
+ * at its own level, in plain words (a Gaussian sample is never stored packed).  Four launches whatever nblk is: key
+ * derivation, the lane sampler, the scatter of its integers into residues, the forward transform.  Enqueued on the
+ * context's stream; the host does not block.  An `out` without polynomials succeeds with nothing launched, tagged EVAL.
+ * Overlap: the only matrix is `out`; nothing can overlap.
+ * Refused, with nothing launched and `out` (contents AND tag) untouched, the message naming this entry: everything
+ * gpupoly_matrix_sample_distribution_blocks refuses for its layouts (MXX_HIP_RNG_COMPAT=reference with "unsupported");
+ * sigma not > 0 ("sigma must be positive"); a ring of n < 128, whose polynomials hold less than a wave's 64 pairs
+ * ("unsupported": issue the requests one by one); more than 2^32 polynomials.                                      */
+int gpupoly_matrix_sample_gauss_blocks(GpuMatrix *out, double sigma, const GpuRngSeed *seeds, size_t nblk, int layout,
+                                       const size_t *seg_cols);
+/* the same with the seeds hashed from (key, tags) on the device, as gpupoly_matrix_sample_hash_blocks: one launch in
+ * front, five in all; the Gaussian matrices of the tagged loops (`sample_hash` with GaussDist) and the hashed error
+ * blocks of the gate stages.  Refused likewise, plus everything gpupoly_hash_seeds refuses of `tags`.               */
+int gpupoly_matrix_sample_hash_gauss_blocks(GpuMatrix *out, double sigma, const GpuHashTags *tags, size_t nblk, int layout,
+                                            const size_t *seg_cols);
 /* out = [blocks[0] | blocks[1] | ...] / blocks[j] = the next blocks[j]->cols columns of src, in one launch per 64
  * blocks (the wrapper's concat_columns / slice_columns are a gpu_matrix_copy_block launch per block,
  * src/matrix/gpu_dcrt_poly.rs:1216-1260).  Same rows, level and context everywhere; the written side takes the read

@@ -156,6 +156,8 @@ SIGNATURES = {
     "gpupoly_matrix_sample_distribution_blocks": (C.c_int, [_vp, C.c_int, C.POINTER(GpuRngSeed), _sz, C.c_int, C.POINTER(_sz)]),
     "gpupoly_hash_seeds": (C.c_int, [_vp, C.POINTER(GpuHashTags), _sz, C.POINTER(GpuRngSeed)]),
     "gpupoly_matrix_sample_hash_blocks": (C.c_int, [_vp, C.c_int, C.POINTER(GpuHashTags), _sz, C.c_int, C.POINTER(_sz)]),
+    "gpupoly_matrix_sample_gauss_blocks": (C.c_int, [_vp, C.c_double, C.POINTER(GpuRngSeed), _sz, C.c_int, C.POINTER(_sz)]),
+    "gpupoly_matrix_sample_hash_gauss_blocks": (C.c_int, [_vp, C.c_double, C.POINTER(GpuHashTags), _sz, C.c_int, C.POINTER(_sz)]),
     "gpupoly_matrix_sample_decomposed_blocks": (C.c_int, [_vp, C.c_int, C.POINTER(GpuRngSeed), _sz, C.c_uint32, C.c_int, _sz, _sz, _sz]),
     "gpupoly_matrix_sample_hash_decomposed_blocks": (C.c_int, [_vp, C.c_int, C.POINTER(GpuHashTags), _sz, C.c_uint32, C.c_int, _sz, _sz, _sz]),
     "gpupoly_matrix_lut_targets": (C.c_int, [C.POINTER(C.c_void_p), _sz, _vp, _vp, _vp, _vp, _sz, C.c_uint32, C.POINTER(C.c_uint64), _sz,

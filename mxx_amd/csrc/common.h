@@ -340,7 +340,7 @@ struct RngBlockWindow {
     size_t cols, full_ncol, col_offset;
 };
 int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, const GpuHashTags *tags,
-                       size_t nblk, int layout, const size_t *seg_cols, const RngBlockWindow *win);
+                       size_t nblk, int layout, const size_t *seg_cols, const RngBlockWindow *win, const double *sigma = nullptr);
 // decompose.hip: both decomposed-blocks entries in `entry`'s name (seeds or tags, the other null)
 int sample_decomposed_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_type, const GpuRngSeed *seeds,
                                   const GpuHashTags *tags, size_t nblk, uint32_t base_bits, int small, size_t src_rows, size_t full_ncol,

@@ -694,6 +694,10 @@ static __device__ int64_t sample_integer_karney(ChaChaRng &rng, double mean, dou
 #define SAMPLER_PER_LANE_CAP 8
 #endif
 constexpr uint32_t kSamplerPerLaneCap = SAMPLER_PER_LANE_CAP;
+// coefficients per stream of the Gaussian lane kernels, as a power of two (sampling.hip has the measurements)
+#ifndef GAUSS_GROUP_LOG
+#define GAUSS_GROUP_LOG 1
+#endif
 // threads per workgroup of the persistent-lane kernels (a lane's ring is 128 bytes of LDS: 8 KB per wave)
 #ifndef SAMPLER_THREADS
 #define SAMPLER_THREADS 64
@@ -801,6 +805,11 @@ __device__ __forceinline__ RngBlockRef rng_block_of(const RngBlockTable &t, uint
     return r;
 }
 #endif
+
+// gauss_blocks.hip: the Gaussian lane kernel over a table of one key per block (polys x N int64 into `stage`; the launch
+// error, if any, is the caller's hipGetLastError)
+struct GpuContext;
+void launch_gauss_blocks(GpuContext *ctx, int64_t *stage, size_t polys, const RngBlockTable &table, double sigma);
 
 static inline uint32_t sampler_per_lane(size_t total, const void *kernel, int device, int forced) {
     if (forced >= 1) return static_cast<uint32_t>(forced);

@@ -646,20 +646,30 @@ __global__ void __launch_bounds__(256) sample_small_blocks_kernel(W *__restrict_
 // `win` (the decomposed blocks, decompose.hip): `out` is the caller's coefficient scratch, rows x (nblk * win->cols), every
 // block the window [col_offset, col_offset + cols) of its own rows x full_ncol matrix (the caller has checked the window);
 // `layout` and `seg_cols` are not read, and the samples stay coefficients in words: no transform, no pack, tagged COEFF.
+// `sigma` (the two Gaussian entries alone; `dist_type` is then not read, `win` is null): the Gaussian leg - one sub-key per
+// block, the lane kernel into an int64 staging array, the plain sampler's scatter and transform.
 int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_type, const GpuRngSeed *seeds, const GpuHashTags *tags,
-                       size_t nblk, int layout, const size_t *seg_cols, const RngBlockWindow *win) {
+                       size_t nblk, int layout, const size_t *seg_cols, const RngBlockWindow *win, const double *sigma) {
     constexpr size_t kMaxBlocks = size_t(1) << 20, kStreamLimit = size_t(1) << 48;
     const auto refuse = [entry](const char *what) { return set_error(std::string(entry) + what); };
     if (!out) return refuse(": null matrix");
     if (!seeds && !tags) return refuse(hashed ? ": null tags" : ": null seeds");
     if (nblk == 0 || nblk > kMaxBlocks) return refuse(": the block count must be 1..2^20");
     if (!win && layout != GPUPOLY_BLOCKS_STACKED && layout != GPUPOLY_BLOCKS_COLUMNS) return refuse(": unknown layout");
-    if (dist_type == GPU_MATRIX_DIST_GAUSS)
-        return refuse(win ? ": unsupported: the Gaussian distribution has no block form"
-                          : ": unsupported: the Gaussian distribution goes through gpupoly_matrix_sample_distribution_segments");
-    if (dist_type < GPU_MATRIX_DIST_UNIFORM || dist_type > GPU_MATRIX_DIST_TERNARY) return refuse(": invalid dist_type");
+    const bool gauss = sigma != nullptr;
+    if (gauss) {
+        if (!(*sigma > 0.0)) return refuse(": sigma must be positive for Gaussian sampling");
+    } else {
+        if (dist_type == GPU_MATRIX_DIST_GAUSS)
+            return refuse(win ? ": unsupported: the Gaussian distribution has no block form"
+                              : ": unsupported: the Gaussian distribution goes through gpupoly_matrix_sample_distribution_segments");
+        if (dist_type < GPU_MATRIX_DIST_UNIFORM || dist_type > GPU_MATRIX_DIST_TERNARY) return refuse(": invalid dist_type");
+    }
     GpuContext *ctx = out->ctx;
     if (ctx->env.rng_compat) return refuse(": unsupported under MXX_HIP_RNG_COMPAT=reference");
+    const size_t pairs_per_poly = static_cast<size_t>(ctx->N) >> GAUSS_GROUP_LOG;
+    if (gauss && (pairs_per_poly == 0 || pairs_per_poly % SAMPLER_THREADS))
+        return refuse(": unsupported: ring too small for a wave per polynomial chunk");
     const bool columns = !win && layout == GPUPOLY_BLOCKS_COLUMNS;
     // a window's shape, its place inside full_ncol and the stream ids of the conceptual matrix are the caller's checks
     if (columns) {
@@ -682,12 +692,13 @@ int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_
     size_t tag_bytes = 0;
     if (tags && hash_tags_check(entry, tags, nblk, &tag_bytes)) return 1;
     const size_t polys = matrix_polys(out);
+    if (gauss && polys >> 32) return refuse(": too many polynomials");
     if (polys == 0) {
         out->format = GPU_POLY_FORMAT_EVAL;
         return 0;
     }
     if (ctx_activate(ctx)) return 1;
-    const bool uniform = dist_type == GPU_MATRIX_DIST_UNIFORM;
+    const bool uniform = !gauss && dist_type == GPU_MATRIX_DIST_UNIFORM;
     const uint32_t L = static_cast<uint32_t>(matrix_limbs(out)), N = static_cast<uint32_t>(ctx->N), groups = (N + 7) / 8;
     const uint32_t per_block = uniform ? L : 1u;
     // the table: [keys][seeds][starts][tag offsets and bytes]; what the host knows of it goes up in one copy out of a staging
@@ -723,7 +734,7 @@ int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_
                         HIP_TRY(hipMemcpyAsync(d_words + (seed_words - given_words), staging.data(), sizeof(uint64_t) * staging.size(),
                                                hipMemcpyHostToDevice, ctx->stream)));
     if (tags && launch_hash_seeds(ctx, d_seeds, tags, nblk, d_starts + start_words)) return 1;
-    const uint64_t tag = uniform ? kTagUniform : (dist_type == GPU_MATRIX_DIST_BIT ? kTagBit : kTagTernary);
+    const uint64_t tag = gauss ? kTagGauss : uniform ? kTagUniform : (dist_type == GPU_MATRIX_DIST_BIT ? kTagBit : kTagTernary);
     MXX_LAUNCH(derive_block_subkeys_kernel, item_grid(nblk * per_block, 256), dim3(256), 0, ctx->stream, d_keys, d_seeds, tag, nblk, per_block,
                uniform ? 1u : 0u);
     HIP_TRY(hipGetLastError());
@@ -733,6 +744,20 @@ int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_
         table.win_cols = win->cols;
         table.full_ncol = win->full_ncol;
         table.col_offset = win->col_offset;
+    }
+    if (gauss) {
+        // the keys are sample_impl's, chacha_subkey(seed, 0, kTagGauss), one per block (gauss_blocks.hip has the kernel)
+        const size_t total = polys * static_cast<size_t>(ctx->N);
+        void *stage = nullptr;
+        if (ctx_alloc(ctx, total * sizeof(int64_t), &stage)) return 1;
+        MXX_TRACE_BYTES(static_cast<double>(total) * sizeof(int64_t));  // no input to speak of: the int64 samples written once
+        launch_gauss_blocks(ctx, static_cast<int64_t *>(stage), polys, table, *sigma);
+        const hipError_t err = hipGetLastError();
+        const int rc = err == hipSuccess ? launch_scatter_i64(out, static_cast<const int64_t *>(stage)) : 0;
+        ctx_free(ctx, stage);
+        HIP_TRY(err);
+        if (rc) return rc;
+        return launch_ntt(ctx, words, polys * L, static_cast<int>(L), false);  // a Gaussian sample is never stored packed
     }
     const size_t threads = polys * per_block * groups;
     const dim3 blocks = item_grid(threads, 256);
@@ -766,6 +791,22 @@ extern "C" int gpupoly_matrix_sample_hash_blocks(GpuMatrix *out, int dist_type, 
                                                  const size_t *seg_cols) {
     ABI_GUARD_BEGIN
     return sample_blocks_impl("gpupoly_matrix_sample_hash_blocks", true, out, dist_type, nullptr, tags, nblk, layout, seg_cols, nullptr);
+    ABI_GUARD_END
+}
+
+extern "C" int gpupoly_matrix_sample_gauss_blocks(GpuMatrix *out, double sigma, const GpuRngSeed *seeds, size_t nblk, int layout,
+                                                  const size_t *seg_cols) {
+    ABI_GUARD_BEGIN
+    return sample_blocks_impl("gpupoly_matrix_sample_gauss_blocks", false, out, GPU_MATRIX_DIST_GAUSS, seeds, nullptr, nblk, layout, seg_cols,
+                              nullptr, &sigma);
+    ABI_GUARD_END
+}
+
+extern "C" int gpupoly_matrix_sample_hash_gauss_blocks(GpuMatrix *out, double sigma, const GpuHashTags *tags, size_t nblk, int layout,
+                                                       const size_t *seg_cols) {
+    ABI_GUARD_BEGIN
+    return sample_blocks_impl("gpupoly_matrix_sample_hash_gauss_blocks", true, out, GPU_MATRIX_DIST_GAUSS, nullptr, tags, nblk, layout,
+                              seg_cols, nullptr, &sigma);
     ABI_GUARD_END
 }
 

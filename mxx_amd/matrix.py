@@ -2140,7 +2140,7 @@ class GpuDCRTPolyMatrix:
         `sample_distribution(params, r, c, dist, 0, seeds[t])`, r * c == P, in row-major order.
         Columns layout, `nrow=r, seg_cols=[c_0, ...]`: [S_0 | S_1 | ...] with S_j == sample_distribution(params, r, c_j,
         dist, 0, seeds[j]).  Raises GpuPolyError (text contains "unsupported") for the
-        Gaussian distribution - `sample_distribution_segments` is its entry - and under MXX_HIP_RNG_COMPAT=reference."""
+        Gaussian distribution - `sample_gauss_blocks` is its entry - and under MXX_HIP_RNG_COMPAT=reference."""
         seeds = list(seeds)
         level = params.crt_depth() - 1
         arr = (GpuRngSeed * max(len(seeds), 1))(*seeds)
@@ -2180,6 +2180,43 @@ class GpuDCRTPolyMatrix:
             layout, cols = _ffi.GPUPOLY_BLOCKS_COLUMNS, (C.c_size_t * max(len(seg_cols), 1))(*seg_cols)
         check_status(_ffi.lib().gpupoly_matrix_sample_hash_blocks(out.raw, dist, C.byref(arg), count, layout, cols),
                      "gpupoly_matrix_sample_hash_blocks")
+        del keep
+        return out
+
+    @classmethod
+    def _blocks_out(cls, who, params, count, block_polys, nrow, seg_cols):
+        """(out, layout, seg_cols array) of a block sample: block_polys (stacked) or nrow and seg_cols (columns)"""
+        level = params.crt_depth() - 1
+        if seg_cols is None:
+            assert block_polys is not None and nrow is None, f"{who}: block_polys (stacked) or nrow and seg_cols (columns)"
+            return cls(params, count, block_polys, level, True), _ffi.GPUPOLY_BLOCKS_STACKED, None
+        assert block_polys is None and nrow is not None, f"{who}: block_polys (stacked) or nrow and seg_cols (columns)"
+        seg_cols = list(seg_cols)
+        assert len(seg_cols) == count, f"{who}: one seed or tag per block"
+        return cls(params, nrow, sum(seg_cols), level, True), _ffi.GPUPOLY_BLOCKS_COLUMNS, (C.c_size_t * max(len(seg_cols), 1))(*seg_cols)
+
+    @classmethod
+    def sample_gauss_blocks(cls, params, seeds, sigma: float, *, block_polys=None, nrow=None, seg_cols=None) -> "GpuDCRTPolyMatrix":
+        """Gaussian samples of len(seeds) independently seeded blocks in one call (gpupoly_matrix_sample_gauss_blocks; DESIGN.md
+        section 5s), any number of blocks up to 2^20 in four launches: `sample_distribution_blocks`' layouts with block t ==
+        sample_distribution(params, r, c, GAUSS, sigma, seeds[t]).  Raises GpuPolyError (text contains "unsupported") for rings
+        below n = 128 and under MXX_HIP_RNG_COMPAT=reference."""
+        seeds = list(seeds)
+        arr = (GpuRngSeed * max(len(seeds), 1))(*seeds)
+        out, layout, cols = cls._blocks_out("sample_gauss_blocks", params, len(seeds), block_polys, nrow, seg_cols)
+        check_status(_ffi.lib().gpupoly_matrix_sample_gauss_blocks(out.raw, float(sigma), arr, len(seeds), layout, cols),
+                     "gpupoly_matrix_sample_gauss_blocks")
+        return out
+
+    @classmethod
+    def sample_hash_gauss_blocks(cls, params, key: bytes, tags, sigma: float, *, hash_name: str = "keccak256", block_polys=None,
+                                 nrow=None, seg_cols=None) -> "GpuDCRTPolyMatrix":
+        """`sample_gauss_blocks` with seeds[t] = hash_seed_for_matrix(key, tags[t], hash_name) derived on the device
+        (gpupoly_matrix_sample_hash_gauss_blocks): `key`, `tags` and `hash_name` as `sample_hash_blocks` takes them."""
+        arg, keep, count = hash_tags_arg(key, tags, hash_name)
+        out, layout, cols = cls._blocks_out("sample_hash_gauss_blocks", params, count, block_polys, nrow, seg_cols)
+        check_status(_ffi.lib().gpupoly_matrix_sample_hash_gauss_blocks(out.raw, float(sigma), C.byref(arg), count, layout, cols),
+                     "gpupoly_matrix_sample_hash_gauss_blocks")
         del keep
         return out
 

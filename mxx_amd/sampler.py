@@ -148,11 +148,42 @@ def sample_gpu_matrix_with_seed_columns(params, nrow, total_ncol, col_start, col
     )
 
 
+def sample_gpu_stack_with_seeds(params, nrow, ncol, dist: DistType, seeds) -> GpuDCRTPolyMatrix:
+    """The len(seeds) x (nrow * ncol) matrix whose row t is sample_gpu_matrix_with_seed(params, nrow, ncol, dist, seeds[t])
+    in row-major order: one stacked-layout call (the Gaussian blocks for GaussDist, the seeded blocks otherwise); where
+    the library answers "unsupported" the rows are sampled one by one and copied in - the same matrix either way."""
+    seeds = list(seeds)
+    polys = nrow * ncol
+    if not seeds or polys == 0:
+        return GpuDCRTPolyMatrix.zero(params, len(seeds), polys)
+    try:
+        if dist.kind == "gauss":
+            return GpuDCRTPolyMatrix.sample_gauss_blocks(params, seeds, dist.sigma, block_polys=polys)
+        return GpuDCRTPolyMatrix.sample_distribution_blocks(params, seeds, dist.as_ffi(), block_polys=polys)
+    except _ffi.GpuPolyError as e:
+        if "unsupported" not in str(e):
+            raise
+    out = GpuDCRTPolyMatrix.new_empty(params, len(seeds), polys)
+    for t, seed in enumerate(seeds):
+        block = sample_gpu_matrix_with_seed(params, nrow, ncol, dist, seed)
+        out.copy_block_from(block.reshape_view(1, polys), t, 0, 0, 0, 1, polys)
+    return out
+
+
 class GpuDCRTPolyUniformSampler:
     """`PolyUniformSampler` for the GPU (src/sampler/gpu.rs:16-46)."""
 
     def sample_uniform(self, params, nrow, ncol, dist: DistType) -> GpuDCRTPolyMatrix:
         return sample_gpu_matrix_with_seed(params, nrow, ncol, dist, random_gpu_rng_seed())
+
+    def sample_uniform_many(self, params, nrow, ncol, dist: DistType, count, _seeds=None) -> GpuDCRTPolyMatrix:
+        """`count` independent sample_uniform(params, nrow, ncol, dist) draws as one stack: the count x (nrow * ncol) matrix
+        whose row t is draw t in row-major order (reshape_view / row_view give the matrices), sampled in one call - the
+        per-gate `US::sample_uniform` calls of the GGH15 gate stages (src/lookup/ggh15/pubkey_gpu.rs:418-537) and of
+        src/bgg/sampler_gpu.rs:125-135.  A fresh seed per draw, as the loop takes them; `_seeds` (tests) gives them."""
+        seeds = [random_gpu_rng_seed() for _ in range(count)] if _seeds is None else list(_seeds)
+        assert len(seeds) == count, "sample_uniform_many: one seed per draw"
+        return sample_gpu_stack_with_seeds(params, nrow, ncol, dist, seeds)
 
     def sample_poly(self, params, dist: DistType) -> GpuDCRTPoly:
         return self.sample_uniform(params, 1, 1, dist).entry(0, 0)
@@ -220,10 +251,13 @@ class GpuDCRTPolyHashSampler:
         return [hash_seed_for_matrix(key, tag, self.hash_name) for tag in tags]
 
     def _hash_blocks(self, params, key, tags, dist, **shape):
-        """sample_hash_blocks where the hash has a device form and the library does not answer "unsupported"; else None"""
+        """sample_hash_blocks (sample_hash_gauss_blocks for GaussDist) where the hash has a device form and the library does
+        not answer "unsupported"; else None"""
         if not self._on_device():
             return None
         try:
+            if dist.kind == "gauss":
+                return GpuDCRTPolyMatrix.sample_hash_gauss_blocks(params, key, tags, dist.sigma, hash_name=self.hash_name, **shape)
             return GpuDCRTPolyMatrix.sample_hash_blocks(params, key, tags, dist.as_ffi(), hash_name=self.hash_name, **shape)
         except _ffi.GpuPolyError as e:
             if "unsupported" not in str(e):
@@ -233,28 +267,28 @@ class GpuDCRTPolyHashSampler:
     def sample_hash_many(self, params, key: bytes, tags, nrow, ncol, dist: DistType) -> list:
         """== [sample_hash(params, key, tag, nrow, ncol, dist) for tag in tags] - the tagged loops of
         src/commit/wee25.rs:687-703, src/lookup/ggh15/pubkey_gpu.rs:924,1296 and src/lookup/lwe/pubkey_gpu.rs:559,616.
-        Uniform / bit / ternary under a Keccak hash: ONE columns-layout sample with the tags hashed on the device (no seeds
-        on the host; an `IndexedTags` is not even uploaded) per 2^20 tags, and one split_columns per 64 of them.  Otherwise
-        one columns-layout sample and one split_columns per 64 tags over host- or device-derived seeds (Gaussian requests
-        through the Gaussian segments).  Where the library answers "unsupported" (MXX_HIP_RNG_COMPAT=reference, rings the
-        Gaussian segments do not cover) the tags are sampled one by one: the same matrices either way."""
+        Under a Keccak hash: ONE columns-layout sample with the tags hashed on the device (no seeds on the host; an
+        `IndexedTags` is not even uploaded) per 2^20 tags - the Gaussian blocks for GaussDist -, and
+        one split_columns per 64 of them.  Otherwise one columns-layout sample and one split_columns per 64 tags over host- or
+        device-derived seeds (Gaussian requests through the Gaussian segments).  Where the library answers "unsupported"
+        (MXX_HIP_RNG_COMPAT=reference, rings the Gaussian entries do not cover) the tags are sampled one by one: the same
+        matrices either way."""
         tags = tags if isinstance(tags, IndexedTags) else list(tags)
         if nrow == 0 or ncol == 0:
             return [GpuDCRTPolyMatrix.zero(params, nrow, ncol) for _ in range(len(tags))]
         outs = []
-        if dist.kind != "gauss":
-            for lo in range(0, len(tags), 1 << 20):  # the entry's block limit; "unsupported" is the first call's answer or nobody's
-                part = tags[lo : lo + (1 << 20)]
-                wide = self._hash_blocks(params, key, part, dist, nrow=nrow, seg_cols=[ncol] * len(part))
-                if wide is None:
-                    break
-                for at in range(0, len(part), 64):
-                    width = min(64, len(part) - at)
-                    piece = wide if width == len(part) else wide.slice_columns(at * ncol, (at + width) * ncol)
-                    outs.extend(piece.split_columns([ncol] * width))
-            if len(outs) == len(tags):
-                return outs
-            outs = []
+        for lo in range(0, len(tags), 1 << 20):  # the entry's block limit; "unsupported" is the first call's answer or nobody's
+            part = tags[lo : lo + (1 << 20)]
+            wide = self._hash_blocks(params, key, part, dist, nrow=nrow, seg_cols=[ncol] * len(part))
+            if wide is None:
+                break
+            for at in range(0, len(part), 64):
+                width = min(64, len(part) - at)
+                piece = wide if width == len(part) else wide.slice_columns(at * ncol, (at + width) * ncol)
+                outs.extend(piece.split_columns([ncol] * width))
+        if len(outs) == len(tags):
+            return outs
+        outs = []
         seeds = self._seeds(key, tags, params)
         for lo in range(0, len(tags), 64):
             chunk = seeds[lo : lo + 64]
@@ -301,27 +335,17 @@ class GpuDCRTPolyHashSampler:
     def sample_hash_stacked(self, params, key: bytes, tags, nrow, ncol, dist: DistType) -> GpuDCRTPolyMatrix:
         """The len(tags) x (nrow * ncol) matrix whose row t is sample_hash(params, key, tags[t], nrow, ncol, dist) in
         row-major order, sampled in one stacked-layout call - under a Keccak hash with the tags hashed on the device, no seeds
-        on the host; where the library answers "unsupported" (the Gaussian distribution, MXX_HIP_RNG_COMPAT=reference) the
-        rows are sampled one by one and copied in."""
+        on the host; where the library answers "unsupported" (MXX_HIP_RNG_COMPAT=reference, a Gaussian request on a ring
+        below n = 128) the rows are sampled one by one and copied in."""
         tags = tags if isinstance(tags, IndexedTags) else list(tags)
         polys = nrow * ncol
         if not len(tags) or polys == 0:
             return GpuDCRTPolyMatrix.zero(params, len(tags), polys)
-        if dist.kind != "gauss" and len(tags) <= 1 << 20:
+        if len(tags) <= 1 << 20:
             out = self._hash_blocks(params, key, tags, dist, block_polys=polys)
             if out is not None:
                 return out
-        seeds = self._seeds(key, tags, params)
-        try:
-            return GpuDCRTPolyMatrix.sample_distribution_blocks(params, seeds, dist.as_ffi(), block_polys=polys)
-        except _ffi.GpuPolyError as e:
-            if "unsupported" not in str(e):
-                raise
-        out = GpuDCRTPolyMatrix.new_empty(params, len(tags), polys)
-        for t, seed in enumerate(seeds):
-            block = sample_gpu_matrix_with_seed(params, nrow, ncol, dist, seed)
-            out.copy_block_from(block.reshape_view(1, polys), t, 0, 0, 0, 1, polys)
-        return out
+        return sample_gpu_stack_with_seeds(params, nrow, ncol, dist, self._seeds(key, tags, params))
 
     def sample_hash_weighted_sum(self, params, key: bytes, tags, weights, nrow, ncol, addend=None, negate: bool = False,
                                  max_stack_bytes: int = 1 << 30) -> GpuDCRTPolyMatrix:
