@@ -216,6 +216,38 @@ int gpupoly_matrix_mul_decompose(GpuMatrix *out, const GpuMatrix *lhs, const Gpu
 int gpupoly_matrix_mul_decompose_many(GpuMatrix *const *outs, const GpuMatrix *const *lhss,
                                       const GpuMatrix *const *addends, const GpuMatrix *const *scalars, size_t n,
                                       const GpuMatrix *rhs, uint32_t base_bits);
+/* Every left operand against ITS OWN G^-1 (extension):
+ *   outs[j] = addends[j] (+|-) (lhss[j] * G^-1(rhss[j][:, col_start .. col_start + c))) o scalars[j]     j < n, c = outs[j]->cols
+ * - for every j the residues, bit for bit, of gpu_matrix_copy_block of the window, gpupoly_matrix_mul_decompose,
+ * gpu_matrix_mul_scalar, then gpu_matrix_add / gpu_matrix_sub / gpupoly_matrix_neg.  Replaces the per-request sequences of the
+ * slot-transfer gate targets, build_gate_target_chunk_gpu and build_slot_reduce_gate_target_chunk_gpu
+ * (src/slot_transfer/bgg_pubkey_gpu.rs:371-407,409-471), over the wave of requests that sample_gate_batch_gpu builds (:842):
+ * the n windows are gathered into one r x (n c) matrix by one launch, ONE fused digit transform gives the (r k) x (n c) EVAL
+ * digit matrix, and one grouped product per 64 operands reads operand j's panel [j c, (j + 1) c) of it, multiplies the
+ * product by the scalar, adds it to or subtracts it from the addend and stores into the operand's own output.
+ *   rhss[j]     r x m, COEFF or EVAL (they may differ), left untouched; all share r and m; only columns
+ *               [col_start, col_start + c) are read; k = ceil(crt_bits/base_bits) * limbs
+ *   lhss[j]     rows_j x (r*k), EVAL; rows_j may differ from operand to operand and may be 0
+ *   outs[j]     rows_j x c, made by the caller, tagged EVAL on success; all share c
+ *   addends     NULL, or addends[j] NULL: no addend; else rows_j x c, EVAL.  addends[j] may be outs[j]'s very block (the rule
+ *               of gpupoly_matrix_mul_sum): every word is read and written by the same thread
+ *   scalars     NULL, or scalars[j] NULL: the product as it is; else 1 x 1, EVAL.  It multiplies the PRODUCT, not the addend -
+ *               the opposite of gpupoly_matrix_mul_decompose_many, whose scalar multiplies the addend
+ *   negate      != 0 subtracts the product term; without an addend the output is then the negated product
+ * One context and one level per call; n = 0 does nothing; r*k = 0 or c = 0 writes the addend term (or nothing) through the
+ * same path.  Enqueued on the context's stream, the host does not block; temporaries come from the context's allocator and
+ * are released stream-ordered.  PACKED24 operands are unpacked first.  When the digit matrix exceeds the budget rule of
+ * gpupoly_matrix_mul_decompose_many (MXX_HIP_MUL_DECOMPOSE_PAIRS_BUDGET=<bytes> overrides it for this entry) the call is cut
+ * into groups of operands.  The launch count does not depend on n up to 64 operands; every further 64 add one launch.
+ * Refused, with nothing launched and every outs[j] (contents AND tag) untouched, all checked for every j before the first
+ * launch: a null outs, lhss or rhss with n > 0, or a null entry in any of them; a context, level or shape mismatch in any j
+ * (lhss[j]->cols != r*k, differing r, m or c, col_start + c > m); an lhss[j], addends[j] or scalars[j] not in EVAL form; an
+ * output that aliases any input or another output, row views included - an addend that is its output's very block is the one
+ * exception; base_bits of 0 or >= 63.                                                                                */
+int gpupoly_matrix_mul_decompose_pairs(GpuMatrix *const *outs, const GpuMatrix *const *addends,
+                                       const GpuMatrix *const *lhss, const GpuMatrix *const *rhss,
+                                       const GpuMatrix *const *scalars, size_t n,
+                                       size_t col_start, uint32_t base_bits, int negate);
 /* outs[i] = lhss[i] * rhss[i], i < count: independent products of one context and level (all EVAL) in one call.  Small
  * products - a level of circuit gates on a small ring, where every product is a launch-latency-bound kernel - go out
  * up to 64 per launch; large ones run one by one through the tuned kernels.  No output may be another product's

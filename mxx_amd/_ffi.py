@@ -118,6 +118,7 @@ SIGNATURES = {
     "gpu_poly_load_compact_bytes": (C.c_int, [_vp, _vp, _sz, C.c_uint16]),
     "gpupoly_matrix_mul_decompose": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
     "gpupoly_matrix_mul_decompose_many": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t, _vp, C.c_uint32]),
+    "gpupoly_matrix_mul_decompose_pairs": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _sz, C.c_uint32, C.c_int]),
     "gpupoly_matrix_mul_batch":(C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t]),
     "gpupoly_batch": (C.c_int, [C.POINTER(GpuBatchOp), C.c_size_t, C.c_uint32]),
     "gpupoly_matrix_mul_decompose_small": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),

@@ -56,6 +56,8 @@ struct EnvSwitches {
     int skinny24_shape = 0;       // the shape after "force:" (matmul_skinny24.hip; 0: the default shape)
     size_t mul_decompose_many_budget = 0;  // MXX_HIP_MUL_DECOMPOSE_MANY_BUDGET=<bytes>: digit-matrix budget of gpupoly_matrix_mul_decompose_many
                                            // alone (0 = a third of the free memory, at least 8 GiB; tests reach its column chunks with it)
+    size_t mul_decompose_pairs_budget = 0;  // MXX_HIP_MUL_DECOMPOSE_PAIRS_BUDGET=<bytes>: the same for gpupoly_matrix_mul_decompose_pairs,
+                                            // which cuts its call into groups of operands (matmul_pairs.hip)
     size_t gadget_scalar_budget = 0;  // MXX_HIP_GADGET_SCALAR_BUDGET=<bytes>: digit-polynomial table budget of
                                       // gpupoly_matrix_mul_decompose_gadget_scalar_many alone (0 = the same rule; tests reach its tower groups with it)
     char mul_sum_path = 0;        // MXX_HIP_MUL_SUM_PATH: 0 auto, 't' the term-table tile kernel at every height, 's' products into

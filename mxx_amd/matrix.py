@@ -1914,6 +1914,50 @@ class GpuDCRTPolyMatrix:
         check_status(st, "gpupoly_matrix_mul_decompose_many")
         return outs
 
+    @staticmethod
+    def mul_decompose_pairs(lhss, rhss, col_start, col_len, scalars=None, addends=None, negate: bool = False, outs=None) -> list:
+        """[a +- (l * r.slice_columns(col_start, col_start + col_len).decompose()) * s for l, r, s, a in ...] through
+        `gpupoly_matrix_mul_decompose_pairs`: every operand has its OWN right operand, the windows of all of them go through
+        one gather and one digit transform, and scalar, sign and addend ride in the product's epilogue (the slot-transfer gate
+        targets: src/slot_transfer/bgg_pubkey_gpu.rs:371-407,409-471).  `scalars` / `addends` may be None or hold None
+        entries: the product as it is / no addend.  The scalar multiplies the product (in `mul_decompose_many` it multiplies
+        the addend).  `outs`: write there (outs[j] may be addends[j] itself, or a row view of the same rows); fresh matrices
+        otherwise.  The right operands may be in either domain and are left as they are."""
+        lhss, rhss = list(lhss), list(rhss)
+        n = len(lhss)
+        assert len(rhss) == n, "mul_decompose_pairs: one right operand per left operand"
+        scalars = [None] * n if scalars is None else list(scalars)
+        addends = [None] * n if addends is None else list(addends)
+        assert len(addends) == n and len(scalars) == n, "mul_decompose_pairs: one addend / scalar slot per operand"
+        assert outs is None or len(outs) == n, "mul_decompose_pairs: one output per operand"
+        if n == 0:
+            return []
+        scalars = [s.inner if hasattr(s, "inner") else s for s in scalars]
+        p = rhss[0].params
+        k = p.modulus_digits()
+        for l_, r_, a_ in zip(lhss, rhss, addends):
+            assert l_.params == p and r_.params == p and l_.ncol == r_.nrow * k, "mul_decompose_pairs: operand mismatch"
+            assert col_start + col_len <= r_.ncol, "mul_decompose_pairs: column window past the right operand"
+            assert a_ is None or (a_.nrow, a_.ncol) == (l_.nrow, col_len), "mul_decompose_pairs: addend shape"
+        # converted copies stay referenced until the call returns
+        ls = [m.ensure_eval() for m in lhss]
+        ads = [None if m is None else m.ensure_eval() for m in addends]
+        scs = [None if m is None else m.ensure_eval() for m in scalars]
+        if outs is None:
+            outs = [GpuDCRTPolyMatrix(p, l_.nrow, col_len, l_.level, True) for l_ in ls]
+        else:
+            outs = list(outs)
+            for o in outs:
+                o._touch()
+        raw = lambda m: None if m is None else (m.raw.value if hasattr(m.raw, "value") else m.raw)
+        arr = lambda ms: (C.c_void_p * n)(*[raw(m) for m in ms])
+        st = _ffi.lib().gpupoly_matrix_mul_decompose_pairs(arr(outs), arr(ads), arr(ls), arr(rhss), arr(scs), n, col_start,
+                                                           p.base_bits(), 1 if negate else 0)
+        check_status(st, "gpupoly_matrix_mul_decompose_pairs")
+        for o in outs:
+            o.is_ntt = True
+        return outs
+
     # ---- the LargeScalarMul gate: lhs * G^-1(G o c) without G or its digit matrix ----
     @staticmethod
     def _int_words(value: int) -> np.ndarray:
