@@ -650,6 +650,57 @@ int gpupoly_matrix_lut_targets(GpuMatrix *const *outs, size_t nrows_T, const Gpu
 int gpupoly_matrix_lut_targets_combine(GpuMatrix *const *outs, size_t nrows_T, const GpuMatrix *w_identity,
                                        const GpuMatrix *w_gy, const GpuMatrix *product, size_t col_start, uint32_t base_bits,
                                        const uint64_t *y_words, size_t words_per_y, const uint64_t *idx);
+/* ---- the same for the other lookup back end (extension).  The LWE public-lookup preprocessing
+ * (sample_aux_matrices_gpu, src/lookup/lwe/pubkey_gpu.rs:397-520) asks for one preimage per LUT row and column chunk and
+ * builds every target with build_adjusted_target_chunk (:193-222): a constant upload, gpu_matrix_mul_scalar over the whole of
+ * G_d and a d x m subtraction for A_z - G_d o x, a gadget slice with its mul_scalar, the decomposed hash sample
+ * (derive_k_low_chunk_for_slot, src/lookup/lwe/utils.rs:152-178), a product and two more subtractions - per row; the target
+ * then goes alone into preimage_batched_sharded.
+ *
+ * The preimage targets of T LUT rows of ONE column chunk of one (gate, slot); the outputs are the `targets` of
+ * gpupoly_trapdoor_preimage_many.  With c = outs[0]->cols, c0 = col_start, m = d * k, k = dpt * (level + 1):
+ *   outs[t] = A_lt[:, c0..c0+c) - G_d[:, c0..c0+c) o y_t - (A_z - G_d o x_t) * G^-1(U_t[:, c0..c0+c))
+ *           = A_lt[:, c0..c0+c) - G_d[:, c0..c0+c) o y_t - A_z * G^-1(U_t[:, c0..c0+c)) + x_t * U_t[:, c0..c0+c),
+ * U_t the d x m uniform matrix under hash_seed_for_matrix(key, tag_t), x_t and y_t constant polynomials.
+ *   a_z, a_lt    d x m, EVAL, one context and one level (it may be below the top)
+ *   outs[t]      d x c, made by the caller, tagged EVAL on success
+ *   y_words      host memory: T integers of words_per_y little-endian 64-bit words each, reduced mod every q_l
+ *                (gpupoly_matrix_load_coeff_words's rule; from_elem_to_constant of the reference)
+ *   x            host memory: T LUT inputs, reduced likewise (from_usize_to_constant)
+ *   tags         T tags (GpuHashTags above); "LWE_R_G_<gate>_<lut>_<entry>_slot<slot>" carries its index in the middle,
+ *                so callers send the TABLE form
+ * Everything is exact arithmetic on canonical residues, so the result equals the reference's sequence bit for bit.  The
+ * two lines are equal because G_d * G^-1(U) = U in every limb: the digits of a canonical residue, weighted by B^e mod q,
+ * sum to that residue.  x_t * U_t is read off the digits the product needs anyway - limb l of its entry (i, cc) is
+ * sum_{e < dpt} (x_t B^e mod q_l) * D_t[(i, l, e), cc] taken in limb l, which holds for the transformed digits by linearity -
+ * and column c0 + cc = (j, tw, e) of G_d o y_t is (y_t mod q_tw) B^e mod q_tw in every slot of limb tw of row j, zero
+ * elsewhere.  Nothing of size d x m is built per row and G is never filled.  The rows go in groups whose digit scratch
+ * m x (Tg * c) stays under 1 GiB, at most 2^20 rows; per group: one staged copy of the rows' table (output pointers,
+ * x_t B^e mod q_l, (y_t mod q_tw) B^e mod q_tw, computed on the host), the decomposed-blocks sample [D_0 | D_1 | ...], ONE
+ * product of A_z - as it is, no copy - against it, one combine kernel that forms every word with one lazy accumulator
+ * (dpt products and up to two negated addends on top of A_lt's word, reduced once, or every lazy window where the modulus
+ * leaves room for fewer terms) and writes it straight into its output.  The launches of a group do not depend on T: no
+ * per-row upload, launch or synchronisation.  Scratch comes from the context's allocator and is released stream-ordered;
+ * the host does not block; PACKED24 operands are unpacked first; T = 0 succeeds with nothing launched.
+ * Overlap: an outs[t] must overlap no operand and no other output, row views included (the message contains "overlap").
+ * Refused, with nothing launched and every output (residues AND tag) untouched, everything checked for every t before the
+ * first launch, the message naming this entry: a null array with T > 0, a null operand or outs[t]; a context, level or
+ * shape mismatch (operands d x m, outputs d x c); an operand not in EVAL form; col_start + c > m; outputs of different
+ * widths; words_per_y == 0; base_bits of 0 or >= 63; everything gpupoly_hash_seeds refuses of `tags`; the overlaps above.
+ * Refused likewise with "unsupported" in the text: a context created under MXX_HIP_RNG_COMPAT=reference.              */
+int gpupoly_matrix_lwe_targets(GpuMatrix *const *outs, size_t nrows_T, const GpuMatrix *a_z, const GpuMatrix *a_lt,
+                               size_t col_start, uint32_t base_bits, const uint64_t *y_words, size_t words_per_y,
+                               const uint64_t *x, const GpuHashTags *tags);
+/* Test instrument: the combine kernel of gpupoly_matrix_lwe_targets alone, with the digits - `digits` is m x (T * c), EVAL,
+ * row t's columns at t * c - and `product` = A_z * digits - d x (T * c), EVAL - GIVEN instead of sampled and multiplied:
+ *   outs[t][i, cc] = A_lt[i, c0 + cc] - G_d[i, c0 + cc] o y_t - product[i, t*c + cc]
+ *                    + (in limb l) sum_{e < dpt} (x_t B^e mod q_l) * digits[(i, l, e), t*c + cc].
+ * It lets a test reach the lazy accumulator's bound with operands no sampler produces (every residue q - 1).  One group
+ * whatever T; arguments, overlap rule and refusals as above (`digits` and `product` count as operands, digits m x (T * c),
+ * product d x (T * c); no tags, any keying).                                                                            */
+int gpupoly_matrix_lwe_targets_combine(GpuMatrix *const *outs, size_t nrows_T, const GpuMatrix *a_lt,
+                                       const GpuMatrix *digits, const GpuMatrix *product, size_t col_start,
+                                       uint32_t base_bits, const uint64_t *y_words, size_t words_per_y, const uint64_t *x);
 /* Exact scale-and-round of every coefficient (extension): coefficient k of out[i][j] becomes
  *   floor((t * c + h) / Q) mod t,   h = round_half ? floor(Q/2) : 0,
  * c the coefficient of in[i][j] as coeffs() gives it (in [0, Q)), Q the context's FULL modulus; written as its residue

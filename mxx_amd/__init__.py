@@ -53,4 +53,5 @@ from .trapdoor import (  # noqa: F401
     preimage_smoothing_parameter,
 )
 from . import lookup  # noqa: F401,E402
+from . import lwe_lookup  # noqa: F401,E402
 from . import slot_transfer  # noqa: F401,E402

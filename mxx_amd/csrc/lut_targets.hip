@@ -20,15 +20,13 @@
 // copy per group; nothing is uploaded, launched or awaited per row.
 #include "common.h"
 #include "modarith.h"
+#include "row_targets.h"
 
 #include <algorithm>
 #include <string>
-#include <utility>
 #include <vector>
 
 namespace {
-
-constexpr size_t kGroupBytes = size_t(1) << 30;  // cap on a group's digit scratch [V_0 | ...] (preimage.hip's rule for p2)
 
 // weights[((t c + cc) L + l) dpt + e'] = digit e' of ((y_t mod q_tw) B^e mod q_tw) mod q_l for column col_start + cc =
 // (j, tw, e), with decompose_kernel's masks; y: [T][L] residues of the rows' constants.  item = (row, column)
@@ -68,12 +66,6 @@ struct CombineArgs {
     const uint64_t *weights;  // device: [T c][L][dpt]
     size_t m, col_start, k, entries;
     uint32_t T, d, c, L, dpt, logN;
-};
-
-template <typename W, int VN>
-struct CombineVec {
-    typedef typename std::conditional<VN == 1, W, typename std::conditional<sizeof(W) == 4, uint4, ulonglong2>::type>::type V;
-    static_assert(sizeof(V) == sizeof(W) * VN, "vector width");
 };
 
 // out_t[i, cc] = W_id[i, c0 + cc] + sum_e' weight(t, cc, e') W_gy[i, (j, tw, e')] + top_t[i, cc] + idx_t bottom_t[i, cc], word by
@@ -181,13 +173,6 @@ int launch_combine(GpuContext *ctx, const CombineArgs &a) {
     return launch_combine_vn<W, 1>(ctx, a);  // a limb vector narrower than 16 bytes
 }
 
-// C mod q for the little-endian words of C (gpupoly_matrix_load_coeff_words's rule)
-uint64_t words_mod(const uint64_t *words, size_t count, uint64_t q) {
-    u128_t r = 0;
-    for (size_t i = count; i-- > 0;) r = ((r << 64) | words[i]) % q;  // r < q < 2^62
-    return static_cast<uint64_t>(r);
-}
-
 // what one accepted call works with
 struct LutCall {
     GpuContext *ctx;
@@ -245,27 +230,11 @@ int check_call(const char *who, GpuMatrix *const *outs, size_t T, const GpuMatri
     size_t tag_bytes = 0;
     if (!prod && hash_tags_check(who, tags, T, &tag_bytes)) return 1;
     // an output is written while every operand is still being read, and by no other row: no overlap with an operand (the
-    // stacked copy of w_v and w_vx is made first, but the rule is the entry's, not the sequence's) or with another output.
-    // The outputs' blocks are sorted by address, so T rows cost T log T comparisons
-    std::vector<std::pair<const char *, const char *>> blocks;
-    std::vector<const GpuMatrix *> seen(outs, outs + T);
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return refuse("overlap: an output is given twice");
-    for (size_t t = 0; t < T; ++t) {
-        const GpuMatrix *out = outs[t];
-        const std::string at = " (row " + std::to_string(t) + ")";
-        for (const GpuMatrix *w : ws)
-            if (storage_overlaps(out, w)) return refuse("overlap: an output overlaps an operand" + at);
-        if (prod && storage_overlaps(out, prod)) return refuse("overlap: an output overlaps the product" + at);
-        if (out->storage && out->bytes) {
-            const char *s = static_cast<const char *>(out->storage);
-            const size_t held = out->layout.v.load(std::memory_order_acquire) == GPU_MATRIX_LAYOUT_PACKED24 ? packed24_bytes(out) : out->bytes;
-            blocks.emplace_back(s, s + held);
-        }
-    }
-    std::sort(blocks.begin(), blocks.end());
-    for (size_t j = 1; j < blocks.size(); ++j)
-        if (blocks[j].first < blocks[j - 1].second) return refuse("overlap: an output overlaps another output");
+    // stacked copy of w_v and w_vx is made first, but the rule is the entry's, not the sequence's) or with another output
+    const GpuMatrix *operands[5] = {ws[0], ws[1], ws[2], ws[3], prod};
+    static const char *const names[5] = {"an operand", "an operand", "an operand", "an operand", "the product"};
+    const std::string overlap = row_outputs_overlap(outs, T, operands, names, prod ? 5 : 4);
+    if (!overlap.empty()) return refuse(overlap);
     *call = LutCall{ctx, level, static_cast<uint32_t>(L), static_cast<uint32_t>(dpt), base_bits, d, m, k, c, col_start, w_id, w_gy};
     return 0;
 }
@@ -315,18 +284,8 @@ int combine_group(const LutCall &call, GpuMatrix *const *outs, size_t Tg, const 
     return ctx->wide ? launch_combine<uint64_t>(ctx, a) : launch_combine<uint32_t>(ctx, a);
 }
 
-// a borrowed rows x cols matrix over `words` (scratch of this call: never swapped for packed storage)
 GpuMatrix scratch_matrix(const LutCall &call, size_t rows, size_t cols, void *words) {
-    GpuMatrix m;
-    m.ctx = call.ctx;
-    m.level = call.level;
-    m.rows = rows;
-    m.cols = cols;
-    m.format = GPU_POLY_FORMAT_EVAL;
-    m.bytes = rows * cols * call.L * static_cast<size_t>(call.ctx->N) * static_cast<size_t>(call.ctx->word_bytes);
-    m.storage = words;
-    m.borrowed = true;
-    return m;
+    return ::scratch_matrix(call.ctx, call.level, rows, cols, words);
 }
 
 }  // namespace
@@ -357,22 +316,14 @@ extern "C" int gpupoly_matrix_lut_targets(GpuMatrix *const *outs, size_t nrows_T
     const GpuMatrix lhs = scratch_matrix(call, 2 * call.d, call.m, stack.ptr);
     // rows per group: the digit scratch m x (Tg c) stays under the cap (one row at least), within the block sampler's 2^20
     const size_t row_bytes = call.m * call.c * poly_bytes;
-    const size_t per_group = std::min<size_t>(std::min<size_t>(T, size_t(1) << 20), std::max<size_t>(1, kGroupBytes / row_bytes));
+    const size_t per_group = rows_per_group(T, row_bytes);
     CtxBlock digits(ctx), prod(ctx);
     if (digits.alloc(per_group * row_bytes)) return 1;
     if (prod.alloc(2 * call.d * per_group * call.c * poly_bytes)) return 1;
     std::vector<size_t> offsets;
     for (size_t t0 = 0; t0 < T; t0 += per_group) {
         const size_t Tg = std::min(per_group, T - t0);
-        GpuHashTags part = *tags;
-        if (tags->form == GPUPOLY_TAGS_TABLE) {
-            offsets.resize(Tg + 1);
-            for (size_t j = 0; j <= Tg; ++j) offsets[j] = tags->tag_offsets[t0 + j] - tags->tag_offsets[t0];
-            part.tag_offsets = offsets.data();
-            if (tags->tags) part.tags = tags->tags + tags->tag_offsets[t0];
-        } else {
-            part.first_index = tags->first_index + t0;
-        }
+        const GpuHashTags part = hash_tags_rows(tags, t0, Tg, offsets);
         GpuMatrix v = scratch_matrix(call, call.m, Tg * call.c, digits.ptr);
         if (int rc = sample_decomposed_blocks_impl(who, true, &v, GPU_MATRIX_DIST_UNIFORM, nullptr, &part, Tg, base_bits, 0, call.d, call.m, col_start))
             return rc;

@@ -2334,6 +2334,33 @@ class GpuDCRTPolyMatrix:
         return outs
 
     @staticmethod
+    def lwe_targets(a_z, a_lt, col_start, col_len, ys, xs, key: bytes, tags, hash_name: str = "keccak256") -> list:
+        """The preimage targets of len(ys) LUT rows of the column chunk [col_start, col_start + col_len) of the LWE public
+        lookup in one call (gpupoly_matrix_lwe_targets):
+            A_lt[:, chunk] - G_d[:, chunk] o ys[t] - (A_z - G_d o xs[t]) G^-1(U_t[:, chunk]),
+        U_t the d x m uniform matrix under hash_seed_for_matrix(key, tags[t]); ys[t], xs[t] non-negative integers (ys of any
+        size, xs below 2^64).  The two operands are d x m EVAL matrices of one level."""
+        ys, xs = [int(y) for y in ys], [int(x) for x in xs]
+        arg, keep, count = hash_tags_arg(key, tags, hash_name)
+        assert len(ys) == len(xs) == count, "lwe_targets: one y, one x and one tag per row"
+        p = a_lt.params
+        outs = [GpuDCRTPolyMatrix(p, a_lt.nrow, col_len, a_lt.level, True) for _ in range(count)]
+        if count == 0:
+            return outs
+        words = [GpuDCRTPolyMatrix._int_words(y) for y in ys]
+        wpy = max(len(w) for w in words)
+        y_arr = np.zeros((count, wpy), dtype=np.uint64)
+        for t, w in enumerate(words):
+            y_arr[t, : len(w)] = w
+        x_arr = np.array(xs, dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        st = _ffi.lib().gpupoly_matrix_lwe_targets(GpuDCRTPolyMatrix._raw_array(outs), count, a_z.raw, a_lt.raw, col_start, p.base_bits(),
+                                                   y_arr.ctypes.data_as(u64p), wpy, x_arr.ctypes.data_as(u64p), C.byref(arg))
+        check_status(st, "gpupoly_matrix_lwe_targets")
+        del keep
+        return outs
+
+    @staticmethod
     def sample_p1_full_cached_segments(cache: GpuP1CovarianceCache, tp2, seeds, seg_cols) -> "GpuDCRTPolyMatrix":
         """`sample_p1_full_cached` over column segments with a seed each (tp2 is taken to the coefficient domain in place)."""
         out = GpuDCRTPolyMatrix.new_empty(tp2.params, tp2.nrow, tp2.ncol)
