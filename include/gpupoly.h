@@ -701,6 +701,54 @@ int gpupoly_matrix_lwe_targets(GpuMatrix *const *outs, size_t nrows_T, const Gpu
 int gpupoly_matrix_lwe_targets_combine(GpuMatrix *const *outs, size_t nrows_T, const GpuMatrix *a_lt,
                                        const GpuMatrix *digits, const GpuMatrix *product, size_t col_start,
                                        uint32_t base_bits, const uint64_t *y_words, size_t words_per_y, const uint64_t *x);
+/* ---- the commitment's public parameters (extension).  The Wee25 commitment samples one trapdoor preimage
+ * per public-parameter index and column part (sample_public_params, src/commit/wee25.rs:494-758) and builds every target
+ * on its own (:696-728): a compact-bytes reload of T_bottom's part, secret_size zero-fills, entry writes and
+ * decompositions with a concat_rows (build_j_2m_block, :536-584), two products and a subtraction; the target then goes
+ * alone into preimage.
+ *
+ * The preimage targets of T indices x P consecutive column parts; the outputs are the `targets` of
+ * gpupoly_trapdoor_preimage_many.  With s = secret_size, k = dpt * (level + 1), m_g = s * k, m_b = t_bottom's rows:
+ *   outs[t * P + p] = G_s * J(idx[t], part_start + p) - W_t * T_bottom[:, (part_start + p) * m_b .. (part_start + p + 1) * m_b)
+ *                   = X(idx[t], part_start + p)       - W_t * T_bottom[:, (part_start + p) * m_b .. (part_start + p + 1) * m_b),
+ * W_t the s x m_b uniform matrix under hash_seed_for_matrix(key, tag_t), J the row-wise concatenation of G^-1(row_i).
+ *   t_bottom     m_b x C, EVAL, C a multiple of m_b, one context and one level (it may be below the top; k follows it)
+ *   outs[t*P+p]  s x m_b, made by the caller, tagged EVAL on success
+ *   idx          host memory: T indices, any 64-bit values (global columns beyond the window simply do not hit)
+ *   tags         T tags (GpuHashTags above) naming W_t: "wee25_w_block_" followed by the index as 8 little-endian bytes is
+ *                the INDEXED_LE64 form for a consecutive run.  The library does not tie tags[t] to idx[t]
+ * Everything is exact arithmetic on canonical residues, so the result equals the reference's sequence bit for bit.  The
+ * two lines are equal because G_s * G^-1(X) = X in every limb, so G_s * J is the matrix X whose row i is row_i itself, and
+ * the index arithmetic of build_j_2m_block leaves one row non-zero: with bg = idx / m_g and rho = idx mod m_g, row
+ * i* = rho / k holds g[kk] * g[s'], kk = rho mod k, at the global columns bg * k + s', s' < k.  For kk = (tw, e) and
+ * s' = (tw', e') that is the constant 2^((e + e') * base_bits) mod q_tw in every slot of limb tw when tw == tw' and zero
+ * otherwise.  G is never built and nothing is decomposed.  The blocks go in groups whose W scratch (Tg * s) x m_b stays
+ * under 1 GiB, at most 2^20 blocks, split further by blocks or columns where the product's grid would not fit; per group:
+ * the hash launch, the stacked block sample [W_0; W_1; ...], one staged copy of the table (output pointers, i*, bg * k and
+ * kk per block, the L * dpt^2 constants computed on the host) and ONE register-tiled product of the stacked W against the
+ * window of T_bottom - as it is, no copy - whose epilogue reduces, negates canonically (q - r, 0 stays 0), adds the
+ * constant where it hits and stores every target word once, straight into its output.  The launches of a group depend on
+ * neither T nor P: no per-target upload, launch or synchronisation.  Scratch comes from the context's allocator and is
+ * released stream-ordered; the host does not block; PACKED24 operands are unpacked first; T = 0 or P = 0 succeeds with
+ * nothing launched.
+ * Overlap: an output must overlap neither an operand nor another output, row views included (the message contains
+ * "overlap").
+ * Refused, with nothing launched and every output (residues AND tag) untouched, everything checked for every output before
+ * the first launch, the message naming this entry: a null array with T * P > 0, a null operand or output; a context,
+ * level or shape mismatch (outputs s x m_b); an operand not in EVAL form; C % m_b != 0 or (part_start + P) * m_b > C;
+ * secret_size == 0; base_bits of 0 or >= 63; T * P overflowing; everything gpupoly_hash_seeds refuses of `tags`; the
+ * overlaps above.  Refused likewise with "unsupported" in the text: a context created under MXX_HIP_RNG_COMPAT=reference. */
+int gpupoly_matrix_wee25_targets(GpuMatrix *const *outs, size_t nblocks_T, size_t nparts_P, const GpuMatrix *t_bottom,
+                                 size_t part_start, size_t secret_size, uint32_t base_bits, const uint64_t *idx,
+                                 const GpuHashTags *tags);
+/* Test instrument: the product kernel of gpupoly_matrix_wee25_targets alone, with [W_0; W_1; ...] GIVEN as `w_stacked`,
+ * (T * s) x m_b, EVAL, instead of sampled:
+ *   outs[t * P + p] = X(idx[t], part_start + p) - w_stacked[t*s .. (t+1)*s, :] * T_bottom[:, part part_start + p].
+ * It lets a test reach the lazy accumulator's bound with operands no sampler produces (every residue q - 1).  Arguments,
+ * overlap rule and refusals as above (`w_stacked` counts as an operand; no tags, any keying).                            */
+int gpupoly_matrix_wee25_targets_product(GpuMatrix *const *outs, size_t nblocks_T, size_t nparts_P, const GpuMatrix *w_stacked,
+                                         const GpuMatrix *t_bottom, size_t part_start, size_t secret_size,
+                                         uint32_t base_bits, const uint64_t *idx);
 /* Exact scale-and-round of every coefficient (extension): coefficient k of out[i][j] becomes
  *   floor((t * c + h) / Q) mod t,   h = round_half ? floor(Q/2) : 0,
  * c the coefficient of in[i][j] as coeffs() gives it (in [0, Q)), Q the context's FULL modulus; written as its residue

@@ -2361,6 +2361,41 @@ class GpuDCRTPolyMatrix:
         return outs
 
     @staticmethod
+    def wee25_targets(t_bottom, part_start, nparts, secret_size, idxs, key: bytes, tags, hash_name: str = "keccak256") -> list:
+        """The preimage targets of len(idxs) public-parameter indices x `nparts` column parts of the Wee25 commitment in one
+        call (gpupoly_matrix_wee25_targets): result[t][p] is the secret_size x m_b matrix
+            G_s J(idxs[t], part_start + p) - W_t T_bottom[:, part part_start + p],
+        W_t the secret_size x m_b uniform matrix under hash_seed_for_matrix(key, tags[t]), m_b = t_bottom.nrow.  `t_bottom` is
+        an m_b x (a multiple of m_b) EVAL matrix; idxs[t] are integers below 2^64."""
+        idxs = [int(i) for i in idxs]
+        arg, keep, count = hash_tags_arg(key, tags, hash_name)
+        assert len(idxs) == count, "wee25_targets: one index and one tag per block"
+        p = t_bottom.params
+        outs = [GpuDCRTPolyMatrix(p, secret_size, t_bottom.nrow, t_bottom.level, True) for _ in range(count * nparts)]
+        if outs:
+            i_arr = np.array(idxs, dtype=np.uint64)
+            st = _ffi.lib().gpupoly_matrix_wee25_targets(GpuDCRTPolyMatrix._raw_array(outs), count, nparts, t_bottom.raw, part_start,
+                                                         secret_size, p.base_bits(), i_arr.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(arg))
+            check_status(st, "gpupoly_matrix_wee25_targets")
+        del keep
+        return [outs[t * nparts:(t + 1) * nparts] for t in range(count)]
+
+    @staticmethod
+    def wee25_targets_product(w_stacked, t_bottom, part_start, nparts, secret_size, idxs) -> list:
+        """Test instrument (gpupoly_matrix_wee25_targets_product): `wee25_targets` with the stacked [W_0; W_1; ...] given as
+        the (len(idxs) * secret_size) x m_b EVAL matrix `w_stacked` instead of sampled."""
+        idxs = [int(i) for i in idxs]
+        p = t_bottom.params
+        outs = [GpuDCRTPolyMatrix(p, secret_size, t_bottom.nrow, t_bottom.level, True) for _ in range(len(idxs) * nparts)]
+        if outs:
+            i_arr = np.array(idxs, dtype=np.uint64)
+            st = _ffi.lib().gpupoly_matrix_wee25_targets_product(GpuDCRTPolyMatrix._raw_array(outs), len(idxs), nparts, w_stacked.raw,
+                                                                 t_bottom.raw, part_start, secret_size, p.base_bits(),
+                                                                 i_arr.ctypes.data_as(C.POINTER(C.c_uint64)))
+            check_status(st, "gpupoly_matrix_wee25_targets_product")
+        return [outs[t * nparts:(t + 1) * nparts] for t in range(len(idxs))]
+
+    @staticmethod
     def sample_p1_full_cached_segments(cache: GpuP1CovarianceCache, tp2, seeds, seg_cols) -> "GpuDCRTPolyMatrix":
         """`sample_p1_full_cached` over column segments with a seed each (tp2 is taken to the coefficient domain in place)."""
         out = GpuDCRTPolyMatrix.new_empty(tp2.params, tp2.nrow, tp2.ncol)
