@@ -165,14 +165,12 @@ int gadget_table(GpuContext *ctx, uint32_t base_bits, const GadgetWeight **out) 
     const uint32_t dpt = (ctx->crt_bits + base_bits - 1) / base_bits;
     const int shift = ctx->wide ? 64 : 32;
     std::vector<GadgetWeight> host(static_cast<size_t>(ctx->limb_count) * dpt);
+    std::vector<uint64_t> w(dpt);
     for (int l = 0; l < ctx->limb_count; ++l) {
         const uint64_t q = ctx->moduli[l];
-        const uint64_t base = (1ull << base_bits) % q;  // base_bits < 63
-        uint64_t w = 1 % q;
-        for (uint32_t e = 0; e < dpt; ++e) {
-            host[static_cast<size_t>(l) * dpt + e] = {w, static_cast<uint64_t>((static_cast<u128_t>(w) << shift) / q)};
-            w = static_cast<uint64_t>(static_cast<u128_t>(w) * base % q);
-        }
+        base_powers(q, base_bits, dpt, w.data());
+        for (uint32_t e = 0; e < dpt; ++e)
+            host[static_cast<size_t>(l) * dpt + e] = {w[e], static_cast<uint64_t>((static_cast<u128_t>(w[e]) << shift) / q)};
     }
     void *dev = nullptr;
     HIP_TRY(hipMalloc(&dev, host.size() * sizeof(GadgetWeight)));

@@ -49,18 +49,6 @@ struct ScalarVec {
     typedef typename std::conditional<sizeof(W) * VN == 16, uint4, W>::type type;
 };
 
-// the sum of up to 4 products of residues: below 2^64 for residues below 2^31, below 2^126 for residues below 2^62
-template <typename W>
-__device__ __forceinline__ W lazy_reduce(typename Wide<W>::type acc, const LimbConst &lc);
-template <>
-__device__ __forceinline__ uint32_t lazy_reduce<uint32_t>(uint64_t acc, const LimbConst &lc) {
-    return reduce_u64_sum(acc, static_cast<uint32_t>(lc.q), lc.mu64);
-}
-template <>
-__device__ __forceinline__ uint64_t lazy_reduce<uint64_t>(u128_t acc, const LimbConst &lc) {
-    return reduce_u128_sum(acc, lc.q, lc.mu, lc.kbits, lc.mu64);
-}
-
 template <typename W>
 __device__ __forceinline__ W epilogue(W val, int negate, bool has_addend, W a, W q) {
     if (negate) val = val ? static_cast<W>(q - val) : static_cast<W>(0);
@@ -412,13 +400,6 @@ void accept_call(GpuMatrix *const *outs, const GpuMatrix *const *lhss, const Gpu
     }
 }
 
-// C mod q for the little-endian words of C
-uint64_t words_mod(const uint64_t *words, size_t count, uint64_t q) {
-    u128_t r = 0;
-    for (size_t i = count; i-- > 0;) r = ((r << 64) | words[i]) % q;  // r < q < 2^62
-    return static_cast<uint64_t>(r);
-}
-
 uint64_t digit_of(uint64_t residue, uint32_t ep, uint32_t base_bits, uint32_t src_bits) {  // decompose_kernel's masks
     const uint32_t shift = ep * base_bits;
     if (shift >= src_bits || shift >= 64) return 0;
@@ -446,20 +427,18 @@ int const_table(GpuContext *ctx, uint32_t L, uint32_t dpt, uint32_t base_bits, c
     }
     const int shift = ctx->wide ? 64 : 32;
     std::vector<ScalarWeight> host(static_cast<size_t>(L) * L * dpt * dpt);
+    std::vector<uint64_t> cb(dpt);  // C B^e mod q_t
     for (uint32_t t = 0; t < L; ++t) {
-        const uint64_t qt = ctx->moduli[t];
-        const uint64_t B = (1ull << base_bits) % qt;  // base_bits < 63
-        uint64_t v = key[2 + t];
+        base_powers(ctx->moduli[t], base_bits, dpt, cb.data(), key[2 + t]);
         for (uint32_t e = 0; e < dpt; ++e) {
             for (uint32_t ep = 0; ep < dpt; ++ep) {
-                const uint64_t digit = digit_of(v, ep, base_bits, ctx->limbs[t].kbits);
+                const uint64_t digit = digit_of(cb[e], ep, base_bits, ctx->limbs[t].kbits);
                 for (uint32_t l = 0; l < L; ++l) {
                     const uint64_t ql = ctx->moduli[l];
                     const uint64_t w = digit >= ql ? digit % ql : digit;
                     host[((static_cast<size_t>(l) * L + t) * dpt + ep) * dpt + e] = {w, static_cast<uint64_t>((static_cast<u128_t>(w) << shift) / ql)};
                 }
             }
-            v = static_cast<uint64_t>(static_cast<u128_t>(v) * B % qt);
         }
     }
     const size_t bytes = host.size() * sizeof(ScalarWeight);

@@ -64,42 +64,33 @@ struct CombineArgs {
     const void *prod;         // 2d x (T c): rows [0, d) the tops, rows [d, 2d) the bottoms, row t's columns at t c
     const uint64_t *rows;     // device: [T] output pointers, then [T][L] idx_t mod q_l
     const uint64_t *weights;  // device: [T c][L][dpt]
-    size_t m, col_start, k, entries;
-    uint32_t T, d, c, L, dpt, logN;
+    CombineShape s;
 };
 
 // out_t[i, cc] = W_id[i, c0 + cc] + sum_e' weight(t, cc, e') W_gy[i, (j, tw, e')] + top_t[i, cc] + idx_t bottom_t[i, cc], word by
-// word.  blockIdx.y/z = the output polynomial (t, i, cc), blockIdx.x strides its L N words VN per lane (16 bytes when VN > 1,
-// VN divides N: one limb per vector).  The dpt + 1 products (each below q^2) and the two addends go into one lazy
-// accumulator - 64 bits for 32-bit words, 128 bits for 64-bit words - reduced once, or every LimbConst::lazy_terms terms
-// where the modulus leaves room for fewer.  DPT 0: any digit count, W_gy's words loaded term by term.
+// word, for the block's output polynomial (t, i, cc) (combine_entry), VN words per lane (VN divides N: one limb per vector).
+// The dpt + 1 products and the two addends go into one lazy accumulator.  DPT 0: any digit count, W_gy's words loaded term
+// by term.
 template <typename W, int VN, int DPT>
 __global__ void __launch_bounds__(256) lut_combine_kernel(CombineArgs a, const LimbConst *__restrict__ limbs) {
     typedef typename CombineVec<W, VN>::V V;
     typedef typename Wide<W>::type D;
     const size_t entry = static_cast<size_t>(blockIdx.z) * gridDim.y + blockIdx.y;
-    if (entry >= a.entries) return;
-    const size_t per_row = static_cast<size_t>(a.d) * a.c;
-    const size_t t = entry / per_row, rest = entry - t * per_row;
-    const size_t i = rest / a.c, cc = rest - i * a.c;
-    const size_t col = a.col_start + cc;
-    const size_t jb = col / a.k;
-    const uint32_t dpt = DPT ? DPT : a.dpt;
-    const uint32_t tw = static_cast<uint32_t>(col - jb * a.k) / dpt;
-    const size_t wpp = static_cast<size_t>(a.L) << a.logN;
-    const size_t tc = static_cast<size_t>(a.T) * a.c, pc = t * a.c + cc;
-    const W *wid = static_cast<const W *>(a.w_id) + (i * a.m + col) * wpp;
-    const W *gy = static_cast<const W *>(a.w_gy) + (i * a.m + jb * a.k + static_cast<size_t>(tw) * dpt) * wpp;
-    const W *top = static_cast<const W *>(a.prod) + (i * tc + pc) * wpp;
-    const W *bot = static_cast<const W *>(a.prod) + ((a.d + i) * tc + pc) * wpp;
-    W *out = reinterpret_cast<W *>(a.rows[t]) + (i * a.c + cc) * wpp;
-    const uint64_t *idx = a.rows + a.T + t * a.L;
-    const uint64_t *wt = a.weights + pc * a.L * dpt;
+    if (entry >= a.s.entries) return;
+    const uint32_t dpt = DPT ? DPT : a.s.dpt;
+    const CombineEntry e = combine_entry(a.s, entry, dpt);
+    const size_t wpp = e.wpp;
+    const W *wid = static_cast<const W *>(a.w_id) + (e.i * a.s.m + e.col) * wpp;
+    const W *gy = static_cast<const W *>(a.w_gy) + (e.i * a.s.m + e.jb * a.s.k + static_cast<size_t>(e.tw) * dpt) * wpp;
+    const W *top = static_cast<const W *>(a.prod) + (e.i * e.tc + e.pc) * wpp;
+    const W *bot = static_cast<const W *>(a.prod) + ((a.s.d + e.i) * e.tc + e.pc) * wpp;
+    W *out = reinterpret_cast<W *>(a.rows[e.t]) + (e.i * a.s.c + e.cc) * wpp;
+    const uint64_t *idx = a.rows + a.s.T + e.t * a.s.L;
+    const uint64_t *wt = a.weights + e.pc * a.s.L * dpt;
     for (size_t w0 = (static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x) * VN; w0 < wpp;
          w0 += static_cast<size_t>(gridDim.x) * blockDim.x * VN) {
-        const uint32_t l = static_cast<uint32_t>(w0 >> a.logN);
+        const uint32_t l = static_cast<uint32_t>(w0 >> a.s.logN);
         const LimbConst lc = limbs[l];
-        const uint32_t lazy = lc.lazy_terms;
         const W x = static_cast<W>(idx[l]);
         W av[VN], tv[VN], bv[VN], ov[VN];
         *reinterpret_cast<V *>(av) = *reinterpret_cast<const V *>(wid + w0);
@@ -115,70 +106,23 @@ __global__ void __launch_bounds__(256) lut_combine_kernel(CombineArgs a, const L
         }
 #pragma unroll
         for (int v = 0; v < VN; ++v) {
-            // the accumulator carries a residue (W_id's word, or a folded sum) into every window of `lazy` terms, each at
-            // most (q - 1)^2: the bound LimbConst::lazy_terms is computed for
-            D acc = av[v];
-            uint32_t pending = 0;
-            auto fold = [&]() {
-                if constexpr (sizeof(W) == 4) acc = reduce_u64_sum(acc, static_cast<uint32_t>(lc.q), lc.mu64);
-                else acc = reduce_u128_sum(acc, lc.q, lc.mu, lc.kbits, lc.mu64);
-                pending = 0;
-            };
-            auto add = [&](D term) {
-                if (pending >= lazy) fold();
-                acc += term;
-                ++pending;
-            };
-            add(static_cast<D>(tv[v]));
-            add(static_cast<D>(x) * bv[v]);
+            LazyAcc<W> sum(av[v], lc.lazy_terms, lc);
+            sum.add(static_cast<D>(tv[v]));
+            sum.add(static_cast<D>(x) * bv[v]);
             if constexpr (DPT > 0) {
 #pragma unroll
-                for (int ep = 0; ep < DPT; ++ep) add(static_cast<D>(wv[ep]) * gv[ep][v]);
+                for (int ep = 0; ep < DPT; ++ep) sum.add(static_cast<D>(wv[ep]) * gv[ep][v]);
             } else {
-                for (uint32_t ep = 0; ep < dpt; ++ep) add(static_cast<D>(static_cast<W>(wt[l * dpt + ep])) * gy[ep * wpp + w0 + v]);
+                for (uint32_t ep = 0; ep < dpt; ++ep) sum.add(static_cast<D>(static_cast<W>(wt[l * dpt + ep])) * gy[ep * wpp + w0 + v]);
             }
-            fold();
-            ov[v] = static_cast<W>(acc);
+            ov[v] = sum.result();
         }
         *reinterpret_cast<V *>(out + w0) = *reinterpret_cast<const V *>(ov);
     }
 }
 
-template <typename W, int VN>
-int launch_combine_vn(GpuContext *ctx, const CombineArgs &a) {
-    const size_t wpp = static_cast<size_t>(a.L) << a.logN, vecs = wpp / VN;
-    const size_t gy = std::min<size_t>(a.entries, 65535), gz = (a.entries + gy - 1) / gy;
-    if (gz > 65535) return set_error("gpupoly_matrix_lut_targets: too many target polynomials in one group");
-    const unsigned threads = static_cast<unsigned>(std::min<size_t>(256, (vecs + 63) / 64 * 64));
-    const dim3 grid(static_cast<unsigned>(std::min<size_t>((vecs + threads - 1) / threads, 64)), static_cast<unsigned>(gy), static_cast<unsigned>(gz));
-    // the targets written once; W_id's chunk, top and bottom read once, W_gy's dpt words per target word (from cache after the first row)
-    MXX_TRACE_BYTES(static_cast<double>(a.entries) * wpp * sizeof(W) * (4.0 + a.dpt));
-#define MXX_COMBINE(D) MXX_LAUNCH((lut_combine_kernel<W, VN, D>), grid, dim3(threads), 0, ctx->stream, a, ctx->d_limbs)
-    switch (a.dpt) {
-        case 1: MXX_COMBINE(1); break;
-        case 2: MXX_COMBINE(2); break;
-        case 3: MXX_COMBINE(3); break;
-        case 4: MXX_COMBINE(4); break;
-        default: MXX_COMBINE(0); break;
-    }
-#undef MXX_COMBINE
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-template <typename W>
-int launch_combine(GpuContext *ctx, const CombineArgs &a) {
-    constexpr int VN = 16 / sizeof(W);
-    if (ctx->N % VN == 0) return launch_combine_vn<W, VN>(ctx, a);
-    return launch_combine_vn<W, 1>(ctx, a);  // a limb vector narrower than 16 bytes
-}
-
 // what one accepted call works with
-struct LutCall {
-    GpuContext *ctx;
-    int level;
-    uint32_t L, dpt, base_bits;
-    size_t d, m, k, c, col_start;
+struct LutCall : ChunkCall {
     const GpuMatrix *w_id, *w_gy;
 };
 
@@ -187,56 +131,30 @@ struct LutCall {
 int check_call(const char *who, GpuMatrix *const *outs, size_t T, const GpuMatrix *w_id, const GpuMatrix *w_gy, const GpuMatrix *w_v,
                const GpuMatrix *w_vx, const GpuMatrix *prod, size_t col_start, uint32_t base_bits, const uint64_t *y_words, size_t words_per_y,
                const uint64_t *idx, const GpuHashTags *tags, LutCall *call) {
-    auto refuse = [&](const std::string &what) { return set_error(std::string(who) + ": " + what); };
+    const Refuse refuse{who};
     if (!outs || !y_words || !idx) return refuse("null array");
     const GpuMatrix *ws[4] = {w_id, w_gy, prod ? w_id : w_v, prod ? w_gy : w_vx};
     for (const GpuMatrix *w : ws)
         if (!w) return refuse("null operand");
     if (!prod && !tags) return refuse("null tags");
-    for (size_t t = 0; t < T; ++t)
-        if (!outs[t]) return refuse("null output (row " + std::to_string(t) + ")");
+    if (int rc = refuse_null_outputs(refuse, outs, T, null_row)) return rc;
     if (words_per_y == 0) return refuse("words_per_y = 0");
-    if (base_bits == 0 || base_bits >= 63) return refuse("base_bits must be in 1..62");
-    GpuContext *ctx = w_id->ctx;
-    const int level = w_id->level;
-    if (level < 0 || level >= ctx->limb_count) return refuse("level out of range");
-    if (ctx->env.rng_compat && !prod) return refuse("unsupported under MXX_HIP_RNG_COMPAT=reference");
-    const size_t L = static_cast<size_t>(level) + 1;
-    const size_t dpt = (ctx->crt_bits + base_bits - 1) / base_bits;
-    const size_t k = dpt * L, d = w_id->rows, m = d * k, c = outs[0]->cols;
-    for (const GpuMatrix *w : ws) {
-        if (w->ctx != ctx) return refuse("context mismatch");
-        if (w->level != level) return refuse("level mismatch");
-        if (w->rows != d || w->cols != m) return refuse("shape mismatch: the W operands are d x (d * digits per tower * limbs)");
-        if (w->format != GPU_POLY_FORMAT_EVAL) return refuse("requires Eval format");
-    }
+    if (int rc = refuse_base_level(refuse, w_id, base_bits, !prod, call)) return rc;
+    const size_t d = w_id->rows, m = d * call->k, c = outs[0]->cols;
+    for (const GpuMatrix *w : ws)
+        if (int rc = refuse_operand(refuse, w, *call, d, m, "shape mismatch: the W operands are d x (d * digits per tower * limbs)")) return rc;
     if (prod) {
-        if (prod->ctx != ctx) return refuse("context mismatch");
-        if (prod->level != level) return refuse("level mismatch");
+        if (int rc = refuse_foreign(refuse, prod, *call)) return rc;
         if (c && T > ~size_t(0) / c) return refuse("matrix too large");
-        if (prod->rows != 2 * d || prod->cols != T * c) return refuse("shape mismatch: the product is 2d x (rows * chunk columns)");
-        if (prod->format != GPU_POLY_FORMAT_EVAL) return refuse("requires Eval format");
+        if (int rc = refuse_form(refuse, prod, 2 * d, T * c, "shape mismatch: the product is 2d x (rows * chunk columns)")) return rc;
     }
-    if (col_start > m || c > m - col_start) return refuse("column chunk past the operands' columns");
-    if (d > 0xffffffffull || c > 0xffffffffull || T > 0xffffffffull) return refuse("matrix too large");
-    for (size_t t = 0; t < T; ++t) {
-        const GpuMatrix *out = outs[t];
-        const std::string at = " (row " + std::to_string(t) + ")";
-        if (out->ctx != ctx) return refuse("context mismatch" + at);
-        if (out->level != level) return refuse("level mismatch" + at);
-        if (out->cols != c) return refuse("the outputs differ in width" + at);
-        if (out->rows != d) return refuse("shape mismatch: an output is d x chunk columns" + at);
-    }
-    size_t tag_bytes = 0;
-    if (!prod && hash_tags_check(who, tags, T, &tag_bytes)) return 1;
+    call->d = d, call->m = m, call->c = c, call->col_start = col_start, call->w_id = w_id, call->w_gy = w_gy;
+    if (int rc = refuse_chunk_outputs(refuse, outs, T, *call)) return rc;
     // an output is written while every operand is still being read, and by no other row: no overlap with an operand (the
     // stacked copy of w_v and w_vx is made first, but the rule is the entry's, not the sequence's) or with another output
     const GpuMatrix *operands[5] = {ws[0], ws[1], ws[2], ws[3], prod};
     static const char *const names[5] = {"an operand", "an operand", "an operand", "an operand", "the product"};
-    const std::string overlap = row_outputs_overlap(outs, T, operands, names, prod ? 5 : 4);
-    if (!overlap.empty()) return refuse(overlap);
-    *call = LutCall{ctx, level, static_cast<uint32_t>(L), static_cast<uint32_t>(dpt), base_bits, d, m, k, c, col_start, w_id, w_gy};
-    return 0;
+    return refuse_tags_overlap(refuse, prod ? nullptr : tags, T, outs, T, operands, names, prod ? 5 : 4);
 }
 
 // rows [0, Tg) of a group: their table (output pointers, idx and y residues) in one staged copy, the weights kernel, the
@@ -244,13 +162,9 @@ int check_call(const char *who, GpuMatrix *const *outs, size_t T, const GpuMatri
 int combine_group(const LutCall &call, GpuMatrix *const *outs, size_t Tg, const void *prod, const uint64_t *y_words, size_t words_per_y,
                   const uint64_t *idx) {
     GpuContext *ctx = call.ctx;
-    const size_t L = call.L, entries = Tg * call.d * call.c;
-    if (entries == 0) return 0;
-    const size_t table_words = Tg + 2 * Tg * L, weight_words = Tg * call.c * L * call.dpt;
-    CtxBlock block(ctx);
-    if (block.alloc(sizeof(uint64_t) * (table_words + weight_words))) return 1;
-    static thread_local std::vector<uint64_t> staging;  // the caller's arrays are not read after this call returns
-    staging.resize(table_words);
+    const size_t L = call.L, weight_words = Tg * call.c * L * call.dpt;
+    static thread_local std::vector<uint64_t> staging;
+    staging.resize(Tg + 2 * Tg * L);
     for (size_t t = 0; t < Tg; ++t) {
         staging[t] = reinterpret_cast<uint64_t>(words_ptr(outs[t]));
         for (size_t l = 0; l < L; ++l) {
@@ -258,34 +172,19 @@ int combine_group(const LutCall &call, GpuMatrix *const *outs, size_t Tg, const 
             staging[Tg + Tg * L + t * L + l] = words_mod(y_words + t * words_per_y, words_per_y, ctx->moduli[l]);
         }
     }
-    uint64_t *d_table = static_cast<uint64_t *>(block.ptr), *d_weights = d_table + table_words;
-    MXX_TRACED_COPY("LUT row table (host to device)", ctx->stream, sizeof(uint64_t) * table_words,
-                    HIP_TRY(hipMemcpyAsync(d_table, staging.data(), sizeof(uint64_t) * table_words, hipMemcpyHostToDevice, ctx->stream)));
+    CtxBlock block(ctx);
+    if (upload_table(block, "LUT row table (host to device)", staging, weight_words)) return 1;
+    uint64_t *d_table = static_cast<uint64_t *>(block.ptr), *d_weights = d_table + staging.size();
     MXX_TRACE_BYTES(sizeof(uint64_t) * (Tg * L + weight_words));
     MXX_LAUNCH(lut_weights_kernel, item_grid(Tg * call.c, 256), dim3(256), 0, ctx->stream, d_weights, d_table + Tg + Tg * L, ctx->d_limbs, Tg,
                static_cast<uint32_t>(call.c), call.col_start, call.L, call.dpt, call.base_bits);
     HIP_TRY(hipGetLastError());
-    CombineArgs a;
-    a.w_id = words_ptr(call.w_id);
-    a.w_gy = words_ptr(call.w_gy);
-    a.prod = prod;
-    a.rows = d_table;
-    a.weights = d_weights;
-    a.m = call.m;
-    a.col_start = call.col_start;
-    a.k = call.k;
-    a.entries = entries;
-    a.T = static_cast<uint32_t>(Tg);
-    a.d = static_cast<uint32_t>(call.d);
-    a.c = static_cast<uint32_t>(call.c);
-    a.L = call.L;
-    a.dpt = call.dpt;
-    a.logN = ctx->logN;
-    return ctx->wide ? launch_combine<uint64_t>(ctx, a) : launch_combine<uint32_t>(ctx, a);
-}
-
-GpuMatrix scratch_matrix(const LutCall &call, size_t rows, size_t cols, void *words) {
-    return ::scratch_matrix(call.ctx, call.level, rows, cols, words);
+    const CombineArgs a{words_ptr(call.w_id), words_ptr(call.w_gy), prod, d_table, d_weights, combine_shape(call, Tg)};
+    // the targets written once; W_id's chunk, top and bottom read once, W_gy's dpt words per target word (from cache after the first row)
+    const double bytes = static_cast<double>(a.s.entries) * (L << ctx->logN) * ctx->word_bytes * (4.0 + call.dpt);
+    return launch_combine(call.who, ctx, bytes, a.s.entries, call.L, ctx->logN, call.dpt, [&](auto cfg, dim3 grid, dim3 block_dim) {
+        MXX_LAUNCH_COMBINE(lut_combine_kernel, cfg, grid, block_dim, 0, ctx->stream, a, ctx->d_limbs);
+    });
 }
 
 }  // namespace
@@ -313,25 +212,21 @@ extern "C" int gpupoly_matrix_lut_targets(GpuMatrix *const *outs, size_t nrows_T
                     HIP_TRY(hipMemcpyAsync(stack.ptr, words_ptr(w_v), w_bytes, hipMemcpyDeviceToDevice, ctx->stream)));
     MXX_TRACED_COPY("copy (device to device)", ctx->stream, 2.0 * w_bytes,
                     HIP_TRY(hipMemcpyAsync(static_cast<char *>(stack.ptr) + w_bytes, words_ptr(w_vx), w_bytes, hipMemcpyDeviceToDevice, ctx->stream)));
-    const GpuMatrix lhs = scratch_matrix(call, 2 * call.d, call.m, stack.ptr);
-    // rows per group: the digit scratch m x (Tg c) stays under the cap (one row at least), within the block sampler's 2^20
+    const GpuMatrix lhs = scratch_matrix(ctx, call.level, 2 * call.d, call.m, stack.ptr);
+    // a group's digit scratch is m x (Tg c)
     const size_t row_bytes = call.m * call.c * poly_bytes;
     const size_t per_group = rows_per_group(T, row_bytes);
     CtxBlock digits(ctx), prod(ctx);
     if (digits.alloc(per_group * row_bytes)) return 1;
     if (prod.alloc(2 * call.d * per_group * call.c * poly_bytes)) return 1;
-    std::vector<size_t> offsets;
-    for (size_t t0 = 0; t0 < T; t0 += per_group) {
-        const size_t Tg = std::min(per_group, T - t0);
-        const GpuHashTags part = hash_tags_rows(tags, t0, Tg, offsets);
-        GpuMatrix v = scratch_matrix(call, call.m, Tg * call.c, digits.ptr);
+    return for_row_groups(T, row_bytes, tags, [&](size_t t0, size_t Tg, const GpuHashTags &part) {
+        GpuMatrix v = scratch_matrix(ctx, call.level, call.m, Tg * call.c, digits.ptr);
         if (int rc = sample_decomposed_blocks_impl(who, true, &v, GPU_MATRIX_DIST_UNIFORM, nullptr, &part, Tg, base_bits, 0, call.d, call.m, col_start))
             return rc;
-        GpuMatrix p = scratch_matrix(call, 2 * call.d, Tg * call.c, prod.ptr);
+        GpuMatrix p = scratch_matrix(ctx, call.level, 2 * call.d, Tg * call.c, prod.ptr);
         if (int rc = launch_matmul(&p, &lhs, &v)) return rc;
-        if (int rc = combine_group(call, outs + t0, Tg, prod.ptr, y_words + t0 * words_per_y, words_per_y, idx + t0)) return rc;
-    }
-    return 0;
+        return combine_group(call, outs + t0, Tg, prod.ptr, y_words + t0 * words_per_y, words_per_y, idx + t0);
+    });
     ABI_GUARD_END
 }
 

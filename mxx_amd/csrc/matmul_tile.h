@@ -39,11 +39,11 @@ constexpr uint32_t kTileKU = TR * TC * SV <= 8 ? 8 : (TR * TC * SV * sizeof(W) <
     _Pragma("unroll") for (int r = 0; r < TR; ++r) _Pragma("unroll") for (int c = 0; c < TC; ++c) \
         _Pragma("unroll") for (int s = 0; s < SV; ++s) acc[r][c][s] = 0
 
-// a lazy accumulator back into [0, q)
+// a lazy accumulator back into [0, q), q = lc.q: modarith.h's lazy_reduce under the name the tiled kernels call it by.
+// The second parameter is vestigial - the call sites still pass their q, which lazy_reduce takes from lc
 template <typename W>
-__device__ __forceinline__ W tile_reduce(typename Wide<W>::type v, W q, const LimbConst &lc) {
-    if constexpr (sizeof(W) == 4) return reduce_u64_sum(v, q, lc.mu64);
-    else return reduce_u128_sum(v, q, lc.mu, lc.kbits, lc.mu64);
+__device__ __forceinline__ W tile_reduce(typename Wide<W>::type v, W, const LimbConst &lc) {
+    return lazy_reduce<W>(v, lc);
 }
 
 // ---- host ---------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 // modarith.h — device modular arithmetic for residues held in uint32_t (q < 2^31)
 // or uint64_t (q < 2^62).  Everything stays in registers: Shoup multiplication for
 // fixed multiplicands (twiddles, n^-1), Barrett for variable x variable products,
-// mulhi-by-floor(2^64/q) for lazily accumulated 64-bit sums.
+// mulhi-by-floor(2^64/q) for lazily accumulated 64-bit sums.  At the end, for the host: the
+// constants every gadget table starts from (a big integer mod q, the powers of the base).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -123,6 +124,13 @@ __device__ __forceinline__ uint64_t reduce_u128_sum(u128_t acc, uint64_t q, uint
     return barrett_reduce(static_cast<u128_t>(y1) * r64 + y0, q, mu, k);
 }
 
+// a lazy accumulator (64 bits for 32-bit words, 128 bits for 64-bit words) back into [0, q)
+template <typename W>
+__device__ __forceinline__ W lazy_reduce(typename Wide<W>::type acc, const LimbConst &lc) {
+    if constexpr (sizeof(W) == 4) return reduce_u64_sum(acc, static_cast<uint32_t>(lc.q), lc.mu64);
+    else return reduce_u128_sum(acc, lc.q, lc.mu, lc.kbits, lc.mu64);
+}
+
 // signed 64-bit integer -> residue in [0,q)
 template <typename W>
 __device__ __forceinline__ W signed_to_residue(int64_t v, W q) {
@@ -152,4 +160,21 @@ __device__ __forceinline__ int64_t centered_residue(uint64_t v, uint64_t q) {
     uint64_t half = q >> 1;
     if (v <= half) return static_cast<int64_t>(v);
     return -static_cast<int64_t>(q - v);
+}
+
+// ---- host: the constants that the gadget tables are built from ----
+// C mod q for the little-endian words of C (gpupoly_matrix_load_coeff_words's rule)
+inline uint64_t words_mod(const uint64_t *words, size_t count, uint64_t q) {
+    u128_t r = 0;
+    for (size_t i = count; i-- > 0;) r = ((r << 64) | words[i]) % q;  // r < q < 2^62
+    return static_cast<uint64_t>(r);
+}
+
+// out[e] = v B^e mod q for e < count, B = 2^base_bits with base_bits < 63 and v < q; v = 1: the powers of the base themselves
+inline void base_powers(uint64_t q, uint32_t base_bits, size_t count, uint64_t *out, uint64_t v = 1) {
+    const uint64_t B = (1ull << base_bits) % q;
+    for (size_t e = 0; e < count; ++e) {
+        out[e] = v;
+        v = static_cast<uint64_t>(static_cast<u128_t>(v) * B % q);
+    }
 }

@@ -129,12 +129,8 @@ int launch_wee25_cfg(GpuContext *ctx, Wee25Args a, size_t b_bytes) {
 }
 
 // what one accepted call works with
-struct Wee25Call {
-    const char *who;
-    GpuContext *ctx;
-    int level;
-    uint32_t L, dpt, base_bits;
-    size_t s, m_b, k, C, T, P, part_start;
+struct Wee25Call : RowCall {
+    size_t s, m_b, C, T, P, part_start;
     const GpuMatrix *t_bottom;
 };
 
@@ -143,49 +139,33 @@ struct Wee25Call {
 int check_call(const char *who, GpuMatrix *const *outs, size_t T, size_t P, const GpuMatrix *w_stacked, const GpuMatrix *t_bottom,
                size_t part_start, size_t secret_size, uint32_t base_bits, const uint64_t *idx, const GpuHashTags *tags, bool full,
                Wee25Call *call) {
-    auto refuse = [&](const std::string &what) { return set_error(std::string(who) + ": " + what); };
+    const Refuse refuse{who};
     if (T > ~size_t(0) / P) return refuse("matrix too large: blocks x parts overflows");
     const size_t count = T * P;
+    auto part = [P](size_t j) { return std::to_string(j / P) + ", part " + std::to_string(j % P) + ")"; };
+    auto at = [&](size_t j) { return " (block " + part(j); };
     if (!outs || !idx) return refuse("null array");
     if (!t_bottom || (!full && !w_stacked)) return refuse("null operand");
     if (full && !tags) return refuse("null tags");
-    for (size_t j = 0; j < count; ++j)
-        if (!outs[j]) return refuse("null output (block " + std::to_string(j / P) + ", part " + std::to_string(j % P) + ")");
+    if (int rc = refuse_null_outputs(refuse, outs, count, [&](size_t j) { return "null output (block " + part(j); })) return rc;
     if (secret_size == 0) return refuse("secret_size = 0");
-    if (base_bits == 0 || base_bits >= 63) return refuse("base_bits must be in 1..62");
-    GpuContext *ctx = t_bottom->ctx;
-    const int level = t_bottom->level;
-    if (level < 0 || level >= ctx->limb_count) return refuse("level out of range");
-    if (ctx->env.rng_compat && full) return refuse("unsupported under MXX_HIP_RNG_COMPAT=reference");
-    const size_t L = static_cast<size_t>(level) + 1;
-    const size_t dpt = (ctx->crt_bits + base_bits - 1) / base_bits;
-    const size_t s = secret_size, m_b = t_bottom->rows, C = t_bottom->cols, k = dpt * L;
+    if (int rc = refuse_base_level(refuse, t_bottom, base_bits, full, call)) return rc;
+    const size_t s = secret_size, m_b = t_bottom->rows, C = t_bottom->cols;
     if (t_bottom->format != GPU_POLY_FORMAT_EVAL) return refuse("requires Eval format");
     if (m_b == 0 || C % m_b != 0) return refuse("shape mismatch: T_bottom is m_b x (a multiple of m_b)");
     if (part_start > C / m_b || P > C / m_b - part_start) return refuse("column parts past T_bottom's columns");
     if (s > 0xffffffffull || m_b > 0xffffffffull || T > ~size_t(0) / s) return refuse("matrix too large");
-    if (w_stacked) {
-        if (w_stacked->ctx != ctx) return refuse("context mismatch");
-        if (w_stacked->level != level) return refuse("level mismatch");
-        if (w_stacked->rows != T * s || w_stacked->cols != m_b) return refuse("shape mismatch: the stacked W is (blocks * secret_size) x m_b");
-        if (w_stacked->format != GPU_POLY_FORMAT_EVAL) return refuse("requires Eval format");
-    }
-    for (size_t j = 0; j < count; ++j) {
-        const GpuMatrix *out = outs[j];
-        const std::string at = " (block " + std::to_string(j / P) + ", part " + std::to_string(j % P) + ")";
-        if (out->ctx != ctx) return refuse("context mismatch" + at);
-        if (out->level != level) return refuse("level mismatch" + at);
-        if (out->rows != s || out->cols != m_b) return refuse("shape mismatch: an output is secret_size x m_b" + at);
-    }
-    size_t tag_bytes = 0;
-    if (full && hash_tags_check(who, tags, T, &tag_bytes)) return 1;
+    if (w_stacked)
+        if (int rc = refuse_operand(refuse, w_stacked, *call, T * s, m_b, "shape mismatch: the stacked W is (blocks * secret_size) x m_b")) return rc;
+    if (int rc = refuse_outputs(refuse, outs, count, *call, at, [&](const GpuMatrix *out) {
+            return out->rows != s || out->cols != m_b ? "shape mismatch: an output is secret_size x m_b" : nullptr;
+        }))
+        return rc;
+    call->s = s, call->m_b = m_b, call->C = C, call->T = T, call->P = P, call->part_start = part_start, call->t_bottom = t_bottom;
     // an output is written while every operand is still being read, and by no other tile
     const GpuMatrix *operands[2] = {t_bottom, w_stacked};
     static const char *const names[2] = {"T_bottom", "the stacked W"};
-    const std::string overlap = row_outputs_overlap(outs, count, operands, names, w_stacked ? 2 : 1);
-    if (!overlap.empty()) return refuse(overlap);
-    *call = Wee25Call{who, ctx, level, static_cast<uint32_t>(L), static_cast<uint32_t>(dpt), base_bits, s, m_b, k, C, T, P, part_start, t_bottom};
-    return 0;
+    return refuse_tags_overlap(refuse, full ? tags : nullptr, T, outs, count, operands, names, w_stacked ? 2 : 1);
 }
 
 bool grid_fits(const GpuContext *ctx, size_t rows, size_t cols, size_t L) {
@@ -200,11 +180,8 @@ int product_group(const Wee25Call &call, GpuMatrix *const *outs, const uint64_t 
     const size_t L = call.L, dpt = call.dpt, m_b = call.m_b, m_g = call.s * call.k;
     const size_t gcol0 = call.part_start * m_b + col0;
     const size_t part0 = gcol0 / m_b, Pg = (gcol0 + cw - 1) / m_b - part0 + 1;
-    const size_t table_words = Tg * Pg + Tg * 3 + L * dpt * dpt;
-    CtxBlock block(ctx);
-    if (block.alloc(sizeof(uint64_t) * table_words)) return 1;
-    static thread_local std::vector<uint64_t> staging, pw;  // the caller's arrays are not read after this call returns
-    staging.resize(table_words);
+    static thread_local std::vector<uint64_t> staging, pw;
+    staging.resize(Tg * Pg + Tg * 3 + L * dpt * dpt);
     uint64_t *hits = staging.data() + Tg * Pg, *consts = hits + Tg * 3;
     for (size_t t = 0; t < Tg; ++t) {
         for (size_t p = 0; p < Pg; ++p)
@@ -216,20 +193,16 @@ int product_group(const Wee25Call &call, GpuMatrix *const *outs, const uint64_t 
     }
     pw.resize(2 * dpt);
     for (size_t l = 0; l < L; ++l) {
-        const uint64_t q = ctx->moduli[l];
-        const uint64_t B = (1ull << call.base_bits) % q;  // base_bits < 63
-        pw[0] = 1 % q;
-        for (size_t j = 1; j < 2 * dpt; ++j) pw[j] = static_cast<uint64_t>(static_cast<unsigned __int128>(pw[j - 1]) * B % q);
+        base_powers(ctx->moduli[l], call.base_bits, 2 * dpt, pw.data());
         for (size_t e = 0; e < dpt; ++e)
             for (size_t e2 = 0; e2 < dpt; ++e2) consts[(l * dpt + e) * dpt + e2] = pw[e + e2];
     }
-    uint64_t *d_table = static_cast<uint64_t *>(block.ptr);
-    MXX_TRACED_COPY("Wee25 target table (host to device)", ctx->stream, sizeof(uint64_t) * table_words,
-                    HIP_TRY(hipMemcpyAsync(d_table, staging.data(), sizeof(uint64_t) * table_words, hipMemcpyHostToDevice, ctx->stream)));
+    CtxBlock block(ctx);
+    if (upload_table(block, "Wee25 target table (host to device)", staging)) return 1;
     Wee25Args a;
     a.w = w;
     a.b = words_ptr(call.t_bottom);
-    a.table = d_table;
+    a.table = static_cast<const uint64_t *>(block.ptr);
     a.C = call.C;
     a.gcol0 = gcol0;
     a.rows = static_cast<uint32_t>(Tg * call.s);
@@ -284,27 +257,21 @@ extern "C" int gpupoly_matrix_wee25_targets(GpuMatrix *const *outs, size_t nbloc
     Wee25Call call;
     if (check_call(who, outs, T, P, nullptr, t_bottom, part_start, secret_size, base_bits, idx, tags, true, &call)) return 1;
     GpuContext *ctx = call.ctx;
-    const size_t poly_bytes = static_cast<size_t>(call.L) * ctx->N * ctx->word_bytes;
-    // blocks per group: the W scratch (Tg s) x m_b stays under the cap (one block at least), within the block sampler's 2^20
-    const size_t block_bytes = call.s * call.m_b * poly_bytes;
-    const size_t per_group = rows_per_group(T, block_bytes);
+    // a group's W scratch is (Tg s) x m_b
+    const size_t block_bytes = call.s * call.m_b * static_cast<size_t>(call.L) * ctx->N * ctx->word_bytes;
     if (!grid_fits(ctx, call.s, 1, call.L)) return set_error(std::string(who) + ": matrix too large");
     // ---- accepted ----
     for (size_t j = 0; j < T * P; ++j) outs[j]->format = GPU_POLY_FORMAT_EVAL;
     if (ctx_activate(ctx)) return 1;
     words_ptr(t_bottom);  // a PACKED24 operand is unpacked once
     CtxBlock w(ctx);
-    if (w.alloc(per_group * block_bytes)) return 1;
-    std::vector<size_t> offsets;
-    for (size_t t0 = 0; t0 < T; t0 += per_group) {
-        const size_t Tg = std::min(per_group, T - t0);
-        const GpuHashTags part = hash_tags_rows(tags, t0, Tg, offsets);
+    if (w.alloc(rows_per_group(T, block_bytes) * block_bytes)) return 1;
+    return for_row_groups(T, block_bytes, tags, [&](size_t t0, size_t Tg, const GpuHashTags &part) {
         // row t of the stacked layout = the s m_b polynomials of block t row-major: the (Tg s) x m_b factor as it lies
         GpuMatrix v = scratch_matrix(ctx, call.level, Tg, call.s * call.m_b, w.ptr);
         if (int rc = sample_blocks_impl(who, true, &v, GPU_MATRIX_DIST_UNIFORM, nullptr, &part, Tg, GPUPOLY_BLOCKS_STACKED, nullptr, nullptr)) return rc;
-        if (int rc = product_blocks(call, outs, idx, t0, Tg, w.ptr)) return rc;
-    }
-    return 0;
+        return product_blocks(call, outs, idx, t0, Tg, w.ptr);
+    });
     ABI_GUARD_END
 }
 

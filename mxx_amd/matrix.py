@@ -2306,6 +2306,27 @@ class GpuDCRTPolyMatrix:
         return out
 
     @staticmethod
+    def _int_rows(values):
+        """The non-negative integers `values` (one at least) as a (count, words) little-endian uint64 array, and `words`."""
+        words = [GpuDCRTPolyMatrix._int_words(v) for v in values]
+        arr = np.zeros((len(words), max(len(w) for w in words)), dtype=np.uint64)
+        for t, w in enumerate(words):
+            arr[t, : len(w)] = w
+        return arr, arr.shape[1]
+
+    @staticmethod
+    def _wee25_call(entry: str, t_bottom, nparts, secret_size, idxs, args) -> list:
+        """len(idxs) x nparts fresh secret_size x m_b outputs, `entry(outs, len(idxs), nparts, *args(idx array))` when there is
+        any, and the outputs regrouped by block."""
+        p = t_bottom.params
+        outs = [GpuDCRTPolyMatrix(p, secret_size, t_bottom.nrow, t_bottom.level, True) for _ in range(len(idxs) * nparts)]
+        if outs:
+            i_arr = np.array(idxs, dtype=np.uint64)
+            st = getattr(_ffi.lib(), entry)(GpuDCRTPolyMatrix._raw_array(outs), len(idxs), nparts, *args(i_arr.ctypes.data_as(C.POINTER(C.c_uint64))))
+            check_status(st, entry)
+        return [outs[t * nparts:(t + 1) * nparts] for t in range(len(idxs))]
+
+    @staticmethod
     def lut_targets(w_identity, w_gy, w_v, w_vx, col_start, col_len, ys, idxs, key: bytes, tags, hash_name: str = "keccak256") -> list:
         """The preimage targets of len(ys) LUT rows of the column chunk [col_start, col_start + col_len) in one call
         (gpupoly_matrix_lut_targets):
@@ -2319,11 +2340,7 @@ class GpuDCRTPolyMatrix:
         outs = [GpuDCRTPolyMatrix(p, w_identity.nrow, col_len, w_identity.level, True) for _ in range(count)]
         if count == 0:
             return outs
-        words = [GpuDCRTPolyMatrix._int_words(y) for y in ys]
-        wpy = max(len(w) for w in words)
-        y_arr = np.zeros((count, wpy), dtype=np.uint64)
-        for t, w in enumerate(words):
-            y_arr[t, : len(w)] = w
+        y_arr, wpy = GpuDCRTPolyMatrix._int_rows(ys)
         i_arr = np.array(idxs, dtype=np.uint64)
         u64p = C.POINTER(C.c_uint64)
         st = _ffi.lib().gpupoly_matrix_lut_targets(GpuDCRTPolyMatrix._raw_array(outs), count, w_identity.raw, w_gy.raw, w_v.raw, w_vx.raw,
@@ -2347,11 +2364,7 @@ class GpuDCRTPolyMatrix:
         outs = [GpuDCRTPolyMatrix(p, a_lt.nrow, col_len, a_lt.level, True) for _ in range(count)]
         if count == 0:
             return outs
-        words = [GpuDCRTPolyMatrix._int_words(y) for y in ys]
-        wpy = max(len(w) for w in words)
-        y_arr = np.zeros((count, wpy), dtype=np.uint64)
-        for t, w in enumerate(words):
-            y_arr[t, : len(w)] = w
+        y_arr, wpy = GpuDCRTPolyMatrix._int_rows(ys)
         x_arr = np.array(xs, dtype=np.uint64)
         u64p = C.POINTER(C.c_uint64)
         st = _ffi.lib().gpupoly_matrix_lwe_targets(GpuDCRTPolyMatrix._raw_array(outs), count, a_z.raw, a_lt.raw, col_start, p.base_bits(),
@@ -2370,30 +2383,20 @@ class GpuDCRTPolyMatrix:
         idxs = [int(i) for i in idxs]
         arg, keep, count = hash_tags_arg(key, tags, hash_name)
         assert len(idxs) == count, "wee25_targets: one index and one tag per block"
-        p = t_bottom.params
-        outs = [GpuDCRTPolyMatrix(p, secret_size, t_bottom.nrow, t_bottom.level, True) for _ in range(count * nparts)]
-        if outs:
-            i_arr = np.array(idxs, dtype=np.uint64)
-            st = _ffi.lib().gpupoly_matrix_wee25_targets(GpuDCRTPolyMatrix._raw_array(outs), count, nparts, t_bottom.raw, part_start,
-                                                         secret_size, p.base_bits(), i_arr.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(arg))
-            check_status(st, "gpupoly_matrix_wee25_targets")
+        base = t_bottom.params.base_bits()
+        out = GpuDCRTPolyMatrix._wee25_call("gpupoly_matrix_wee25_targets", t_bottom, nparts, secret_size, idxs,
+                                            lambda i_ptr: (t_bottom.raw, part_start, secret_size, base, i_ptr, C.byref(arg)))
         del keep
-        return [outs[t * nparts:(t + 1) * nparts] for t in range(count)]
+        return out
 
     @staticmethod
     def wee25_targets_product(w_stacked, t_bottom, part_start, nparts, secret_size, idxs) -> list:
         """Test instrument (gpupoly_matrix_wee25_targets_product): `wee25_targets` with the stacked [W_0; W_1; ...] given as
         the (len(idxs) * secret_size) x m_b EVAL matrix `w_stacked` instead of sampled."""
         idxs = [int(i) for i in idxs]
-        p = t_bottom.params
-        outs = [GpuDCRTPolyMatrix(p, secret_size, t_bottom.nrow, t_bottom.level, True) for _ in range(len(idxs) * nparts)]
-        if outs:
-            i_arr = np.array(idxs, dtype=np.uint64)
-            st = _ffi.lib().gpupoly_matrix_wee25_targets_product(GpuDCRTPolyMatrix._raw_array(outs), len(idxs), nparts, w_stacked.raw,
-                                                                 t_bottom.raw, part_start, secret_size, p.base_bits(),
-                                                                 i_arr.ctypes.data_as(C.POINTER(C.c_uint64)))
-            check_status(st, "gpupoly_matrix_wee25_targets_product")
-        return [outs[t * nparts:(t + 1) * nparts] for t in range(len(idxs))]
+        base = t_bottom.params.base_bits()
+        return GpuDCRTPolyMatrix._wee25_call("gpupoly_matrix_wee25_targets_product", t_bottom, nparts, secret_size, idxs,
+                                             lambda i_ptr: (w_stacked.raw, t_bottom.raw, part_start, secret_size, base, i_ptr))
 
     @staticmethod
     def sample_p1_full_cached_segments(cache: GpuP1CovarianceCache, tp2, seeds, seg_cols) -> "GpuDCRTPolyMatrix":

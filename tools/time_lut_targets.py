@@ -6,7 +6,8 @@ and the same two followed by `preimage_many_abi` over the targets (loop+pre, cal
   n = 256, 12 x 51 bits, base 2^17, d = 2, c = 4, T = 16 and T = 64;   n = 2^14, 8 x 24 bits, base 2^12, d = 1, c = 4, T = 16.
 The targets of both legs are compared first (`gpu_matrix_equal`) and A x == target is checked.  Then the legs alternate;
 every leg is bracketed by device events on the context's stream and by the host clock until the device is idle; median,
-minimum and maximum of REPS (6) after a warm-up - the spread is max - min of a leg -, launches per call from
+minimum, maximum and 90th percentile (nearest rank, as time_lwe_targets.py takes it) of REPS (6) after a warm-up - the
+spread is max - min of a leg -, launches per call from
 gpupoly_launch_count, and the launch trace of both target legs summed per kernel.  Output goes to stdout and to
 profiles/lut_targets_timing.txt (or the path given as the first argument)."""
 import collections
@@ -30,6 +31,11 @@ SHAPES = [
 lib = _ffi.lib()
 OUT = open(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "lut_targets_timing.txt"), "w")
 _PARAMS = {}
+
+
+def pct(xs, q):
+    xs = sorted(xs)
+    return xs[min(len(xs) - 1, max(0, round(q * (len(xs) - 1))))]
 
 
 def say(line):
@@ -94,8 +100,8 @@ def run_shape(name, n, limbs, bits, base, d, c, T):
             launches[nm] = lib.gpupoly_launch_count() - c0
             del out
     for nm, _ in legs:
-        say(f"{nm:9s} device events median {statistics.median(dev[nm]):.3f} ms (min {min(dev[nm]):.3f}, max {max(dev[nm]):.3f}), "
-            f"host until idle median {statistics.median(wall[nm]):.3f} ms (min {min(wall[nm]):.3f}, max {max(wall[nm]):.3f}), "
+        say(f"{nm:9s} device events median {statistics.median(dev[nm]):.3f} ms (min {min(dev[nm]):.3f}, max {max(dev[nm]):.3f}, p90 {pct(dev[nm], 0.9):.3f}), "
+            f"host until idle median {statistics.median(wall[nm]):.3f} ms (min {min(wall[nm]):.3f}, max {max(wall[nm]):.3f}, p90 {pct(wall[nm], 0.9):.3f}), "
             f"{launches[nm]} launches per call")
     for nm, fn in legs[:2]:
         mx.gpu_device_sync()
