@@ -749,6 +749,62 @@ int gpupoly_matrix_wee25_targets(GpuMatrix *const *outs, size_t nblocks_T, size_
 int gpupoly_matrix_wee25_targets_product(GpuMatrix *const *outs, size_t nblocks_T, size_t nparts_P, const GpuMatrix *w_stacked,
                                          const GpuMatrix *t_bottom, size_t part_start, size_t secret_size,
                                          uint32_t base_bits, const uint64_t *idx);
+/* ---- the online side of the GGH15 lookup (extension).  The evaluator's build_public_lookup_output_chunk
+ * (src/lookup/ggh15/encoding.rs:172-300; device path src/lookup/ggh15/poly_encoding_gpu.rs:338-567,686-1420, stage-1 /
+ * stage-2 tasks of one product each) runs per slot and output chunk: it re-reads the five gate preimages, samples and
+ * decomposes V up to three times and multiplies P * rhs before c_b0 * (...).  With d the secret size, k = dpt * (level + 1),
+ * m_g = d * k, w = d * (k + 2), r the rows of an encoding vector (1 in the reference), c_b0_s r x w, c_in_s r x m_g, x_s the
+ * slot's plaintext, (k_s, y_s) = plt.get(x_s), V_s = G^-1(U_s[:, chunk]) for the d x m_g uniform U_s under tag_s
+ * ("ggh15_lut_v_idx_<lut>_<k_s>") and K_s the chunk of the LUT-row preimage lut_aux_<lut>_idx<k_s>:
+ *   out_s[:, chunk] = (c_b0_s P_id)[:, chunk] + (c_b0_s P_gy) G^-1(G_d[:, chunk] o y_s)
+ *                   + (c_b0_s P_v + x_s o (c_b0_s P_vx) + c_in_s G^-1(U_g)) V_s - (c_b0_s P_g1) K_s.
+ * Everything is exact ring arithmetic on canonical residues, so this re-association of the reference's c_b0 * (P * rhs)
+ * changes no bit.  STAGE 1 is the caller's, with the existing product entries: the S slots' c_b0 / c_in stacked into
+ * (S r)-row left factors against P_id, P_gy, P_v, P_vx, P_g1 and G^-1(U_g), each read once per wave instead of once per
+ * slot and chunk.
+ *
+ * STAGE 2 of the lookup for S slots of one gate and ONE output column chunk [col_start, col_start + c), c = outs[0]->cols.
+ * mid_* are the stage-1 products, slot s in rows [s r, (s + 1) r):
+ *   mid_identity, mid_gy, mid_v, mid_vx, mid_rand   (S r) x m_g, EVAL      mid_gate1   (S r) x w, EVAL
+ *   lut_preimages[s]   w x c, EVAL (the stored column chunk of the slot's LUT-row preimage; the same matrix may be given
+ *                      for several slots)        xs[s]   1 x 1, EVAL        outs[s]   r x c, made by the caller, tagged EVAL
+ *   y_words / tags     as gpupoly_matrix_lut_targets (y_s reduced mod every q_l; tag_s names U_s)
+ * The slots go in groups whose scratch - the digits m_g x (Sg c) and the left factor (Sg r) x (m_g + w) - stays under 1 GiB
+ * (MXX_HIP_GGH15_LOOKUP_BUDGET=<bytes> overrides the cap), at most 2^20 slots.  Per group: ONE staged copy of the slots'
+ * table (output, K_s and x_s pointers; the weights of the gy term, digit e' of (y_s mod q_tw) B^e mod q_tw per (s, cc, e'),
+ * computed on the host), the decomposed-blocks hash sample [V_0 | V_1 | ...], ONE pre-pass kernel that writes
+ * Lhs = [mid_v + x_s o mid_vx + mid_rand | neg(mid_gate1)] with canonical residues (neg(0) = 0), and ONE main kernel: every
+ * output word is mid_identity's word + m_g terms against V_s + w terms against K_s, read in place through the table, + dpt
+ * weighted words of mid_gy, in one lazy accumulator folded every lazy_terms terms wherever they fall, reduced once, written
+ * once.  A lane holds a term's left words in registers for a tile of up to 4 chunk columns and 2 rows, 16 bytes per load
+ * and store (one word where a limb vector is narrower).  Launches per group: the sampler's (those of
+ * gpupoly_matrix_sample_hash_decomposed_blocks for Sg tags) + 2 kernels + 1 copy, whatever S - 7 kernels and 2 copies for
+ * 48 slots as for 2 at n = 256, 3 x 51 bits, against 88 kernels and 20 copies of the per-slot sequence for 2 slots of one
+ * chunk (tests/test_gpu_ggh15_lookup.py); the slot descriptors live in the device table, not in the kernel arguments.  Scratch comes from the context's allocator and is released
+ * stream-ordered; the host does not block; PACKED24 operands are unpacked first; S = 0 and c = 0 succeed with nothing
+ * launched.
+ * Overlap: an outs[s] must overlap no mid_*, no lut_preimages[t], no xs[t] and no other output, row views included (the
+ * message contains "overlap").
+ * Refused, with nothing launched and every output (residues AND tag) untouched, everything checked for every slot before
+ * the first launch, the message naming this entry: a null array or entry; a context, level or shape mismatch; (S r) not
+ * divisible by S; an operand not in EVAL form; col_start + c > m_g; outputs of different widths; words_per_y == 0;
+ * base_bits of 0 or >= 63; everything gpupoly_hash_seeds refuses of `tags`; the overlaps above.  Refused likewise with
+ * "unsupported" in the text: a context created under MXX_HIP_RNG_COMPAT=reference.                                       */
+int gpupoly_matrix_ggh15_lookup(GpuMatrix *const *outs, size_t nslots_S, const GpuMatrix *mid_identity,
+                                const GpuMatrix *mid_gy, const GpuMatrix *mid_v, const GpuMatrix *mid_vx,
+                                const GpuMatrix *mid_rand, const GpuMatrix *mid_gate1,
+                                const GpuMatrix *const *lut_preimages, const GpuMatrix *const *xs, size_t col_start,
+                                uint32_t base_bits, const uint64_t *y_words, size_t words_per_y, const GpuHashTags *tags);
+/* Test instrument: the same with the digits GIVEN - `digits` is m_g x (S * c), EVAL, slot s at columns [s c, (s + 1) c) -
+ * instead of sampled: the table copy, the pre-pass and the main kernel alone, one group whatever S.  It lets a test reach
+ * the lazy accumulator's bound with operands no sampler produces.  Arguments, overlap rule and refusals as above (`digits`
+ * counts as an operand; no tags, any RNG keying).                                                                        */
+int gpupoly_matrix_ggh15_lookup_combine(GpuMatrix *const *outs, size_t nslots_S, const GpuMatrix *mid_identity,
+                                        const GpuMatrix *mid_gy, const GpuMatrix *mid_v, const GpuMatrix *mid_vx,
+                                        const GpuMatrix *mid_rand, const GpuMatrix *mid_gate1,
+                                        const GpuMatrix *const *lut_preimages, const GpuMatrix *const *xs, size_t col_start,
+                                        uint32_t base_bits, const uint64_t *y_words, size_t words_per_y,
+                                        const GpuMatrix *digits);
 /* Exact scale-and-round of every coefficient (extension): coefficient k of out[i][j] becomes
  *   floor((t * c + h) / Q) mod t,   h = round_half ? floor(Q/2) : 0,
  * c the coefficient of in[i][j] as coeffs() gives it (in [0, Q)), Q the context's FULL modulus; written as its residue

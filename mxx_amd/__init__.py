@@ -54,5 +54,6 @@ from .trapdoor import (  # noqa: F401
 )
 from . import lookup  # noqa: F401,E402
 from . import lwe_lookup  # noqa: F401,E402
+from . import ggh15_eval  # noqa: F401,E402
 from . import slot_transfer  # noqa: F401,E402
 from . import commit  # noqa: F401,E402

@@ -137,8 +137,8 @@ inline int refuse_tags_overlap(const Refuse &refuse, const GpuHashTags *tags, si
 constexpr size_t kRowGroupBytes = size_t(1) << 30;  // cap on a group's scratch [V_0 | ...] (preimage.hip's rule for p2)
 
 // rows per group: the scratch of row_bytes per row stays under the cap (one row at least), within the block sampler's 2^20
-inline size_t rows_per_group(size_t T, size_t row_bytes) {
-    return std::min<size_t>(std::min<size_t>(T, size_t(1) << 20), std::max<size_t>(1, kRowGroupBytes / row_bytes));
+inline size_t rows_per_group(size_t T, size_t row_bytes, size_t cap = kRowGroupBytes) {
+    return std::min<size_t>(std::min<size_t>(T, size_t(1) << 20), std::max<size_t>(1, cap / row_bytes));
 }
 
 // a borrowed rows x cols EVAL matrix over `words` (scratch of one call: never swapped for packed storage)
@@ -169,10 +169,10 @@ inline GpuHashTags hash_tags_rows(const GpuHashTags *tags, size_t t0, size_t Tg,
     return part;
 }
 
-// body(t0, Tg, the tags of rows [t0, t0 + Tg)) for every group of rows_per_group(T, row_bytes) rows, until one fails
+// body(t0, Tg, the tags of rows [t0, t0 + Tg)) for every group of rows_per_group(T, row_bytes, cap) rows, until one fails
 template <typename Body>
-int for_row_groups(size_t T, size_t row_bytes, const GpuHashTags *tags, Body &&body) {
-    const size_t per_group = rows_per_group(T, row_bytes);
+int for_row_groups(size_t T, size_t row_bytes, const GpuHashTags *tags, Body &&body, size_t cap = kRowGroupBytes) {
+    const size_t per_group = rows_per_group(T, row_bytes, cap);
     std::vector<size_t> offsets;
     for (size_t t0 = 0; t0 < T; t0 += per_group) {
         const size_t Tg = std::min(per_group, T - t0);

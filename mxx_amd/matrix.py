@@ -2399,6 +2399,44 @@ class GpuDCRTPolyMatrix:
                                              lambda i_ptr: (w_stacked.raw, t_bottom.raw, part_start, secret_size, base, i_ptr))
 
     @staticmethod
+    def _ggh15_lookup_call(entry: str, mids, lut_preimages, xs, col_start, col_len, ys, last) -> list:
+        """len(ys) fresh r x col_len outputs and `entry(outs, S, *mids, K array, x array, col_start, base, y words, words, last)`"""
+        mids, lut_preimages, xs, ys = list(mids), list(lut_preimages), list(xs), [int(y) for y in ys]
+        count = len(ys)
+        assert len(mids) == 6 and len(lut_preimages) == len(xs) == count, "ggh15_lookup: six stage-1 products; one K, x and y per slot"
+        first = mids[0]
+        outs = [GpuDCRTPolyMatrix(first.params, first.nrow // max(count, 1), col_len, first.level, True) for _ in range(count)]
+        if count == 0:
+            return outs
+        y_arr, wpy = GpuDCRTPolyMatrix._int_rows(ys)
+        st = getattr(_ffi.lib(), entry)(GpuDCRTPolyMatrix._raw_array(outs), count, *[m.raw for m in mids], GpuDCRTPolyMatrix._raw_array(lut_preimages),
+                                        GpuDCRTPolyMatrix._raw_array(xs), col_start, first.params.base_bits(),
+                                        y_arr.ctypes.data_as(C.POINTER(C.c_uint64)), wpy, last)
+        check_status(st, entry)
+        return outs
+
+    @staticmethod
+    def ggh15_lookup(mids, lut_preimages, xs, col_start, col_len, ys, key: bytes, tags, hash_name: str = "keccak256") -> list:
+        """Stage 2 of the GGH15 public lookup for len(ys) slots of one gate and the output column chunk
+        [col_start, col_start + col_len) in one call (gpupoly_matrix_ggh15_lookup):
+            mid_id_s[:, chunk] + mid_gy_s G^-1(G_d[:, chunk] o ys[s]) + (mid_v_s + xs[s] o mid_vx_s + mid_rand_s) V_s - mid_g1_s K_s,
+        `mids` = (mid_identity, mid_gy, mid_v, mid_vx, mid_rand, mid_gate1), the stage-1 products with slot s in rows
+        [s r, (s + 1) r); lut_preimages[s] = K_s (w x col_len; one matrix may serve several slots), xs[s] the slot's plaintext
+        as a 1 x 1 EVAL matrix, V_s = G^-1(U_s[:, chunk]) with U_s the d x m_g uniform matrix under
+        hash_seed_for_matrix(key, tags[s]).  Returns the slots' r x col_len matrices."""
+        arg, keep, count = hash_tags_arg(key, tags, hash_name)
+        assert count == len(ys), "ggh15_lookup: one tag per slot"
+        out = GpuDCRTPolyMatrix._ggh15_lookup_call("gpupoly_matrix_ggh15_lookup", mids, lut_preimages, xs, col_start, col_len, ys, C.byref(arg))
+        del keep
+        return out
+
+    @staticmethod
+    def ggh15_lookup_combine(mids, lut_preimages, xs, digits, col_start, col_len, ys) -> list:
+        """Test instrument (gpupoly_matrix_ggh15_lookup_combine): `ggh15_lookup` with [V_0 | V_1 | ...] given as the
+        m_g x (len(ys) * col_len) EVAL matrix `digits` instead of sampled."""
+        return GpuDCRTPolyMatrix._ggh15_lookup_call("gpupoly_matrix_ggh15_lookup_combine", mids, lut_preimages, xs, col_start, col_len, ys, digits.raw)
+
+    @staticmethod
     def sample_p1_full_cached_segments(cache: GpuP1CovarianceCache, tp2, seeds, seg_cols) -> "GpuDCRTPolyMatrix":
         """`sample_p1_full_cached` over column segments with a seed each (tp2 is taken to the coefficient domain in place)."""
         out = GpuDCRTPolyMatrix.new_empty(tp2.params, tp2.nrow, tp2.ncol)
