@@ -413,3 +413,9 @@ int launch_copy_block(GpuMatrix *out, const GpuMatrix *src, size_t dst_row, size
 int sample_p1_keyed_segments(const GpuP1CovarianceCache *cache, const P1KeyEntry *d_keys, const GpuMatrix *tp2,
                              const GpuRngSeed *seeds, const size_t *seg_cols, size_t nseg, GpuMatrix *out);
 int launch_scatter_i64(GpuMatrix *out, const int64_t *vals);  // int64 [poly][N] -> residues in every limb
+// The staged finish of the Gaussian lane samplers: `stage` holds the int64 samples [poly][N] of `out`, `launch_err` is
+// hipGetLastError() after the lane kernel.  Scatters, frees the stage, transforms and tags EVAL; a launch error is
+// reported under `what` after the stage is freed (the Gaussian matrix sites pass "err", the text their HIP_TRY(err) has
+// always put in front of the HIP error; p1 names its kernel).  transform = false: the samples stay coefficients, the tag
+// is the caller's.
+int finish_staged_i64(GpuMatrix *out, CtxBlock &stage, hipError_t launch_err, const char *what, bool transform = true);

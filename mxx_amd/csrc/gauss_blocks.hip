@@ -82,23 +82,15 @@ __global__ void __launch_bounds__(SAMPLER_THREADS) sample_gauss_blocks_kernel(in
     }
 }
 
-// The lane count is the segments entry's: the plain launcher's, cut down to a divisor of a polynomial's wave-chunks, so
-// that a wave's chunk stays inside one polynomial, i.e. inside one block; the grid is exact (no empty wave).  The caller
-// has checked that a polynomial holds a multiple of 64 pairs and that there are at most 2^32 polynomials.
+// The segments entry's plan: a wave's chunk stays inside one polynomial, i.e. inside one block, and the grid is exact (no
+// empty wave).  The caller has checked that a polynomial holds a multiple of 64 pairs and that there are at most 2^32
+// polynomials.
 void launch_gauss_blocks(GpuContext *ctx, int64_t *stage, size_t polys, const RngBlockTable &table, double sigma) {
     const size_t pairs_per_poly = static_cast<size_t>(ctx->N) >> GAUSS_GROUP_LOG, pairs = polys * pairs_per_poly;
-    uint32_t per_lane = sampler_per_lane(pairs, reinterpret_cast<const void *>(sample_gauss_blocks_kernel<KARNEY_SERVICES>), ctx->device,
-                                         ctx->env.sampler_per_lane);
-    while ((pairs_per_poly / SAMPLER_THREADS) % per_lane) --per_lane;
-    const unsigned blocks = static_cast<unsigned>(pairs / (static_cast<size_t>(SAMPLER_THREADS) * per_lane));
-    const KarneyDivisor div = karney_divisor(sigma);
-    // refills as the plain launcher sets them: every checkpoint with one group per lane, else every third and never forced
-#define LAUNCH_SGB(SV)                                                                                                          \
-    MXX_LAUNCH((sample_gauss_blocks_kernel<SV>), dim3(blocks), dim3(SAMPLER_THREADS), 0, ctx->stream, stage, polys, table, ctx->logN, \
-               sigma, div, per_lane,                                                                                             \
-               static_cast<uint32_t>(ctx->env.sampler_fill_every ? ctx->env.sampler_fill_every : (per_lane == 1 ? 1 : 3)),       \
-               per_lane == 1 ? 1 : 65)
-    if (per_lane == 1) LAUNCH_SGB(1);
-    else LAUNCH_SGB(KARNEY_SERVICES);
-#undef LAUNCH_SGB
+    const LanePlan plan = lane_plan(pairs, pairs_per_poly,
+                                    sampler_per_lane(pairs, reinterpret_cast<const void *>(sample_gauss_blocks_kernel<KARNEY_SERVICES>), ctx->device,
+                                                     ctx->env.sampler_per_lane),
+                                    true, ctx->env.sampler_fill_every, kCadenceGaussMatrix, true);
+    MXX_LAUNCH_LANES(plan, ctx->stream, (sample_gauss_blocks_kernel<1>), (sample_gauss_blocks_kernel<KARNEY_SERVICES>), stage, polys, table,
+                     ctx->logN, sigma, karney_divisor(sigma), plan.per_lane, plan.fill_every, plan.starve_limit);
 }

@@ -154,6 +154,21 @@ int launch_scatter_i64(GpuMatrix *out, const int64_t *vals) {
     return 0;
 }
 
+// common.h: the finish of the Gaussian lane samplers.  The stage goes back to the context's cache between the scatter and
+// the transform: what the transform allocates can reuse it, and the cache's high-water mark does not grow by the stage.
+int finish_staged_i64(GpuMatrix *out, CtxBlock &stage, hipError_t launch_err, const char *what, bool transform) {
+    GpuContext *ctx = out->ctx;
+    int rc = launch_err == hipSuccess ? launch_scatter_i64(out, static_cast<const int64_t *>(stage.ptr)) : 0;
+    ctx_free(ctx, stage.release());
+    if (launch_err != hipSuccess) return set_error(launch_err, what);
+    if (rc || !transform) return rc;
+    const size_t L = matrix_limbs(out);
+    rc = launch_ntt(ctx, words_ptr(out), matrix_polys(out) * L, static_cast<int>(L), false);
+    if (rc) return rc;
+    out->format = GPU_POLY_FORMAT_EVAL;
+    return 0;
+}
+
 // common.h: the coefficient-domain words of a matrix for an entry that reads them and leaves the matrix as it is
 int coeff_domain_source(const GpuMatrix *mat, CtxBlock &scratch, const void **src) {
     GpuContext *ctx = mat->ctx;

@@ -46,6 +46,7 @@
 #include <cstdlib>
 
 #include "detmath.h"
+#include "lane_plan.h"
 
 struct ChaChaRng {
     uint32_t state[16];
@@ -225,9 +226,7 @@ __device__ __forceinline__ void rng_fill_lane(ChaChaRng &rng) {
 // A pass happens when the checkpoint is `scheduled` and some lane is urgent, or when 16 lanes are starving; in a pass
 // every wanting lane computes its own block (960 instructions for up to 64 blocks).  A lane that runs dry between
 // passes waits (it only consumes draws it holds), so holding passes to every second or third checkpoint trades a few
-// idle lane-steps for whole passes: the kernels choose `scheduled` (G-sampler every third checkpoint - an element
-// starts with block 0's leftover draws -, p1 every second, the Gaussian matrix - a pair of coefficients per stream -
-// every third with starve_limit out of reach: sampling.hip).
+// idle lane-steps for whole passes: the launch plan sets `scheduled` and starve_limit per kernel family (lane_plan.h).
 // `make FILL_POLICY=1` builds the cooperative form instead (measured, not the default:
 // profiles/r03_notes.md): for passes with fewer than 40 wanting lanes the first 16 get a quad
 // each; lane c of the quad holds column c of the requester's state (its counter / nonce words fetched with
@@ -698,10 +697,6 @@ constexpr uint32_t kSamplerPerLaneCap = SAMPLER_PER_LANE_CAP;
 #ifndef GAUSS_GROUP_LOG
 #define GAUSS_GROUP_LOG 1
 #endif
-// threads per workgroup of the persistent-lane kernels (a lane's ring is 128 bytes of LDS: 8 KB per wave)
-#ifndef SAMPLER_THREADS
-#define SAMPLER_THREADS 64
-#endif
 // ---- column segments: several independent requests sampled by ONE launch -------------------------------------------
 // The GGH15 callers hand `preimage_batched_sharded` dozens of small requests against one trapdoor
 // (src/sampler/trapdoor/gpu.rs:371-397, src/lookup/ggh15/pubkey_gpu.rs:615-971); at n = 256 a request of four columns
@@ -822,3 +817,23 @@ static inline uint32_t sampler_per_lane(size_t total, const void *kernel, int de
     return static_cast<uint32_t>(per < 1 ? 1 : (per > kSamplerPerLaneCap ? kSamplerPerLaneCap : per));
 }
 
+// The launch of a lane kernel from its plan (lane_plan.h): one-wave workgroups, plan.blocks of them, and the choice among
+// the instances the caller names - K1* with one service point per superstep for plan.single, KS* with KARNEY_SERVICES;
+// *U the UNI form for plan.uni, *N the other.  The trace records a launch under MXX_LAUNCH's kernel argument as written,
+// so the instances stand at the call as literals; they are named there in the order the device code is emitted in.
+#define MXX_LAUNCH_LANES_ONE(plan, strm, K, ...) MXX_LAUNCH(K, dim3((plan).blocks), dim3(SAMPLER_THREADS), 0, strm, __VA_ARGS__)
+#define MXX_LAUNCH_LANES(plan, strm, K1, KS, ...)                            \
+    do {                                                                     \
+        if ((plan).single) MXX_LAUNCH_LANES_ONE(plan, strm, K1, __VA_ARGS__); \
+        else MXX_LAUNCH_LANES_ONE(plan, strm, KS, __VA_ARGS__);              \
+    } while (0)
+#define MXX_LAUNCH_LANES_UNI(plan, strm, K1U, K1N, KSU, KSN, ...)                  \
+    do {                                                                           \
+        if ((plan).single) {                                                       \
+            if ((plan).uni) MXX_LAUNCH_LANES_ONE(plan, strm, K1U, __VA_ARGS__);     \
+            else MXX_LAUNCH_LANES_ONE(plan, strm, K1N, __VA_ARGS__);               \
+        } else {                                                                   \
+            if ((plan).uni) MXX_LAUNCH_LANES_ONE(plan, strm, KSU, __VA_ARGS__);     \
+            else MXX_LAUNCH_LANES_ONE(plan, strm, KSN, __VA_ARGS__);               \
+        }                                                                          \
+    } while (0)

@@ -106,21 +106,13 @@ __global__ void __launch_bounds__(256) sample_uniform_kernel(W *__restrict__ out
     store_group<W, 1>(out + vec * N + static_cast<size_t>(g) * 8u, r, count);
 }
 
-// bit / ternary: the draw is shared by all limbs
+// bit / ternary: the draw is shared by all limbs.  One thread's work for group g of polynomial p, whose draws are block g of
+// stream (stream0, 0) under `key`; the plain and the block kernel differ in how they find that key and stream alone
 template <typename W>
-__global__ void __launch_bounds__(256) sample_small_kernel(W *__restrict__ out, const LimbConst *__restrict__ limbs,
-                                                           const ChaChaKey *__restrict__ keys, size_t polys, size_t local_ncol,
-                                                           size_t full_ncol, size_t col_offset, uint32_t L, uint32_t N, uint32_t groups,
-                                                           int dist) {
-    const size_t idx = item_index();
-    if (idx >= polys * groups) return;
-    const size_t p = idx / groups;
-    const uint32_t g = static_cast<uint32_t>(idx - p * groups);
-    const size_t row = p / local_ncol, lcol = p - row * local_ncol;
-    const uint64_t gpoly = row * full_ncol + col_offset + lcol;
-    const ChaChaKey key = load_key(keys, 0);
+__device__ __forceinline__ void sample_small_group(W *__restrict__ out, const LimbConst *__restrict__ limbs, const ChaChaKey &key,
+                                                   uint64_t stream0, size_t p, uint32_t g, uint32_t L, uint32_t N, int dist) {
     uint64_t w[8];
-    chacha_block_words(key, gpoly + 1, 0, g, w);
+    chacha_block_words(key, stream0, 0, g, w);
     const uint32_t count = min(8u, N - g * 8u);
     int32_t z[8];
 #pragma unroll
@@ -139,6 +131,21 @@ __global__ void __launch_bounds__(256) sample_small_kernel(W *__restrict__ out, 
         for (int j = 0; j < 8; ++j) r[j] = z[j] < 0 ? q - 1 : static_cast<W>(z[j]);
         store_group<W, 1>(out + (p * L + l) * N + static_cast<size_t>(g) * 8u, r, count);
     }
+}
+
+template <typename W>
+__global__ void __launch_bounds__(256) sample_small_kernel(W *__restrict__ out, const LimbConst *__restrict__ limbs,
+                                                           const ChaChaKey *__restrict__ keys, size_t polys, size_t local_ncol,
+                                                           size_t full_ncol, size_t col_offset, uint32_t L, uint32_t N, uint32_t groups,
+                                                           int dist) {
+    const size_t idx = item_index();
+    if (idx >= polys * groups) return;
+    const size_t p = idx / groups;
+    const uint32_t g = static_cast<uint32_t>(idx - p * groups);
+    const size_t row = p / local_ncol, lcol = p - row * local_ncol;
+    const uint64_t gpoly = row * full_ncol + col_offset + lcol;
+    const ChaChaKey key = load_key(keys, 0);
+    sample_small_group<W>(out, limbs, key, gpoly + 1, p, g, L, N, dist);
 }
 
 // discrete Gaussian: persistent lanes (rng.h).  An element is a PAIR of consecutive coefficients of one polynomial drawn
@@ -424,39 +431,22 @@ int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t 
         return launch_ntt(ctx, words_ptr(out), polys * L, static_cast<int>(L), false);
     }
     if (dist == GPU_MATRIX_DIST_GAUSS) {
-        // enough lanes to fill the chip first, then up to 16 coefficients per lane
         if (polys >> 32) return set_error("gpu_matrix_sample_distribution: too many polynomials");
-        const size_t groups = total >> (ctx->logN < GAUSS_GROUP_LOG ? ctx->logN : GAUSS_GROUP_LOG);
-        const uint32_t per_lane = sampler_per_lane(groups, reinterpret_cast<const void *>(sample_gauss_kernel<KARNEY_SERVICES>), ctx->device, ctx->env.sampler_per_lane);
-        const unsigned blocks = static_cast<unsigned>((groups + SAMPLER_THREADS * per_lane - 1) / (SAMPLER_THREADS * per_lane));
+        const uint32_t glog = ctx->logN < GAUSS_GROUP_LOG ? ctx->logN : GAUSS_GROUP_LOG;
+        const size_t groups = total >> glog;
+        const LanePlan plan = lane_plan(groups, static_cast<size_t>(ctx->N) >> glog,
+                                        sampler_per_lane(groups, reinterpret_cast<const void *>(sample_gauss_kernel<KARNEY_SERVICES>), ctx->device, ctx->env.sampler_per_lane),
+                                        false, ctx->env.sampler_fill_every, kCadenceGaussMatrix, true);
         const KarneyDivisor div = karney_divisor(sigma);
         const ChaChaKey key = chacha_subkey(seed, 0, kTagGauss);
-        void *stage = nullptr;
-        if (ctx_alloc(ctx, total * sizeof(int64_t), &stage)) return 1;
+        CtxBlock stage(ctx);
+        if (stage.alloc(total * sizeof(int64_t))) return 1;
         MXX_TRACE_BYTES(static_cast<double>(total) * sizeof(int64_t));  // no input: the int64 samples written once
-        // one group per lane at most: the call lasts as long as its unluckiest lane's chain, which must not wait for
-        // keystream - refills at every checkpoint, one service point per superstep; otherwise every third checkpoint and
-        // never forced (64 lanes cannot reach 65)
-        const size_t groups_per_poly = static_cast<size_t>(ctx->N) >> (ctx->logN < GAUSS_GROUP_LOG ? ctx->logN : GAUSS_GROUP_LOG);
-        const bool uni = groups_per_poly % (static_cast<size_t>(SAMPLER_THREADS) * per_lane) == 0;
-#define LAUNCH_SG(SV, UNI)                                                                                                     \
-    MXX_LAUNCH((sample_gauss_kernel<SV, UNI>), dim3(blocks), dim3(SAMPLER_THREADS), 0, ctx->stream, static_cast<int64_t *>(stage), polys, \
-               static_cast<uint32_t>(out->cols), full_ncol, col_offset, ctx->logN, sigma, div, key, per_lane,                   \
-               static_cast<uint32_t>(ctx->env.sampler_fill_every ? ctx->env.sampler_fill_every : (per_lane == 1 ? 1 : 3)),      \
-               per_lane == 1 ? 1 : 65, NoSegments{})
-        if (per_lane == 1) {
-            if (uni) LAUNCH_SG(1, true);
-            else LAUNCH_SG(1, false);
-        } else {
-            if (uni) LAUNCH_SG(KARNEY_SERVICES, true);
-            else LAUNCH_SG(KARNEY_SERVICES, false);
-        }
-#undef LAUNCH_SG
-        const hipError_t err = hipGetLastError();
-        const int rc = err == hipSuccess ? launch_scatter_i64(out, static_cast<const int64_t *>(stage)) : 0;
-        ctx_free(ctx, stage);
-        HIP_TRY(err);
-        if (rc) return rc;
+        MXX_LAUNCH_LANES_UNI(plan, ctx->stream, (sample_gauss_kernel<1, true>), (sample_gauss_kernel<1, false>),
+                             (sample_gauss_kernel<KARNEY_SERVICES, true>), (sample_gauss_kernel<KARNEY_SERVICES, false>),
+                             static_cast<int64_t *>(stage.ptr), polys, static_cast<uint32_t>(out->cols), full_ncol, col_offset, ctx->logN,
+                             sigma, div, key, plan.per_lane, plan.fill_every, plan.starve_limit, NoSegments{});
+        return finish_staged_i64(out, stage, hipGetLastError(), "err", !keep_coeff);
     } else {
         const bool uniform = dist == GPU_MATRIX_DIST_UNIFORM;
         const uint32_t groups = (N + 7) / 8;
@@ -517,30 +507,17 @@ extern "C" int gpupoly_matrix_sample_distribution_segments(GpuMatrix *out, int d
     if (ctx_activate(ctx)) return 1;
     const size_t total = polys * static_cast<size_t>(ctx->N);
     const size_t groups = total >> glog;
-    const uint32_t L = static_cast<uint32_t>(matrix_limbs(out));
-    // the plain launcher's lane count, cut down to a divisor of a polynomial's groups: a wave's chunk stays inside one
-    // polynomial, i.e. inside one segment
-    uint32_t per_lane = sampler_per_lane(groups, reinterpret_cast<const void *>(sample_gauss_kernel<KARNEY_SERVICES, true, true>), ctx->device, ctx->env.sampler_per_lane);
-    while ((groups_per_poly / SAMPLER_THREADS) % per_lane) --per_lane;
-    const unsigned blocks = static_cast<unsigned>((groups + SAMPLER_THREADS * per_lane - 1) / (SAMPLER_THREADS * per_lane));
+    const LanePlan plan = lane_plan(groups, groups_per_poly,
+                                    sampler_per_lane(groups, reinterpret_cast<const void *>(sample_gauss_kernel<KARNEY_SERVICES, true, true>), ctx->device, ctx->env.sampler_per_lane),
+                                    true, ctx->env.sampler_fill_every, kCadenceGaussMatrix, true);
     const KarneyDivisor div = karney_divisor(sigma);
-    void *stage = nullptr;
-    if (ctx_alloc(ctx, total * sizeof(int64_t), &stage)) return 1;
+    CtxBlock stage(ctx);
+    if (stage.alloc(total * sizeof(int64_t))) return 1;
     MXX_TRACE_BYTES(static_cast<double>(total) * sizeof(int64_t));
-#define LAUNCH_SGS(SV)                                                                                                         \
-    MXX_LAUNCH((sample_gauss_kernel<SV, true, true>), dim3(blocks), dim3(SAMPLER_THREADS), 0, ctx->stream, static_cast<int64_t *>(stage), polys, \
-               static_cast<uint32_t>(out->cols), out->cols, size_t(0), ctx->logN, sigma, div, ChaChaKey{}, per_lane,            \
-               static_cast<uint32_t>(ctx->env.sampler_fill_every ? ctx->env.sampler_fill_every : (per_lane == 1 ? 1 : 3)),      \
-               per_lane == 1 ? 1 : 65, segs)
-    if (per_lane == 1) LAUNCH_SGS(1);
-    else LAUNCH_SGS(KARNEY_SERVICES);
-#undef LAUNCH_SGS
-    const hipError_t err = hipGetLastError();
-    const int rc = err == hipSuccess ? launch_scatter_i64(out, static_cast<const int64_t *>(stage)) : 0;
-    ctx_free(ctx, stage);
-    HIP_TRY(err);
-    if (rc) return rc;
-    return launch_ntt(ctx, words_ptr(out), polys * L, static_cast<int>(L), false);
+    MXX_LAUNCH_LANES(plan, ctx->stream, (sample_gauss_kernel<1, true, true>), (sample_gauss_kernel<KARNEY_SERVICES, true, true>),
+                     static_cast<int64_t *>(stage.ptr), polys, static_cast<uint32_t>(out->cols), out->cols, size_t(0), ctx->logN, sigma, div,
+                     ChaChaKey{}, plan.per_lane, plan.fill_every, plan.starve_limit, segs);
+    return finish_staged_i64(out, stage, hipGetLastError(), "err");
     ABI_GUARD_END
 }
 
@@ -617,26 +594,7 @@ __global__ void __launch_bounds__(256) sample_small_blocks_kernel(W *__restrict_
     const uint32_t g = static_cast<uint32_t>(idx - p * groups);
     const RngBlockRef ref = refs[p - p_first];
     const ChaChaKey key = load_key(table.keys + ref.blk, 0);
-    uint64_t w[8];
-    chacha_block_words(key, ref.local + 1, 0, g, w);
-    const uint32_t count = min(8u, N - g * 8u);
-    int32_t z[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        if (dist == GPU_MATRIX_DIST_BIT) {
-            z[j] = static_cast<int32_t>(w[j] & 1ull);
-        } else {
-            const uint32_t pick = static_cast<uint32_t>(w[j] % 3ull);
-            z[j] = pick == 0 ? 0 : (pick == 1 ? 1 : -1);
-        }
-    }
-    for (uint32_t l = 0; l < L; ++l) {
-        const W q = static_cast<W>(limbs[l].q);
-        W r[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = z[j] < 0 ? q - 1 : static_cast<W>(z[j]);
-        store_group<W, 1>(out + (p * L + l) * N + static_cast<size_t>(g) * 8u, r, count);
-    }
+    sample_small_group<W>(out, limbs, key, ref.local + 1, p, g, L, N, dist);
 }
 
 // Both block entries: the argument checks in `entry`'s name, then the table, the launches and the finish.  The seeds of
@@ -748,16 +706,11 @@ int sample_blocks_impl(const char *entry, bool hashed, GpuMatrix *out, int dist_
     if (gauss) {
         // the keys are sample_impl's, chacha_subkey(seed, 0, kTagGauss), one per block (gauss_blocks.hip has the kernel)
         const size_t total = polys * static_cast<size_t>(ctx->N);
-        void *stage = nullptr;
-        if (ctx_alloc(ctx, total * sizeof(int64_t), &stage)) return 1;
+        CtxBlock stage(ctx);
+        if (stage.alloc(total * sizeof(int64_t))) return 1;
         MXX_TRACE_BYTES(static_cast<double>(total) * sizeof(int64_t));  // no input to speak of: the int64 samples written once
-        launch_gauss_blocks(ctx, static_cast<int64_t *>(stage), polys, table, *sigma);
-        const hipError_t err = hipGetLastError();
-        const int rc = err == hipSuccess ? launch_scatter_i64(out, static_cast<const int64_t *>(stage)) : 0;
-        ctx_free(ctx, stage);
-        HIP_TRY(err);
-        if (rc) return rc;
-        return launch_ntt(ctx, words, polys * L, static_cast<int>(L), false);  // a Gaussian sample is never stored packed
+        launch_gauss_blocks(ctx, static_cast<int64_t *>(stage.ptr), polys, table, *sigma);
+        return finish_staged_i64(out, stage, hipGetLastError(), "err");  // a Gaussian sample is never stored packed
     }
     const size_t threads = polys * per_block * groups;
     const dim3 blocks = item_grid(threads, 256);

@@ -457,17 +457,14 @@ static int launch_gauss_samp_lanes(GpuContext *ctx, W *out, const W *src, size_t
                                    const RngSegments *segs = nullptr) {
     if ((total >> ctx->logN) >> 32 || k >> 32) return set_error("gpu_matrix_gauss_samp_gq_arb_base: matrix too large");
     // [L] towers | [8][total] words between passes 1 and 2 | [total][dpt] digits
-    void *towers = nullptr, *a_buf = nullptr, *stage = nullptr;
-    if (ctx_alloc(ctx, static_cast<size_t>(L) * sizeof(GqTower), &towers) ||
-        ctx_alloc(ctx, total * 8 * sizeof(uint64_t), &a_buf) || ctx_alloc(ctx, total * dpt * sizeof(int64_t), &stage)) {
-        ctx_free(ctx, towers);
-        ctx_free(ctx, a_buf);
+    CtxBlock stage(ctx), a_buf(ctx), towers(ctx);  // released towers first, as allocated
+    if (towers.alloc(static_cast<size_t>(L) * sizeof(GqTower)) || a_buf.alloc(total * 8 * sizeof(uint64_t)) ||
+        stage.alloc(total * dpt * sizeof(int64_t)))
         return 1;
-    }
-    double *a_words = static_cast<double *>(a_buf);
-    uint64_t *left_words = static_cast<uint64_t *>(a_buf) + total * dpt;
+    double *a_words = static_cast<double *>(a_buf.ptr);
+    uint64_t *left_words = static_cast<uint64_t *>(a_buf.ptr) + total * dpt;
     const ChaChaKey key = chacha_subkey(seed, 0, kTagGadget);
-    MXX_LAUNCH(gq_tower_kernel, dim3(1), dim3(64), 0, ctx->stream, static_cast<GqTower *>(towers), ctx->d_limbs,
+    MXX_LAUNCH(gq_tower_kernel, dim3(1), dim3(64), 0, ctx->stream, static_cast<GqTower *>(towers.ptr), ctx->d_limbs,
                        L, dpt, base_bits, c);
     // per element: the residue read; dpt centres + the 8 - 2 dpt unused keystream words handed to pass 2
     MXX_TRACE_BYTES(static_cast<double>(total) * (sizeof(W) + 8.0 * (8 - dpt)));
@@ -479,47 +476,31 @@ static int launch_gauss_samp_lanes(GpuContext *ctx, W *out, const W *src, size_t
         MXX_LAUNCH((gauss_samp_prep_kernel<W, MAXD>), item_grid(total, 256), dim3(256), 0,
                            ctx->stream, a_words, left_words, src, ctx->d_limbs, key, total, L,
                            ctx->logN, dpt, base_bits, c, gq_pert_consts(dpt, base_bits), src_cols, NoSegments{});
-    uint32_t per_lane =
-        sampler_per_lane(total, reinterpret_cast<const void *>(gauss_samp_lanes_kernel<W, MAXD, KARNEY_SERVICES>), ctx->device, ctx->env.sampler_per_lane);
-    if (segs)  // a divisor of n / 64: every wave's chunk inside one (polynomial, tower) vector, i.e. inside one segment
-        while ((static_cast<size_t>(ctx->N) / SAMPLER_THREADS) % per_lane) --per_lane;
-    const unsigned blocks = static_cast<unsigned>((total + SAMPLER_THREADS * per_lane - 1) / (SAMPLER_THREADS * per_lane));
+    // a span is one (polynomial, tower) vector; with segments every wave's chunk stays inside one, i.e. inside one segment
+    const LanePlan plan = lane_plan(total, static_cast<size_t>(ctx->N),
+                                    sampler_per_lane(total, reinterpret_cast<const void *>(gauss_samp_lanes_kernel<W, MAXD, KARNEY_SERVICES>), ctx->device, ctx->env.sampler_per_lane),
+                                    segs != nullptr, ctx->env.sampler_fill_every, kCadenceGadget, !ctx->env.gsamp_no_uni);
     const double sigma = c / (static_cast<double>(1ull << base_bits) + 1.0);
     MXX_TRACE_BYTES(static_cast<double>(total) * (8.0 * (8 - dpt) + 8.0 * dpt));  // pass 1's words read, dpt int64 digits written
-    // a chunk of 64 * per_lane consecutive elements inside one (polynomial, tower) vector: the kernel's UNI form
-    const bool uni = (static_cast<size_t>(ctx->N) % (static_cast<size_t>(SAMPLER_THREADS) * per_lane)) == 0 && !ctx->env.gsamp_no_uni;
-#define LAUNCH_GL(SV, UNI)                                                                                                  \
-    MXX_LAUNCH((gauss_samp_lanes_kernel<W, MAXD, SV, UNI>), dim3(blocks), dim3(SAMPLER_THREADS), 0, ctx->stream,            \
-               static_cast<int64_t *>(stage), ctx->d_limbs, key, static_cast<const GqTower *>(towers), a_words, left_words, \
-               total, src_cols, L, ctx->logN, dpt, base_bits, c, karney_divisor(sigma), per_lane,                           \
-               static_cast<uint32_t>(ctx->env.sampler_fill_every ? ctx->env.sampler_fill_every : 3), NoSegments{})
-#define LAUNCH_GLS(SV)                                                                                                      \
-    MXX_LAUNCH((gauss_samp_lanes_kernel<W, MAXD, SV, true, true>), dim3(blocks), dim3(SAMPLER_THREADS), 0, ctx->stream,     \
-               static_cast<int64_t *>(stage), ctx->d_limbs, key, static_cast<const GqTower *>(towers), a_words, left_words, \
-               total, src_cols, L, ctx->logN, dpt, base_bits, c, karney_divisor(sigma), per_lane,                           \
-               static_cast<uint32_t>(ctx->env.sampler_fill_every ? ctx->env.sampler_fill_every : 3), *segs)
-    if (segs) {
-        if (per_lane == 1) LAUNCH_GLS(1);
-        else LAUNCH_GLS(KARNEY_SERVICES);
-    } else if (per_lane == 1) {
-        if (uni) LAUNCH_GL(1, true);
-        else LAUNCH_GL(1, false);
-    } else {
-        if (uni) LAUNCH_GL(KARNEY_SERVICES, true);
-        else LAUNCH_GL(KARNEY_SERVICES, false);
-    }
-#undef LAUNCH_GLS
-#undef LAUNCH_GL
+    int64_t *digits = static_cast<int64_t *>(stage.ptr);
+    const GqTower *d_towers = static_cast<const GqTower *>(towers.ptr);
+    const KarneyDivisor div = karney_divisor(sigma);
+    if (segs)
+        MXX_LAUNCH_LANES(plan, ctx->stream, (gauss_samp_lanes_kernel<W, MAXD, 1, true, true>),
+                         (gauss_samp_lanes_kernel<W, MAXD, KARNEY_SERVICES, true, true>), digits, ctx->d_limbs, key, d_towers, a_words,
+                         left_words, total, src_cols, L, ctx->logN, dpt, base_bits, c, div, plan.per_lane, plan.fill_every, *segs);
+    else
+        MXX_LAUNCH_LANES_UNI(plan, ctx->stream, (gauss_samp_lanes_kernel<W, MAXD, 1, true>), (gauss_samp_lanes_kernel<W, MAXD, 1, false>),
+                             (gauss_samp_lanes_kernel<W, MAXD, KARNEY_SERVICES, true>), (gauss_samp_lanes_kernel<W, MAXD, KARNEY_SERVICES, false>),
+                             digits, ctx->d_limbs, key, d_towers, a_words, left_words, total, src_cols, L, ctx->logN, dpt, base_bits, c, div,
+                             plan.per_lane, plan.fill_every, NoSegments{});
     // the int64 digits and the residue read; every digit written as a residue of every limb (the call's output: 655 MB at M3A)
     MXX_TRACE_BYTES(static_cast<double>(total) * (8.0 * dpt + sizeof(W) + static_cast<double>(dpt) * L * sizeof(W)));
     MXX_LAUNCH(gauss_samp_expand_kernel<W>, item_grid(total, 256), dim3(256), 0,
-                       ctx->stream, out, static_cast<const int64_t *>(stage), src, ctx->d_limbs, total, src_cols, L, ctx->logN,
+                       ctx->stream, out, digits, src, ctx->d_limbs, total, src_cols, L, ctx->logN,
                        dpt, static_cast<uint32_t>(k), base_bits);
     const hipError_t err = hipGetLastError();
-    ctx_free(ctx, towers);
-    ctx_free(ctx, a_buf);
-    ctx_free(ctx, stage);
-    HIP_TRY(err);
+    HIP_TRY(err);  // reported under this name
     return 0;
 }
 
@@ -731,11 +712,10 @@ __global__ void p1_divisor_kernel(KarneyDivisor *__restrict__ div, const double 
 }
 
 // persistent-lane form for m <= 8 (rng.h): element = (column, coefficient), m dependent Karney
-// integers each (rows m-1 .. 0); integers go to the int64 staging array [row][col][N].  Keystream refills every
-// second checkpoint (fill_every; M3A: 0.47 -> 0.445 ms, every third 0.447)
-// SEG: the columns are independently seeded segments (rng.h, RngSegments).  The launcher picks a lane count that keeps
-// every wave's chunk inside one column (64 * per_lane divides n), so the segment's sub-key and the column's index inside
-// its segment - the stream's first word - are per-wave scalars.
+// integers each (rows m-1 .. 0); integers go to the int64 staging array [row][col][N].
+// SEG: the columns are independently seeded segments (rng.h, RngSegments).  The plan keeps every wave's chunk inside one
+// column, so the segment's sub-key and the column's index inside its segment - the stream's first word - are per-wave
+// scalars.
 // KEYED (with SEG): every segment also names its own covariance cache (gpupoly_trapdoor_preimage_keyed: the requests of
 // one launch belong to several trapdoors).  The three cache arrays of segment j come from a table in device memory
 // (P1KeyEntry, common.h) - one wave-uniform 24-byte read per wave - and replace the kernel's three pointer arguments,
@@ -1028,44 +1008,33 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
     // MXX_HIP_P1=simple keeps the one-thread-per-element kernel for every m (A/B runs, tests): the same bytes from either.
     // At 4 < m <= 8 the lane kernel is the default because it measured 2.1 - 2.8x faster
     if (m <= 8 && !ctx->env.p1_simple) {
-        void *stage = nullptr;
-        if (ctx_alloc(ctx, total * m * sizeof(int64_t), &stage)) return 1;
+        CtxBlock stage(ctx);
+        if (stage.alloc(total * m * sizeof(int64_t))) return 1;
         const ChaChaKey key = chacha_subkey(seed, 0, kTagP1);
         // per (column, coefficient): m limb-0 residues of tp2, m standard deviations + divisors and m^2 update coefficients of
         // the cache (the cache is per coefficient: re-read per column from L2 / the Infinity Cache), m int64 samples written
         MXX_TRACE_BYTES(static_cast<double>(total) * m * (ctx->word_bytes + 8.0) +
                         static_cast<double>(N) * m * (8.0 + sizeof(KarneyDivisor) + 8.0 * m));
-#define LAUNCH_P1K(WT, MAXM, SV, SEG, SEGARG)                                                                     \
-    MXX_LAUNCH((p1_sample_lanes_kernel<WT, MAXM, SV, SEG>), dim3(lblocks), dim3(SAMPLER_THREADS), 0, ctx->stream, \
-               static_cast<int64_t *>(stage), static_cast<const WT *>(words_ptr(tp2)), cache->sqrt_var,                \
-               cache->update_coeff, static_cast<const KarneyDivisor *>(cache->karney_div), (uint32_t)m,           \
-               (uint32_t)cols, L, ctx->logN, ctx->moduli[0], c_scale, key, total, per_lane,                       \
-               static_cast<uint32_t>(ctx->env.sampler_fill_every ? ctx->env.sampler_fill_every : 2), SEGARG)
-#define LAUNCH_P1KEYED(WT, MAXM, SV) /* the cache arrays come from the table: the three pointer arguments are not read */ \
-    MXX_LAUNCH((p1_sample_lanes_kernel<WT, MAXM, SV, true, true>), dim3(lblocks), dim3(SAMPLER_THREADS), 0, ctx->stream, \
-               static_cast<int64_t *>(stage), static_cast<const WT *>(words_ptr(tp2)), static_cast<const double *>(nullptr), \
-               static_cast<const double *>(nullptr), static_cast<const KarneyDivisor *>(nullptr), (uint32_t)m,   \
-               (uint32_t)cols, L, ctx->logN, ctx->moduli[0], c_scale, key, total, per_lane,                       \
-               static_cast<uint32_t>(ctx->env.sampler_fill_every ? ctx->env.sampler_fill_every : 2), keyed_segs)
-#define LAUNCH_P1L(WT, MAXM)                                                                                      \
-    do {                                                                                                          \
-        uint32_t per_lane =                                                                                       \
-            sampler_per_lane(total, reinterpret_cast<const void *>(p1_sample_lanes_kernel<WT, MAXM, KARNEY_SERVICES>), ctx->device, ctx->env.sampler_per_lane); \
-        if (segs) /* a divisor of n / 64: every wave's chunk inside one column, i.e. inside one segment */        \
-            while ((static_cast<size_t>(N) / SAMPLER_THREADS) % per_lane) --per_lane;                             \
-        const unsigned lblocks = static_cast<unsigned>((total + SAMPLER_THREADS * per_lane - 1) / (SAMPLER_THREADS * per_lane)); \
-        if (segs && d_keys) {                                                                                     \
-            const P1KeyedSegments keyed_segs{*segs, d_keys};                                                      \
-            if (per_lane == 1) LAUNCH_P1KEYED(WT, MAXM, 1);                                                       \
-            else LAUNCH_P1KEYED(WT, MAXM, KARNEY_SERVICES);                                                       \
-        } else if (segs) {                                                                                        \
-            if (per_lane == 1) LAUNCH_P1K(WT, MAXM, 1, true, *segs);                                              \
-            else LAUNCH_P1K(WT, MAXM, KARNEY_SERVICES, true, *segs);                                              \
-        } else if (per_lane == 1) {                                                                               \
-            LAUNCH_P1K(WT, MAXM, 1, false, NoSegments{});                                                         \
-        } else {                                                                                                  \
-            LAUNCH_P1K(WT, MAXM, KARNEY_SERVICES, false, NoSegments{});                                           \
-        }                                                                                                         \
+        // The keyed form reads the cache arrays from its table: the three pointer arguments are null there.  A span is one
+        // column; with segments every wave's chunk stays inside one, i.e. inside one segment.  The trace names a launch by its
+        // kernel argument as written (rng.h, MXX_LAUNCH_LANES), word type and row bound included: the six (word, rows) choices
+        // are spelled out through a macro, not a function template over them, whose labels would read "WT, MAXM"
+        const bool keyed = segs && d_keys;
+        const double *sqrt_var = keyed ? nullptr : cache->sqrt_var, *update = keyed ? nullptr : cache->update_coeff;
+        const KarneyDivisor *kdiv = keyed ? nullptr : static_cast<const KarneyDivisor *>(cache->karney_div);
+#define P1_LANES(WT, MAXM, SEGARG, ...)                                                                                            \
+    MXX_LAUNCH_LANES(plan, ctx->stream, (p1_sample_lanes_kernel<WT, MAXM, 1, __VA_ARGS__>),                                        \
+                     (p1_sample_lanes_kernel<WT, MAXM, KARNEY_SERVICES, __VA_ARGS__>), static_cast<int64_t *>(stage.ptr),          \
+                     static_cast<const WT *>(words_ptr(tp2)), sqrt_var, update, kdiv, (uint32_t)m, (uint32_t)cols, L, ctx->logN,   \
+                     ctx->moduli[0], c_scale, key, total, plan.per_lane, plan.fill_every, SEGARG)
+#define LAUNCH_P1L(WT, MAXM)                                                                                                       \
+    do {                                                                                                                           \
+        const LanePlan plan = lane_plan(total, N,                                                                                  \
+                                        sampler_per_lane(total, reinterpret_cast<const void *>(p1_sample_lanes_kernel<WT, MAXM, KARNEY_SERVICES>), ctx->device, ctx->env.sampler_per_lane), \
+                                        segs != nullptr, ctx->env.sampler_fill_every, kCadenceP1, false);                          \
+        if (keyed) P1_LANES(WT, MAXM, (P1KeyedSegments{*segs, d_keys}), true, true);                                               \
+        else if (segs) P1_LANES(WT, MAXM, *segs, true);                                                                            \
+        else P1_LANES(WT, MAXM, NoSegments{}, false);                                                                              \
     } while (0)
         if (ctx->wide) {
             if (m <= 2) LAUNCH_P1L(uint64_t, 2);
@@ -1077,17 +1046,8 @@ static int sample_p1_impl(const GpuP1CovarianceCache *cache, const GpuMatrix *tp
             else LAUNCH_P1L(uint32_t, 8);
         }
 #undef LAUNCH_P1L
-#undef LAUNCH_P1KEYED
-#undef LAUNCH_P1K
-        const hipError_t le = hipGetLastError();
-        int lrc = le == hipSuccess ? launch_scatter_i64(out, static_cast<const int64_t *>(stage)) : 0;
-        ctx_free(ctx, stage);
-        if (le != hipSuccess) return set_error(le, "p1_sample_lanes_kernel");
-        if (lrc) return lrc;
-        lrc = launch_ntt(ctx, words_ptr(out), matrix_polys(out) * L, static_cast<int>(L), false);
-        if (lrc) return lrc;
-        out->format = GPU_POLY_FORMAT_EVAL;
-        return 0;
+#undef P1_LANES
+        return finish_staged_i64(out, stage, hipGetLastError(), "p1_sample_lanes_kernel");
     }
     const dim3 blocks = item_grid(total, 128);
     void *mean_ws = nullptr;

@@ -11,7 +11,7 @@ Target legs, 16 gates, d = 2, a four-column chunk:
   per_gate  the reference's function restated, gate by gate (build_gate_stageN_target_chunk)
   batched   gate_stageN_targets
 hipEvent timing on the context's stream (gpupoly_timer_start / _stop) around each leg - host stalls of the loop legs
-included: it is what the caller waits for -, every shape warmed up, REPS alternated iterations, median and min..max,
+included: it is what the caller waits for -, every shape warmed up, REPS alternated iterations, median, min..max and 90th percentile,
 launches per leg from gpupoly_launch_count, results compared with gpu_matrix_equal before timing.
 Shapes:
   (a) 64 blocks of 2 x 4 at n = 2^8, 12 limbs of 51 bits, sigma 4.578
@@ -48,7 +48,8 @@ def say(text):
 
 def stats(ms):
     ms = sorted(ms)
-    return {"median_ms": round(ms[len(ms) // 2], 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4)}
+    p90 = ms[min(len(ms) - 1, max(0, round(0.9 * (len(ms) - 1))))]  # nearest rank, as time_lut_targets.py takes it
+    return {"median_ms": round(ms[len(ms) // 2], 4), "min_ms": round(ms[0], 4), "max_ms": round(ms[-1], 4), "p90_ms": round(p90, 4)}
 
 
 def seed(tag):
@@ -80,7 +81,7 @@ def measure(name, ctx, legs, check, compare):
     say(name)
     for k in legs:
         s = out[k]
-        say(f"    {k:10s} {s['median_ms']:10.4f} ms [{s['min_ms']:.4f}..{s['max_ms']:.4f}] {s['launches']:5d} launches")
+        say(f"    {k:10s} {s['median_ms']:10.4f} ms [{s['min_ms']:.4f}..{s['max_ms']:.4f}] p90 {s['p90_ms']:.4f} {s['launches']:5d} launches")
     for new, old in compare:
         ratio = out[old]["median_ms"] / out[new]["median_ms"]
         inside = out[new]["median_ms"] <= out[old]["max_ms"]

@@ -67,8 +67,9 @@ def worker(reps, trace):
                     before(nm)
                 t, launches[nm] = sample(ctx, fn)
                 ms[nm].append(t)
-        return {nm: {"median_ms": statistics.median(ms[nm]), "min_ms": min(ms[nm]), "max_ms": max(ms[nm]), "launches": launches[nm]}
-                for nm, _ in legs}
+        p90 = lambda xs: sorted(xs)[min(len(xs) - 1, max(0, round(0.9 * (len(xs) - 1))))]  # noqa: E731 - nearest rank, as time_lut_targets.py
+        return {nm: {"median_ms": statistics.median(ms[nm]), "min_ms": min(ms[nm]), "max_ms": max(ms[nm]), "p90_ms": p90(ms[nm]),
+                     "launches": launches[nm]} for nm, _ in legs}
 
     # ---- (a) the plain p1 entry
     def p1_mode(nm):
@@ -100,7 +101,7 @@ def worker(reps, trace):
             r = alternate(p.ctx(), legs, before=p1_mode)
             p1_mode("default")
             for v in r.values():  # per call
-                for key in ("median_ms", "min_ms", "max_ms"):
+                for key in ("median_ms", "min_ms", "max_ms", "p90_ms"):
                     v[key] /= calls
                 v["launches"] //= calls
             res[f"a/{name}/m{2 * d}"] = r

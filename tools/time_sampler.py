@@ -15,14 +15,16 @@ def seed(tag):
     return mx.GpuRngSeed.from_bytes(bytes([(tag * 37 + i * 11 + 5) & 0xFF for i in range(32)]))
 
 
-def timed(ctx, fn, reps=5):
+def timed(ctx, fn, reps=int(os.environ.get("REPS", "5"))):
+    """(minimum, median, 90th percentile - nearest rank, as time_lut_targets.py takes it) of `reps` timed calls after one warm-up"""
     fn()
     out = []
     for r in range(reps):
         ctx.timer_start()
         fn()
         out.append(ctx.timer_stop())
-    return min(out), sorted(out)[len(out) // 2]
+    out.sort()
+    return out[0], out[len(out) // 2], out[min(len(out) - 1, max(0, round(0.9 * (len(out) - 1))))]
 
 
 def main():
@@ -37,9 +39,9 @@ def main():
                 continue
             full = lambda: _ffi.check_status(lib.gpu_matrix_sample_distribution(m.raw, dist, sigma, seed(3)), "sample")
             ntt = lambda: (_ffi.check_status(lib.gpu_matrix_intt_all(m.raw), "intt"), _ffi.check_status(lib.gpu_matrix_ntt_all(m.raw), "ntt"))
-            mn, med = timed(ctx, full)
-            nmn, _ = timed(ctx, ntt)
-            print(f"{name:18s} {dname:8s}: sample+NTT {mn:8.3f} ms (median {med:.3f}); INTT+NTT pair {nmn:7.3f} ms -> sampler alone ~{mn - nmn / 2:7.3f} ms "
+            mn, med, p90 = timed(ctx, full)
+            nmn, _, _ = timed(ctx, ntt)
+            print(f"{name:18s} {dname:8s}: sample+NTT {mn:8.3f} ms (median {med:.3f}, p90 {p90:.3f}); INTT+NTT pair {nmn:7.3f} ms -> sampler alone ~{mn - nmn / 2:7.3f} ms "
                   f"= {gb / max(mn - nmn / 2, 1e-6) * 1e3 / 1e3:6.2f} TB/s of output ({gb:.2f} GB)")
         del m
 
