@@ -805,6 +805,55 @@ int gpupoly_matrix_ggh15_lookup_combine(GpuMatrix *const *outs, size_t nslots_S,
                                         const GpuMatrix *const *lut_preimages, const GpuMatrix *const *xs, size_t col_start,
                                         uint32_t base_bits, const uint64_t *y_words, size_t words_per_y,
                                         const GpuMatrix *digits);
+/* ---- the online side of the LWE lookup (extension).  The evaluator's public_lookup_poly_gpu
+ * (src/lookup/lwe/poly_encoding_gpu.rs:419-453) is a plain loop over the slots, with a TODO asking for a slot-level
+ * scheduler, around public_lookup_slot_gpu (src/lookup/lwe/encoding_gpu.rs:225-370), which per slot and column chunk forms
+ * two products - c_b against the stored K_high chunk, the input vector against the decomposed hash sample K_low
+ * (compute_wave, src/lookup/lwe/encoding_gpu.rs:142-188) -, takes both through compact bytes, concatenates the chunks and
+ * adds the two families (reduce_contribution_bytes_by_chunk, :190-223).  With d the secret size, k = dpt * (level + 1),
+ * m_g = d * k, w the rows of a stored K_high chunk (the width of the trapdoor's public matrix; not tied to d here) and r the
+ * rows of an encoding vector (1 in the reference), this entry serves S slots of one gate and ONE output column chunk
+ * [col_start, col_start + c), c = k_highs[0]->cols:
+ *   out_s[:, dst_col .. dst_col + c) = c_b_s K_high_s + c_z_s G^-1(U_s[:, col_start .. col_start + c)),
+ *   c_bs[s]   r x w, EVAL        k_highs[s]   w x c, EVAL (the stored chunk of the slot's LUT-row preimage)
+ *   c_zs[s]   r x m_g, EVAL (m_g = c_zs[0]->cols, a multiple of k)        outs[s]   r x C, made by the caller, dst_col + c <= C
+ *   U_s the d x m_g uniform matrix under hash_seed_for_matrix(key, tag_s), tag_s = "LWE_R_G_<gate>_<lut>_<entry_s>_slot<slot>":
+ *   the entry index stands in the middle of the tag, so callers send the TABLE form of `tags`.
+ * The same matrix may be given for several slots in c_bs, k_highs and c_zs; one context and one level, which may be below the
+ * top.  Exact arithmetic on canonical residues: the result equals the reference's two gpu_matrix_mul, one gpu_matrix_add and
+ * a copy_block into place bit for bit.  Columns of outs[s] outside the block are not touched; every output is tagged EVAL on
+ * success, and a partial block into an output not already tagged EVAL is refused (gpupoly_matrix_mul_sum's rule), so a caller
+ * writes every chunk straight into the full-width r x m_g result, without a concatenation.
+ * The slots go in groups whose digit scratch m_g x (Sg c) stays under 1 GiB (MXX_HIP_LWE_LOOKUP_BUDGET=<bytes> overrides the
+ * cap), at most 2^20 slots each.  Per group: ONE staged copy of the slots' table (output, c_b, K_high and c_z pointers), the
+ * decomposed-blocks hash sample [D_0 | D_1 | ...] into scratch of the context's allocator, and ONE main kernel - no pre-pass,
+ * the left factors are read in place through the table: every output word is one lazy accumulator over the w terms against
+ * K_high_s and the m_g terms against D_s, folded every lazy_terms terms wherever they fall, reduced once and stored once.  A
+ * lane holds a term's left words in registers for a tile of up to 4 chunk columns and 2 rows, 16 bytes per load and store
+ * (one word where a limb vector is narrower); every word of K_high_s and D_s is loaded by one tile only.  Launches per group:
+ * those of gpupoly_matrix_sample_hash_decomposed_blocks for Sg tags + 1 kernel + 1 copy, whatever S; the slot descriptors
+ * live in the device table, not in the kernel arguments.  Scratch is released stream-ordered; the host does not block;
+ * PACKED24 operands are unpacked first; S = 0, c = 0 and r = 0 succeed with nothing launched; w = 0 is legal and gives the
+ * digits term alone.
+ * Overlap: an outs[s] must overlap no c_bs[t], k_highs[t], c_zs[t] and no other output, row views included; disjoint views
+ * of one parent are accepted (the message contains "overlap").
+ * Refused, with nothing launched and every output (residues AND tag) untouched, everything checked for every slot before
+ * the first launch, the message naming this entry: a null array or entry; a context, level or shape mismatch (the slot in
+ * the message); an operand not in EVAL form; m_g not a multiple of k; col_start + c > m_g; dst_col + c > C; K_high chunks or
+ * outputs of different widths; a partial block into a non-EVAL output; base_bits of 0 or >= 63; everything
+ * gpupoly_hash_seeds refuses of `tags`; the overlaps above.  Refused likewise with "unsupported" in the text: a context
+ * created under MXX_HIP_RNG_COMPAT=reference.                                                                            */
+int gpupoly_matrix_lwe_lookup(GpuMatrix *const *outs, size_t nslots_S, size_t dst_col, const GpuMatrix *const *c_bs,
+                              const GpuMatrix *const *k_highs, const GpuMatrix *const *c_zs, size_t col_start,
+                              uint32_t base_bits, const GpuHashTags *tags);
+/* Test instrument: the same with the digits GIVEN - `digits` is m_g x (S * c), EVAL, slot s at columns [s c, (s + 1) c) -
+ * instead of sampled: the table copy and the main kernel alone, one group whatever S.  It lets a test reach the lazy
+ * accumulator's bound with operands no sampler produces.  Arguments, overlap rule and refusals as above (`digits` counts as
+ * an operand; no tags, any RNG keying).                                                                                  */
+int gpupoly_matrix_lwe_lookup_combine(GpuMatrix *const *outs, size_t nslots_S, size_t dst_col,
+                                      const GpuMatrix *const *c_bs, const GpuMatrix *const *k_highs,
+                                      const GpuMatrix *const *c_zs, size_t col_start, uint32_t base_bits,
+                                      const GpuMatrix *digits);
 /* Exact scale-and-round of every coefficient (extension): coefficient k of out[i][j] becomes
  *   floor((t * c + h) / Q) mod t,   h = round_half ? floor(Q/2) : 0,
  * c the coefficient of in[i][j] as coeffs() gives it (in [0, Q)), Q the context's FULL modulus; written as its residue

@@ -177,6 +177,10 @@ SIGNATURES = {
                                     C.POINTER(C.c_void_p), _sz, C.c_uint32, C.POINTER(C.c_uint64), _sz, C.POINTER(GpuHashTags)]),
     "gpupoly_matrix_ggh15_lookup_combine": (C.c_int, [C.POINTER(C.c_void_p), _sz, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_void_p),
                                             C.POINTER(C.c_void_p), _sz, C.c_uint32, C.POINTER(C.c_uint64), _sz, _vp]),
+    "gpupoly_matrix_lwe_lookup": (C.c_int, [C.POINTER(C.c_void_p), _sz, _sz, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                  _sz, C.c_uint32, C.POINTER(GpuHashTags)]),
+    "gpupoly_matrix_lwe_lookup_combine": (C.c_int, [C.POINTER(C.c_void_p), _sz, _sz, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_void_p), _sz, C.c_uint32, _vp]),
     "gpupoly_matrix_sample_p1_full_cached_segments":(C.c_int, [_vp, _vp, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz, _vp]),
     "gpupoly_matrix_gauss_samp_gq_arb_base_segments": (C.c_int, [_vp, C.c_uint32, C.c_double, C.c_double, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz, _vp]),
     "gpupoly_matrix_concat_columns": (C.c_int, [_vp, C.POINTER(C.c_void_p), _sz]),

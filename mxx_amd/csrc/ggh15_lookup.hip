@@ -207,34 +207,6 @@ struct LookupCall : RowCall {
     size_t cap;                // a group's scratch
 };
 
-inline std::string slot_at(size_t s) { return " (slot " + std::to_string(s) + ")"; }
-
-inline size_t held_bytes(const GpuMatrix *m) {
-    return m->layout.v.load(std::memory_order_acquire) == GPU_MATRIX_LAYOUT_PACKED24 ? packed24_bytes(m) : m->bytes;
-}
-
-// an output overlaps one of the per-slot operands (K_s, x_s; the same matrix may stand for several slots): the operands'
-// blocks sorted by start with the furthest end so far, one search per output
-std::string slot_operands_overlap(GpuMatrix *const *outs, const GpuMatrix *const *luts, const GpuMatrix *const *xs, size_t S) {
-    std::vector<std::pair<const char *, const char *>> blocks;
-    for (size_t s = 0; s < S; ++s)
-        for (const GpuMatrix *m : {luts[s], xs[s]})
-            if (m->storage && m->bytes) blocks.emplace_back(static_cast<const char *>(m->storage), static_cast<const char *>(m->storage) + held_bytes(m));
-    std::sort(blocks.begin(), blocks.end());
-    for (size_t j = 1; j < blocks.size(); ++j) blocks[j].second = std::max(blocks[j].second, blocks[j - 1].second);
-    for (size_t t = 0; t < S; ++t) {
-        const GpuMatrix *out = outs[t];
-        for (size_t s = 0; s < S; ++s)
-            if (out == luts[s] || out == xs[s]) return "overlap: an output overlaps a slot's operand" + slot_at(t);
-        if (!out->storage || !out->bytes) continue;
-        const char *lo = static_cast<const char *>(out->storage), *hi = lo + held_bytes(out);
-        // the blocks that start below the output's end: the furthest of their ends reaches past its start
-        const auto it = std::lower_bound(blocks.begin(), blocks.end(), std::make_pair(hi, static_cast<const char *>(nullptr)));
-        if (it != blocks.begin() && (it - 1)->second > lo) return "overlap: an output overlaps a slot's operand" + slot_at(t);
-    }
-    return "";
-}
-
 // Everything both entries refuse, for every slot, before anything is launched.  `digits` null: the sampling entry, whose
 // tags are checked; otherwise the combine entry with [V_0 | V_1 | ...] given.
 int check_call(const char *who, GpuMatrix *const *outs, size_t S, const GpuMatrix *const (&mids)[6], const GpuMatrix *const *luts,
@@ -283,7 +255,7 @@ int check_call(const char *who, GpuMatrix *const *outs, size_t S, const GpuMatri
     static const char *const names[7] = {"a stage-1 product", "a stage-1 product", "a stage-1 product", "a stage-1 product",
                                          "a stage-1 product", "a stage-1 product", "the digits"};
     if (int rc = refuse_tags_overlap(refuse, full ? tags : nullptr, S, outs, S, operands, names, digits ? 7 : 6)) return rc;
-    const std::string overlap = slot_operands_overlap(outs, luts, xs, S);
+    const std::string overlap = slot_operands_overlap(outs, S, {luts, xs});
     return overlap.empty() ? 0 : refuse(overlap);
 }
 

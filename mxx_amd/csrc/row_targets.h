@@ -3,7 +3,9 @@
 // keeps its own order, shape sentences and position suffix), the rows of a call in groups under one scratch cap with
 // their tags cut per group, one staged table per group, the outputs' overlap rule and the one launcher of a combine
 // kernel.  Device side: what the two combine kernels share - the output polynomial of a block and the lazy accumulator.  A
-// builder adds its formula: its operands' checks, its table's rows and its kernel's terms.  Every kernel of the three
+// builder adds its formula: its operands' checks, its table's rows and its kernel's terms.  The online lookups
+// (ggh15_lookup.hip, lwe_lookup.hip) stand on the same host scaffold with slots for rows, and share the rule for operands
+// that every slot brings of its own.  Every kernel of the three
 // files compiles to the bytes it had before it was written on top of this (profiles/row_targets_refactor.txt), and some
 // pieces have the form they have for that reason; each says so.
 #pragma once
@@ -12,6 +14,7 @@
 #include "modarith.h"
 
 #include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -131,6 +134,39 @@ inline int refuse_tags_overlap(const Refuse &refuse, const GpuHashTags *tags, si
     if (tags && hash_tags_check(refuse.who, tags, T, &tag_bytes)) return 1;
     const std::string overlap = row_outputs_overlap(outs, count, operands, names, noperands);
     return overlap.empty() ? 0 : refuse(overlap);
+}
+
+// ---- the lookups (ggh15_lookup.hip, lwe_lookup.hip): S slots, each with operands of its own ------------------------
+inline std::string slot_at(size_t s) { return " (slot " + std::to_string(s) + ")"; }
+
+inline size_t held_bytes(const GpuMatrix *m) {
+    return m->layout.v.load(std::memory_order_acquire) == GPU_MATRIX_LAYOUT_PACKED24 ? packed24_bytes(m) : m->bytes;
+}
+
+// an output overlaps one of the per-slot operands (`kinds`: arrays of S matrices; the same matrix may stand for several
+// slots): the operands' blocks sorted by start with the furthest end so far, one search per output
+inline std::string slot_operands_overlap(GpuMatrix *const *outs, size_t S, std::initializer_list<const GpuMatrix *const *> kinds) {
+    std::vector<std::pair<const char *, const char *>> blocks;
+    std::vector<const GpuMatrix *> given;
+    for (size_t s = 0; s < S; ++s)
+        for (const GpuMatrix *const *kind : kinds) {
+            const GpuMatrix *m = kind[s];
+            given.push_back(m);
+            if (m->storage && m->bytes) blocks.emplace_back(static_cast<const char *>(m->storage), static_cast<const char *>(m->storage) + held_bytes(m));
+        }
+    std::sort(given.begin(), given.end());
+    std::sort(blocks.begin(), blocks.end());
+    for (size_t j = 1; j < blocks.size(); ++j) blocks[j].second = std::max(blocks[j].second, blocks[j - 1].second);
+    for (size_t t = 0; t < S; ++t) {
+        const GpuMatrix *out = outs[t];
+        if (std::binary_search(given.begin(), given.end(), out)) return "overlap: an output overlaps a slot's operand" + slot_at(t);
+        if (!out->storage || !out->bytes) continue;
+        const char *lo = static_cast<const char *>(out->storage), *hi = lo + held_bytes(out);
+        // the blocks that start below the output's end: the furthest of their ends reaches past its start
+        const auto it = std::lower_bound(blocks.begin(), blocks.end(), std::make_pair(hi, static_cast<const char *>(nullptr)));
+        if (it != blocks.begin() && (it - 1)->second > lo) return "overlap: an output overlaps a slot's operand" + slot_at(t);
+    }
+    return "";
 }
 
 // ---- host: groups of rows, their scratch and their table ------------------------------------------

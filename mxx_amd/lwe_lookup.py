@@ -9,7 +9,9 @@ x the row's LUT input and y its value, both constant polynomials, and the online
 c_b K_high + c_z K_low chunk by chunk.  `build_adjusted_target_chunk` is the reference's function restated with the
 mirror's operations, one row at a time; `lwe_target_chunks` builds the targets of many rows in one library call
 (gpupoly_matrix_lwe_targets); `sample_lwe_preimages` feeds them into the batched preimage, the body
-of the reference's `wave` loop; `public_lookup` is the online side."""
+of the reference's `wave` loop; `public_lookup` is the online side for one LUT row of one slot, `public_lookup_slots` for
+many slots of one gate with one library call per output chunk (gpupoly_matrix_lwe_lookup), and
+`public_lookup_poly` the body of the evaluator's public_lookup_poly_gpu (src/lookup/lwe/poly_encoding_gpu.rs:389-463) on top."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -121,3 +123,92 @@ def public_lookup(shared: LweShared, c_b: GpuDCRTPolyMatrix, c_z: GpuDCRTPolyMat
         GpuDCRTPolyMatrix.mul_sum([c_b, c_z], [k_high, k_low], out=out, dst_col=col_start)
         col_start += k_high.ncol
     return out
+
+
+def public_lookup_slots(shareds, c_bs, c_zs, k_high_chunks_by_slot, entry_idxs) -> list:
+    """[public_lookup(shareds[s], c_bs[s], c_zs[s], k_high_chunks_by_slot[s], entry_idxs[s]) for every slot s] - the slot loop
+    of public_lookup_poly_gpu (poly_encoding_gpu.rs:419-453) around public_lookup_slot_gpu (encoding_gpu.rs:225-370) - for
+    the slots of ONE gate: the S full-width r x m_g outputs are allocated once and every output chunk of all slots is ONE
+    library call that writes in place (gpupoly_matrix_lwe_lookup with dst_col).  The slots share the key, the gate and
+    LUT ids and the chunk widths; a K_high chunk, c_b or c_z may serve several slots.  Where the library answers
+    "unsupported" (MXX_HIP_RNG_COMPAT=reference) and for hashes without a device form the per-slot `public_lookup` runs: the
+    same matrices either way."""
+    shareds, c_bs, c_zs, entry_idxs = list(shareds), list(c_bs), list(c_zs), [int(i) for i in entry_idxs]
+    by_slot = [list(chunks) for chunks in k_high_chunks_by_slot]
+    count = len(shareds)
+    assert len(c_bs) == len(c_zs) == len(by_slot) == len(entry_idxs) == count, "public_lookup_slots: one c_b, c_z, chunk list and LUT row per slot"
+    if count == 0:
+        return []
+    first = shareds[0]
+    for sh in shareds:
+        assert (sh.params, sh.hash_key, sh.gate_id, sh.lut_id, sh.hash_name, sh.m_g) == \
+            (first.params, first.hash_key, first.gate_id, first.lut_id, first.hash_name, first.m_g), "public_lookup_slots: the slots of one gate"
+    widths = [kh.ncol for kh in by_slot[0]]
+    assert sum(widths) == first.m_g, "public_lookup_slots: the K_high chunks cover the m_g columns"
+    for chunks in by_slot:
+        assert [kh.ncol for kh in chunks] == widths, "public_lookup_slots: the slots' chunks have the same widths"
+    if first.sampler()._on_device():
+        tags = [sh.tag(i) for sh, i in zip(shareds, entry_idxs)]
+        outs = [GpuDCRTPolyMatrix(first.params, c_b.nrow, first.m_g, c_b.level, True) for c_b in c_bs]
+        try:
+            col_start = 0
+            for j, width in enumerate(widths):
+                GpuDCRTPolyMatrix.lwe_lookup(outs, c_bs, [chunks[j] for chunks in by_slot], c_zs, col_start, first.hash_key, tags,
+                                             first.hash_name, dst_col=col_start)
+                col_start += width
+            return outs
+        except _ffi.GpuPolyError as e:
+            if "unsupported" not in str(e):
+                raise
+    return [public_lookup(shareds[s], c_bs[s], c_zs[s], by_slot[s], entry_idxs[s]) for s in range(count)]
+
+
+def public_lookup_poly(params, hash_key: bytes, gate_id: int, lut_id: int, plt, d: int, c_bs, input_vectors, plaintexts, k_high_blobs,
+                       slot_idxs=None, hash_name: str = "keccak256", wave_slots=None):
+    """The body of public_lookup_poly_gpu (poly_encoding_gpu.rs:389-463) for the slots of one BggPolyEncoding: `plt` maps a
+    slot's plaintext constant x to its LUT row (k, y) (plt.get, encoding_gpu.rs:245-249); c_bs[s] is the slot's encoding under
+    the trapdoor's public matrix, input_vectors[s] its input encoding, plaintexts[s] its plaintext polynomial.
+    `k_high_blobs(k, slot_idx)` gives the compact bytes of the stored K_high chunks of LUT row k in column order (the
+    reference reads them from its checkpoint directory, load_wave).  slot_idxs: what the tags and A_lt are derived with per
+    slot - None for every slot, as the reference passes (poly_encoding_gpu.rs:436).  The S A_lt matrices are ONE
+    `sample_hash_many` call; the slots go in waves of `wave_slots` (default: all), a wave's K_high chunks - one per distinct
+    (row, slot index, chunk) - are loaded by ONE `from_compact_bytes_many` call and its output vectors made by
+    `public_lookup_slots`.  Returns (the slots' r x m_g vectors, A_lt per slot, y per slot)."""
+    c_bs, input_vectors, plaintexts = list(c_bs), list(input_vectors), list(plaintexts)
+    count = len(plaintexts)
+    assert len(c_bs) == len(input_vectors) == count, "public_lookup_poly: one c_b, input vector and plaintext per slot"
+    slot_idxs = [None] * count if slot_idxs is None else list(slot_idxs)
+    assert len(slot_idxs) == count
+    rows = []
+    for x in plaintexts:
+        x_u64 = x.const_coeff_u64()
+        if x_u64 not in plt:
+            raise KeyError(f"{x_u64} not found in the LUT of gate {gate_id}")
+        k, y = plt[x_u64]
+        rows.append((int(k), int(y)))
+    sampler = GpuDCRTPolyHashSampler(hash_name)
+    a_lts = sampler.sample_hash_many(params, hash_key, [f"A_LT_{gate_id}_slot{i or 0}".encode("ascii") for i in slot_idxs], d,
+                                     d * params.modulus_digits(), DistType.FinRingDist())
+    shareds = [LweShared(params, hash_key, gate_id, lut_id, i, None, a_lt, hash_name) for i, a_lt in zip(slot_idxs, a_lts)]
+    vectors = []
+    step = count if not wave_slots else int(wave_slots)
+    for lo in range(0, count, max(step, 1)):
+        wave = range(lo, min(lo + step, count))
+        keys = {}
+        blobs = []
+        for s in wave:
+            key = (rows[s][0], slot_idxs[s] or 0)
+            if key not in keys:
+                mine = list(k_high_blobs(rows[s][0], slot_idxs[s]))
+                keys[key] = (len(blobs), len(mine))
+                blobs += mine
+        loaded = GpuDCRTPolyMatrix.from_compact_bytes_many(params, blobs)
+        for m in loaded:
+            m.ntt_all_in_place()
+        by_slot = []
+        for s in wave:
+            at, n = keys[(rows[s][0], slot_idxs[s] or 0)]
+            by_slot.append(loaded[at:at + n])
+        vectors += public_lookup_slots([shareds[s] for s in wave], [c_bs[s] for s in wave], [input_vectors[s] for s in wave], by_slot,
+                                       [rows[s][0] for s in wave])
+    return vectors, a_lts, [y for _, y in rows]

@@ -2437,6 +2437,52 @@ class GpuDCRTPolyMatrix:
         return GpuDCRTPolyMatrix._ggh15_lookup_call("gpupoly_matrix_ggh15_lookup_combine", mids, lut_preimages, xs, col_start, col_len, ys, digits.raw)
 
     @staticmethod
+    def _lwe_lookup_call(entry: str, outs, c_bs, k_highs, c_zs, col_start, dst_col, last) -> list:
+        """`entry(outs, S, dst_col, c_b array, K_high array, c_z array, col_start, base, last)`; `outs` None: S fresh
+        r x chunk-column outputs (dst_col = 0)"""
+        c_bs, k_highs, c_zs = list(c_bs), list(k_highs), list(c_zs)
+        count = len(c_zs)
+        assert len(c_bs) == len(k_highs) == count, "lwe_lookup: one c_b, K_high chunk and input vector per slot"
+        if outs is None:
+            assert dst_col == 0, "lwe_lookup: dst_col needs `outs` to place the block in"
+            outs = [GpuDCRTPolyMatrix(z.params, z.nrow, kh.ncol, z.level, True) for z, kh in zip(c_zs, k_highs)]
+        else:
+            outs = list(outs)
+            assert len(outs) == count, "lwe_lookup: one output per slot"
+        if count == 0:
+            return outs
+        for out in outs:
+            out._touch()
+        st = getattr(_ffi.lib(), entry)(GpuDCRTPolyMatrix._raw_array(outs), count, dst_col, GpuDCRTPolyMatrix._raw_array(c_bs),
+                                        GpuDCRTPolyMatrix._raw_array(k_highs), GpuDCRTPolyMatrix._raw_array(c_zs), col_start,
+                                        c_zs[0].params.base_bits(), last)
+        check_status(st, entry)
+        for out in outs:
+            out.is_ntt = True
+        return outs
+
+    @staticmethod
+    def lwe_lookup(outs, c_bs, k_highs, c_zs, col_start, key: bytes, tags, hash_name: str = "keccak256", dst_col: int = 0) -> list:
+        """The online side of the LWE public lookup for len(c_zs) slots of one gate and the output column chunk
+        [col_start, col_start + c), c = k_highs[0].ncol, in one call (gpupoly_matrix_lwe_lookup):
+            outs[s][:, dst_col .. dst_col + c) = c_bs[s] k_highs[s] + c_zs[s] G^-1(U_s[:, col_start .. col_start + c)),
+        c_bs[s] r x w, k_highs[s] w x c, c_zs[s] r x m_g, U_s the d x m_g uniform matrix under
+        hash_seed_for_matrix(key, tags[s]); one matrix may serve several slots.  `outs` None: fresh r x c matrices; otherwise
+        the slots' r x C matrices, whose columns outside the block keep their contents.  Returns the outputs."""
+        c_zs = list(c_zs)
+        arg, keep, count = hash_tags_arg(key, tags, hash_name)
+        assert count == len(c_zs), "lwe_lookup: one tag per slot"
+        out = GpuDCRTPolyMatrix._lwe_lookup_call("gpupoly_matrix_lwe_lookup", outs, c_bs, k_highs, c_zs, col_start, dst_col, C.byref(arg))
+        del keep
+        return out
+
+    @staticmethod
+    def lwe_lookup_combine(outs, c_bs, k_highs, c_zs, digits, col_start, dst_col: int = 0) -> list:
+        """Test instrument (gpupoly_matrix_lwe_lookup_combine): `lwe_lookup` with [D_0 | D_1 | ...] given as the
+        m_g x (len(c_zs) * c) EVAL matrix `digits` instead of sampled."""
+        return GpuDCRTPolyMatrix._lwe_lookup_call("gpupoly_matrix_lwe_lookup_combine", outs, c_bs, k_highs, c_zs, col_start, dst_col, digits.raw)
+
+    @staticmethod
     def sample_p1_full_cached_segments(cache: GpuP1CovarianceCache, tp2, seeds, seg_cols) -> "GpuDCRTPolyMatrix":
         """`sample_p1_full_cached` over column segments with a seed each (tp2 is taken to the coefficient domain in place)."""
         out = GpuDCRTPolyMatrix.new_empty(tp2.params, tp2.nrow, tp2.ncol)
