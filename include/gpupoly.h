@@ -854,6 +854,76 @@ int gpupoly_matrix_lwe_lookup_combine(GpuMatrix *const *outs, size_t nslots_S, s
                                       const GpuMatrix *const *c_bs, const GpuMatrix *const *k_highs,
                                       const GpuMatrix *const *c_zs, size_t col_start, uint32_t base_bits,
                                       const GpuMatrix *digits);
+/* ---- the online side of the slot-transfer gates (extension).  The evaluator's output_slot_for_params
+ * (src/slot_transfer/bgg_poly_encoding.rs:119-248) and slot_reduce_output_slot_for_params (:250-386) - on the device
+ * src/slot_transfer/bgg_poly_encoding_gpu.rs:255-786: stage-1 tasks, stage-2 tasks, reduce_slot_transfer_matrix_bytes, all
+ * behind the plain `for dst_slot` loop of evaluate_slot_transfer_slots_gpu (:748-786) - form per destination slot and column
+ * chunk one one-row product per term and family (lhs * &rhs_chunk, :477 and :640), take each through compact bytes and
+ * concatenate; c_b0 P0_src is recomputed for every destination, in slot_reduce num_slots times per destination (:300-372).
+ * With d the secret size, k = dpt * (level + 1), m_g = d * k, r the rows of an encoding vector (1 in the reference), w0 the
+ * columns of B0 and w1 the columns of B1 (d (k + 2) and 2 d (k + 2) in the reference; neither is tied to d here), a
+ * destination slot s with terms t has
+ *   out_s = c_b0 Pg_s + sum_t x^shift_t o kappa_t o ( c_in_t G^-1(A_s) + mu_t o ((c_b0 P0_src_t) P1_s) ),
+ * Pg_s the stored gate preimage (w0 x m_g), P0_src (w0 x w1) and P1_s (w1 x m_g) the stored slot preimages, A_s the d x m_g
+ * uniform matrix under hash_seed_for_matrix(key, "slot_transfer_slot_a_<s>"), mu_t the constant coefficient of the source
+ * plaintext (an integer below Q), kappa_t the optional scalar; slot_transfer has one term per output with shift 0,
+ * slot_reduce num_slots terms with shift = the source index and kappa = 1.  Exact arithmetic on canonical residues, so
+ * re-associating changes no bit.  STAGE 1 is the caller's, with the product entries: mid_src = c_b0 P0_src once per DISTINCT
+ * source.  STAGE 2, this entry, for S outputs of one gate and ONE output column chunk [col_start, col_start + c),
+ * c = gate_preimages[0]->cols:
+ *   LhsA_s = sum_t (kappa_t x^shift_t) o c_in_t (r x m_g)        LhsB_s = sum_t (kappa_t mu_t x^shift_t) o mid_t (r x w1)
+ *   outs[s][:, dst_col .. dst_col + c) = c_b0 Pg_s[:, chunk] + LhsA_s G^-1(A_s[:, chunk]) + LhsB_s P1_s[:, chunk]
+ *   c_b0   r x w0, EVAL        gate_preimages[s]   w0 x c, EVAL        b1_preimages[s]   w1 x c, EVAL
+ *   terms of output s: terms[term_offsets[s] .. term_offsets[s + 1]), at least one; term_offsets has S + 1 entries from 0
+ *   mu_words   one integer of words_per_mu little-endian 64-bit words PER TERM (as y_words of gpupoly_matrix_lut_targets)
+ *   tags       tag_s names A_s: indexed-decimal form for consecutive destinations, the TABLE form otherwise
+ *   outs[s]    r x C, made by the caller, dst_col + c <= C; columns outside the block are not touched
+ * The same matrix may serve several outputs or terms.  Every output is tagged EVAL on success; a partial block into an
+ * output not already EVAL is refused (gpupoly_matrix_mul_sum's rule), so a caller writes every chunk straight into the
+ * full-width r x m_g result.
+ * The outputs go in groups whose scratch - the digits m_g x (Sg c) and the left factors (Sg r) x (m_g + w1) - stays under
+ * 1 GiB (MXX_HIP_SLOT_EVAL_BUDGET=<bytes> overrides the cap), at most 2^20 outputs each.  Per group: ONE staged copy of the
+ * table (per output the output, Pg, P1 and A-segment pointers and the term range; per term the c_in and mid pointers, the
+ * shift mod 2N and per limb kappa mod q_l and kappa mu mod q_l, computed on the host), the decomposed-blocks hash sample
+ * [D_0 | D_1 | ...], ONE pre-pass kernel that writes LhsA and LhsB with canonical residues (a thread owns a 16-byte vector
+ * of evaluation slots of 4 polynomials of one limb, forms weight * psi_l^(shift (2 bitrev(k) + 1)) once per term - no table
+ * gather when the shift is 0 - and accumulates lazily), and ONE main kernel: gpupoly_matrix_lwe_lookup's register tile (up
+ * to 2 rows x 4 chunk columns, 16 bytes per load and store, one word where a limb vector is narrower) with three streams
+ * into one lazy accumulator - w0 terms of c_b0 against Pg_s, m_g terms of the A segment against D_s, w1 terms of LhsB_s
+ * against P1_s - folded every lazy_terms terms wherever they fall, reduced once, stored once.  An output whose only term
+ * has shift 0 (mod 2N) and scalar 1 gets no A segment: the main kernel reads its c_in in place.  Launches per group: those
+ * of gpupoly_matrix_sample_hash_decomposed_blocks for Sg tags + 2 kernels + 1 copy, whatever S and the number of terms.
+ * Scratch is released stream-ordered; the host does not block; PACKED24 operands are unpacked first; S = 0, c = 0 and
+ * r = 0 succeed with nothing launched; w0 = 0 and w1 = 0 are legal; scalar = 0 is a legal weight.
+ * Overlap: an outs[s] must overlap no operand and no other output, row views included; disjoint views of one parent are
+ * accepted (the message contains "overlap").
+ * Refused, with nothing launched and every output (residues AND tag) untouched, everything checked for every output and
+ * term before the first launch, the message naming this entry and the slot or term: a null array or entry; a context,
+ * level or shape mismatch; an operand not in EVAL form; term_offsets not non-decreasing from 0 or an output without terms;
+ * m_g not a multiple of k; col_start + c > m_g; dst_col + c > C; preimage chunks or outputs of different widths; a
+ * partial block into a non-EVAL output; words_per_mu == 0; base_bits of 0 or >= 63; everything gpupoly_hash_seeds refuses
+ * of `tags`; the overlaps above.  Refused likewise with "unsupported" in the text: a context created under
+ * MXX_HIP_RNG_COMPAT=reference.                                                                                          */
+typedef struct {
+    const GpuMatrix *c_in; /* r x m_g, EVAL */
+    const GpuMatrix *mid;  /* r x w1, EVAL: c_b0 * P0_src, made by the caller (stage 1) */
+    uint64_t shift;        /* the term is multiplied by x^shift, taken mod 2N */
+    uint64_t scalar;       /* and by this integer; 1 = none */
+} GpuSlotTerm;
+int gpupoly_matrix_slot_transfer_eval(GpuMatrix *const *outs, size_t nouts_S, size_t dst_col, const GpuMatrix *c_b0,
+                                      const GpuMatrix *const *gate_preimages, const GpuMatrix *const *b1_preimages,
+                                      const GpuSlotTerm *terms, const size_t *term_offsets, const uint64_t *mu_words,
+                                      size_t words_per_mu, size_t col_start, uint32_t base_bits, const GpuHashTags *tags);
+/* Test instrument (the stage-2 tasks of src/slot_transfer/bgg_poly_encoding_gpu.rs:255-786 without their sampler): the
+ * same with the digits GIVEN - `digits` is m_g x (S * c), EVAL, output s at columns [s c, (s + 1) c) - instead of sampled:
+ * the table copy, the pre-pass and the main kernel alone, one group whatever S.  It lets a test reach the lazy
+ * accumulator's bound with operands no sampler produces.  Arguments, overlap rule and refusals as above (`digits` counts as
+ * an operand; no tags, any RNG keying).                                                                                  */
+int gpupoly_matrix_slot_transfer_eval_combine(GpuMatrix *const *outs, size_t nouts_S, size_t dst_col, const GpuMatrix *c_b0,
+                                              const GpuMatrix *const *gate_preimages,
+                                              const GpuMatrix *const *b1_preimages, const GpuSlotTerm *terms,
+                                              const size_t *term_offsets, const uint64_t *mu_words, size_t words_per_mu,
+                                              size_t col_start, uint32_t base_bits, const GpuMatrix *digits);
 /* Exact scale-and-round of every coefficient (extension): coefficient k of out[i][j] becomes
  *   floor((t * c + h) / Q) mod t,   h = round_half ? floor(Q/2) : 0,
  * c the coefficient of in[i][j] as coeffs() gives it (in [0, Q)), Q the context's FULL modulus; written as its residue

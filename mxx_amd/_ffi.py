@@ -58,6 +58,13 @@ class GpuHashTags(C.Structure):
                 ("tag_offsets", C.POINTER(C.c_size_t)), ("prefix_len", C.c_size_t), ("first_index", C.c_uint64)]
 
 
+class GpuSlotTerm(C.Structure):
+    """`struct GpuSlotTerm { const GpuMatrix *c_in, *mid; uint64_t shift, scalar; }` (include/gpupoly.h): one term of an output
+    of gpupoly_matrix_slot_transfer_eval."""
+
+    _fields_ = [("c_in", C.c_void_p), ("mid", C.c_void_p), ("shift", C.c_uint64), ("scalar", C.c_uint64)]
+
+
 class GpuBatchOp(C.Structure):
     """`struct GpuBatchOp { int kind; GpuMatrix *out; const GpuMatrix *lhs, *rhs; }` (include/gpupoly.h)."""
 
@@ -181,6 +188,11 @@ SIGNATURES = {
                                   _sz, C.c_uint32, C.POINTER(GpuHashTags)]),
     "gpupoly_matrix_lwe_lookup_combine": (C.c_int, [C.POINTER(C.c_void_p), _sz, _sz, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                           C.POINTER(C.c_void_p), _sz, C.c_uint32, _vp]),
+    "gpupoly_matrix_slot_transfer_eval": (C.c_int, [C.POINTER(C.c_void_p), _sz, _sz, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                          C.POINTER(GpuSlotTerm), C.POINTER(_sz), C.POINTER(C.c_uint64), _sz, _sz, C.c_uint32,
+                                          C.POINTER(GpuHashTags)]),
+    "gpupoly_matrix_slot_transfer_eval_combine": (C.c_int, [C.POINTER(C.c_void_p), _sz, _sz, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                  C.POINTER(GpuSlotTerm), C.POINTER(_sz), C.POINTER(C.c_uint64), _sz, _sz, C.c_uint32, _vp]),
     "gpupoly_matrix_sample_p1_full_cached_segments":(C.c_int, [_vp, _vp, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz, _vp]),
     "gpupoly_matrix_gauss_samp_gq_arb_base_segments": (C.c_int, [_vp, C.c_uint32, C.c_double, C.c_double, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz, _vp]),
     "gpupoly_matrix_concat_columns": (C.c_int, [_vp, C.POINTER(C.c_void_p), _sz]),

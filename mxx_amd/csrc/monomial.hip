@@ -23,6 +23,7 @@
 // place: out == addend accumulates in place.
 #include "common.h"
 #include "modarith.h"
+#include "monomial_factor.h"
 
 #include <algorithm>
 #include <string>
@@ -38,16 +39,7 @@ struct MonoArgs {
     uint32_t shift[kMonoMax];  // reduced mod 2N
 };
 
-__device__ __forceinline__ uint32_t bitrev_n(uint32_t x, uint32_t logN) { return logN ? __brev(x) >> (32u - logN) : 0u; }
-
-// psi^(s * odd) of one limb, odd = 2 bitrev(slot) + 1: the table entry, negated in the upper half of the exponents (psi^N = -1;
-// a power of psi is never 0)
-template <typename W>
-__device__ __forceinline__ W monomial_factor(const W *__restrict__ tw, uint32_t s, uint32_t odd, uint32_t N, uint32_t logN, W q) {
-    const uint32_t e = (s * odd) & (2u * N - 1u);  // wraps mod 2^32, a multiple of 2N
-    const W f = tw[bitrev_n(e & (N - 1u), logN)];
-    return (e & N) ? static_cast<W>(q - f) : f;
-}
+// bitrev_n and monomial_factor - psi^(s * odd) of one limb through the forward twiddle table - stand in monomial_factor.h
 
 template <typename W, int SV>
 struct VecOf {

@@ -144,16 +144,19 @@ inline size_t held_bytes(const GpuMatrix *m) {
 }
 
 // an output overlaps one of the per-slot operands (`kinds`: arrays of S matrices; the same matrix may stand for several
-// slots): the operands' blocks sorted by start with the furthest end so far, one search per output
-inline std::string slot_operands_overlap(GpuMatrix *const *outs, size_t S, std::initializer_list<const GpuMatrix *const *> kinds) {
+// slots): the operands' blocks sorted by start with the furthest end so far, one search per output.  `more`: `nmore` further
+// operands that do not come one per slot (slot_transfer_eval.hip's terms)
+inline std::string slot_operands_overlap(GpuMatrix *const *outs, size_t S, std::initializer_list<const GpuMatrix *const *> kinds,
+                                         const GpuMatrix *const *more = nullptr, size_t nmore = 0) {
     std::vector<std::pair<const char *, const char *>> blocks;
     std::vector<const GpuMatrix *> given;
+    auto give = [&](const GpuMatrix *m) {
+        given.push_back(m);
+        if (m->storage && m->bytes) blocks.emplace_back(static_cast<const char *>(m->storage), static_cast<const char *>(m->storage) + held_bytes(m));
+    };
     for (size_t s = 0; s < S; ++s)
-        for (const GpuMatrix *const *kind : kinds) {
-            const GpuMatrix *m = kind[s];
-            given.push_back(m);
-            if (m->storage && m->bytes) blocks.emplace_back(static_cast<const char *>(m->storage), static_cast<const char *>(m->storage) + held_bytes(m));
-        }
+        for (const GpuMatrix *const *kind : kinds) give(kind[s]);
+    for (size_t j = 0; j < nmore; ++j) give(more[j]);
     std::sort(given.begin(), given.end());
     std::sort(blocks.begin(), blocks.end());
     for (size_t j = 1; j < blocks.size(); ++j) blocks[j].second = std::max(blocks[j].second, blocks[j - 1].second);

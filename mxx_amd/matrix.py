@@ -2483,6 +2483,68 @@ class GpuDCRTPolyMatrix:
         return GpuDCRTPolyMatrix._lwe_lookup_call("gpupoly_matrix_lwe_lookup_combine", outs, c_bs, k_highs, c_zs, col_start, dst_col, digits.raw)
 
     @staticmethod
+    def _slot_transfer_eval_call(entry: str, outs, c_b0, gate_preimages, b1_preimages, terms_by_out, col_start, dst_col, last) -> list:
+        """`entry(outs, S, dst_col, c_b0, Pg array, P1 array, terms, term offsets, mu words, words per mu, col_start, base,
+        last)`; terms_by_out[s] lists output s's terms (c_in, mid, shift, scalar, mu); `outs` None: S fresh r x chunk-column
+        outputs (dst_col = 0)"""
+        gate_preimages, b1_preimages = list(gate_preimages), list(b1_preimages)
+        terms_by_out = [list(ts) for ts in terms_by_out]
+        count = len(terms_by_out)
+        assert len(gate_preimages) == len(b1_preimages) == count, "slot_transfer_eval: one gate preimage chunk, P1 chunk and term list per output"
+        if outs is None:
+            assert dst_col == 0, "slot_transfer_eval: dst_col needs `outs` to place the block in"
+            outs = [GpuDCRTPolyMatrix(c_b0.params, c_b0.nrow, pg.ncol, c_b0.level, True) for pg in gate_preimages]
+        else:
+            outs = list(outs)
+            assert len(outs) == count, "slot_transfer_eval: one output per term list"
+        if count == 0:
+            return outs
+        flat = [t for ts in terms_by_out for t in ts]
+        terms = (_ffi.GpuSlotTerm * max(len(flat), 1))()
+        for j, (c_in, mid, shift, scalar, _) in enumerate(flat):
+            terms[j].c_in, terms[j].mid = GpuDCRTPolyMatrix._raw_array([c_in, mid])
+            terms[j].shift, terms[j].scalar = int(shift), int(scalar)
+        offsets = (C.c_size_t * (count + 1))()
+        for s, ts in enumerate(terms_by_out):
+            offsets[s + 1] = offsets[s] + len(ts)
+        mu_arr, wpm = GpuDCRTPolyMatrix._int_rows([int(t[4]) for t in flat] or [0])
+        for out in outs:
+            out._touch()
+        st = getattr(_ffi.lib(), entry)(GpuDCRTPolyMatrix._raw_array(outs), count, dst_col, c_b0.raw, GpuDCRTPolyMatrix._raw_array(gate_preimages),
+                                        GpuDCRTPolyMatrix._raw_array(b1_preimages), terms, offsets, mu_arr.ctypes.data_as(C.POINTER(C.c_uint64)), wpm,
+                                        col_start, c_b0.params.base_bits(), last)
+        check_status(st, entry)
+        for out in outs:
+            out.is_ntt = True
+        return outs
+
+    @staticmethod
+    def slot_transfer_eval(outs, c_b0, gate_preimages, b1_preimages, terms_by_out, col_start, key: bytes, tags, hash_name: str = "keccak256",
+                           dst_col: int = 0) -> list:
+        """Stage 2 of the slot-transfer online evaluation for len(terms_by_out) outputs of one gate and the output column chunk
+        [col_start, col_start + c), c = gate_preimages[0].ncol, in one call (gpupoly_matrix_slot_transfer_eval; DESIGN.md
+        section 5y):
+            outs[s][:, dst_col .. dst_col + c) = c_b0 Pg_s + sum_t (kappa_t x^shift_t) o (c_in_t G^-1(A_s[:, chunk]) + mu_t o (mid_t P1_s)),
+        c_b0 r x w0, gate_preimages[s] = Pg_s w0 x c, b1_preimages[s] = P1_s w1 x c, terms_by_out[s] the output's terms as
+        (c_in r x m_g, mid = c_b0 P0_src r x w1, shift, scalar kappa, integer mu), A_s the d x m_g uniform matrix under
+        hash_seed_for_matrix(key, tags[s]); one matrix may serve several outputs or terms.  `outs` None: fresh r x c matrices;
+        otherwise the outputs' r x C matrices, whose columns outside the block keep their contents.  Returns the outputs."""
+        terms_by_out = [list(ts) for ts in terms_by_out]
+        arg, keep, count = hash_tags_arg(key, tags, hash_name)
+        assert count == len(terms_by_out), "slot_transfer_eval: one tag per output"
+        out = GpuDCRTPolyMatrix._slot_transfer_eval_call("gpupoly_matrix_slot_transfer_eval", outs, c_b0, gate_preimages, b1_preimages, terms_by_out,
+                                                         col_start, dst_col, C.byref(arg))
+        del keep
+        return out
+
+    @staticmethod
+    def slot_transfer_eval_combine(outs, c_b0, gate_preimages, b1_preimages, terms_by_out, digits, col_start, dst_col: int = 0) -> list:
+        """Test instrument (gpupoly_matrix_slot_transfer_eval_combine): `slot_transfer_eval` with [D_0 | D_1 | ...] given as
+        the m_g x (outputs * c) EVAL matrix `digits` instead of sampled."""
+        return GpuDCRTPolyMatrix._slot_transfer_eval_call("gpupoly_matrix_slot_transfer_eval_combine", outs, c_b0, gate_preimages, b1_preimages,
+                                                          terms_by_out, col_start, dst_col, digits.raw)
+
+    @staticmethod
     def sample_p1_full_cached_segments(cache: GpuP1CovarianceCache, tp2, seeds, seg_cols) -> "GpuDCRTPolyMatrix":
         """`sample_p1_full_cached` over column segments with a seed each (tp2 is taken to the coefficient domain in place)."""
         out = GpuDCRTPolyMatrix.new_empty(tp2.params, tp2.nrow, tp2.ncol)
