@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import ran
 from conftest import make_params, rand_matrix
 
 pytestmark = pytest.mark.gpu
@@ -198,16 +199,22 @@ def test_both_fast_forms_and_the_general_path_in_one_batch(gpu, oracle, hip_env,
     coeffs = [_signed(rng, (3, 4), n, moduli, mag_one), planted, _signed(rng, (3, 4), n, moduli, mag_two)]
     ms = [_matrix(gpu, p, c, False) for c in coeffs]
     c0 = _lib().gpupoly_launch_count()
-    got = store_many(ms)
+    with ran.launches() as launched:
+        got = store_many(ms)
     launches = _lib().gpupoly_launch_count() - c0
+    if FORCED["test_both_fast_forms_and_the_general_path_in_one_batch"]["pairs"][("MXX_HIP_SERDE", None)](dict(depth=depth)):
+        launched.assert_ran("MXX_HIP_SERDE", None, moduli)
     # one batched width launch + the general width kernel for the flagged matrix, one batched pack launch + its general pack
     assert launches == 2 + 2, f"{launches} launches: the flagged matrix must not take its neighbours off the batched kernels"
     _check_against_one_matrix_entry_and_oracle(oracle, coeffs, ms, got)
     hip_env.set("MXX_HIP_SERDE", "general")
     ms2 = [_matrix(gpu, p, c, False) for c in coeffs]
     c0 = _lib().gpupoly_launch_count()
-    general = store_many(ms2)
+    with ran.launches() as launched:
+        general = store_many(ms2)
     assert _lib().gpupoly_launch_count() - c0 == 2 * 3
+    if FORCED["test_both_fast_forms_and_the_general_path_in_one_batch"]["pairs"][("MXX_HIP_SERDE", "general")](dict(depth=depth)):
+        launched.assert_ran("MXX_HIP_SERDE", "general", moduli)
     hip_env.unset("MXX_HIP_SERDE")
     assert general == got
 
@@ -448,3 +455,12 @@ def test_lookup_buffer_round_trip_of_a_batched_preimage(gpu, oracle):
     # the buffer is the layout of the blobs the one-matrix method gives
     order = sorted(range(5), key=lambda j: indices[j])
     assert data == storage.lookup_buffer_from_blobs(sorted(indices), [xs[j].to_compact_bytes() for j in order])
+
+
+# forced kernel paths (tests/ran.py): a matrix rides the batched kernels up to 16 limbs unless the switch says general
+# (serde.hip: ManyItem::batched); evaluated over the parameter lists by tests/test_ran_table_host.py
+FORCED = {
+    "test_both_fast_forms_and_the_general_path_in_one_batch": {"pairs": {
+        ("MXX_HIP_SERDE", None): lambda c: c["depth"] <= 16,
+        ("MXX_HIP_SERDE", "general"): lambda c: c["depth"] <= 16}},
+}

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import ran
 from conftest import make_params, rand_matrix
 from mxx_amd import _ffi
 from mxx_amd.codeobj import kernel_base
@@ -27,6 +28,103 @@ PARAM_SETS = [
     (256, 3, 51, 17),    # u64 words, config-5 style
     (1024, 5, 51, 17),   # reference norm-test params (u64, tuned kernel)
 ]
+
+
+# ---- forced kernel paths: which cases must show that the forced kernel ran (tests/ran.py) -------------------------------
+# The acceptance conditions of the kernels that may decline, as their launchers state them (`return -1`, or the branch
+# that goes on to the next family).  A case skips the name assertion only where its condition is false.
+def _cls(bits):
+    return "u32" if bits <= 31 else ("u64f" if bits <= 51 else "u64")  # a context has 64-bit words from q >= 2^31
+
+
+def _word_bytes(bits):
+    return 4 if bits <= 31 else 8
+
+
+def _lazy_or_tight(bits):
+    """ctx->lazy_ok || ctx->tight_ok (runtime.hip): seven spare bits in the word, or four in 32-bit words"""
+    return bits + 7 <= 8 * _word_bytes(bits) or (bits <= 31 and bits + 4 <= 32)
+
+
+def _generic_accepts(logn, bits):
+    """launch_ntt_typed (ntt.hip): fits_generic - the vector fits 160 KB of LDS; larger ones go to the per-stage kernels"""
+    return (1 << logn) * _word_bytes(bits) <= 160 * 1024
+
+
+def _f64_accepts(bits):
+    """f64_transforms (ntt_lds_u64.hip) with ctx->f64_ok (runtime.hip): 64-bit words, every modulus at most 51 bits; the
+    tuned launchers are tried at all only with lazy_ok (launch_ntt_typed), which 51 bits in 64-bit words have"""
+    return 32 <= bits <= 51
+
+
+def _fused_digits_accepts(logn, bits):
+    """launch_ntt_digits_u32 / _u64: ntt14_switches (32-bit words: lazy or tight moduli) or lazy_ok (64-bit words), and a
+    ring of the table in ntt_rings.h (visit_ring: 2^10 .. 2^17); DigitLaunch::plan's grid limits are far from these shapes"""
+    ok = _lazy_or_tight(bits) if bits <= 31 else bits + 7 <= 64
+    return ok and 10 <= logn <= 17
+
+
+def _streamed_accepts(c, slots):
+    """launch_matmul_dma_u32 / launch_matmul_dma32_u32 (matmul_dma.hip): 32-bit words, n a multiple of the kernel's slots
+    per workgroup (64 / 32), the inner dimension a non-zero multiple of KC = 4"""
+    inner = c["shape"][1]
+    return c["bits"] <= 31 and c["n"] % slots == 0 and inner >= 4 and inner % 4 == 0
+
+
+def _when(key, value, accepts=lambda c: True):
+    """the pair is used by the cases whose parameter `key` is `value`; there the forced kernel runs where it accepts"""
+    return lambda c: accepts(c) if c[key] == value else None
+
+
+# test -> the (switch, value) pairs it forces -> case (a dict of its parameters and of `fixed`) -> True: the case asserts
+# that the forced kernel ran; False: the kernel declines this case by its own condition; None: the case does not use the
+# pair.  tests/test_ran_table_host.py evaluates this over the tests' parameter lists on the CPU.
+FORCED = {
+    "test_ntt_small_rings": {"pairs": {
+        ("MXX_HIP_NTT64", None): lambda c: True if _f64_accepts(c["bits"]) else None,
+        ("MXX_HIP_NTT64", "int"): lambda c: True if _f64_accepts(c["bits"]) else None,
+        ("MXX_HIP_NTT_PATH", "generic"): lambda c: _generic_accepts(c["logn"], c["bits"])}},
+    "test_ntt_u64_double_precision_kernels": {"pairs": {
+        ("MXX_HIP_NTT64", None): lambda c: _f64_accepts(c["bits"]),
+        ("MXX_HIP_NTT64", "int"): lambda c: _f64_accepts(c["bits"]),
+        ("MXX_HIP_DECOMPOSE_FUSED", None): lambda c: _fused_digits_accepts(c["logn"], c["bits"])}},
+    "test_ntt_alternate_kernels": {"pairs": {
+        ("MXX_HIP_NTT_PATH", "generic"): _when("path", "generic", lambda c: _generic_accepts(c["n"].bit_length() - 1, c["bits"])),
+        ("MXX_HIP_NTT_PATH", "global"): _when("path", "global")}},
+    "test_ntt_n16384_bench_moduli": {"fixed": {"bits": 24}, "pairs": {("MXX_HIP_NTT14", None): lambda c: True}},
+    "test_ntt_n16384_both_kernel_designs": {"fixed": {"bits": 24}, "pairs": {
+        # 24-bit moduli: lazy_ok and signed_ok, and every batch here has an exact grid (ntt14_grid)
+        ("MXX_HIP_NTT14", "grouped"): lambda c: True,
+        ("MXX_HIP_NTT14", "unsigned"): lambda c: True,
+        ("MXX_HIP_NTT14", "whole"): lambda c: True}},
+    "test_matmul_kernel_families": {"fixed": {"bits": 24, "n": 128}, "pairs": {
+        ("MXX_HIP_MATMUL_PATH", "reg"): _when("path", "reg"),
+        ("MXX_HIP_MATMUL_PATH", "lds"): _when("path", "lds", lambda c: c["n"] >= 64 and c["n"] % 64 == 0)}},  # lds_ok (launch_matmul)
+    "test_matmul_dma_kernel": {"fixed": {"n": 128}, "pairs": {
+        ("MXX_HIP_MATMUL_PATH", "dma"): _when("path", "dma", lambda c: _streamed_accepts(c, 64)),
+        ("MXX_HIP_MATMUL_PATH", "wide"): _when("path", "wide", lambda c: _streamed_accepts(c, 32))}},
+    "test_matmul_register_tiles": {"fixed": {"n": 64}, "pairs": {
+        ("MXX_HIP_MATMUL_PATH", "reg"): lambda c: True,
+        ("MXX_HIP_MATMUL_TILE", "RCS[p]"): lambda c: c["n"] >= 4}},  # launch_matmul reads the tile switch from n = 4 on
+    "test_decompose_fused_with_ntt_at_2_14": {"pairs": {
+        ("MXX_HIP_DECOMPOSE_FUSED", None): lambda c: _fused_digits_accepts(14, c["bits"]),
+        ("MXX_HIP_DECOMPOSE_FUSED", "0"): lambda c: True}},
+    "test_decompose_fused_with_ntt_tight_and_split_sizes": {"pairs": {
+        ("MXX_HIP_DECOMPOSE_FUSED", None): lambda c: _fused_digits_accepts(c["logn"], c["bits"]),
+        ("MXX_HIP_DECOMPOSE_FUSED", "0"): lambda c: True}},
+    "test_ntt_28_bit_moduli_tight_lazy_kernels": {"pairs": {
+        ("MXX_HIP_NTT_PATH", "generic"): lambda c: _generic_accepts(c["logn"], c["bits"]) if c["logn"] <= 15 else None,
+        ("MXX_HIP_NTT_PATH", "global"): lambda c: True if c["logn"] > 15 else None,
+        ("MXX_HIP_NTT14", "whole"): lambda c: True if c["logn"] == 14 else None}},
+    "test_ntt_beyond_lds_split_kernels_equal_the_per_stage_path": {"pairs": {
+        ("MXX_HIP_NTT64", None): lambda c: True if _f64_accepts(c["bits"]) else None,
+        ("MXX_HIP_NTT_PATH", "global"): lambda c: True}},
+}
+
+
+def _forced(test, switch, value, **case):
+    e = FORCED[test]
+    return e["pairs"][(switch, value)](dict(e.get("fixed", {}), **case))
 
 
 @pytest.mark.parametrize("n,depth,bits,base", PARAM_SETS)
@@ -83,24 +181,34 @@ def test_ntt_small_rings(gpu, oracle, hip_env, logn, bits):
     x = rand_matrix(oracle, 40 + logn, 3, 7, moduli, n)     # 63 vectors: never a whole number of waves' worth below 64 points
     x[0, 0] = (np.asarray(moduli, dtype=np.uint64) - np.uint64(1)).reshape(-1, 1)
     x[0, 1] = 0
+    case = dict(logn=logn, bits=bits)
     m = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-    m.ntt_all_in_place()
-    ev = oracle.matrix_ntt(x, moduli)
-    assert np.array_equal(m.to_rns(), ev)
-    m.intt_all_in_place()
+    with ran.launches() as k:
+        m.ntt_all_in_place()
+        ev = oracle.matrix_ntt(x, moduli)
+        assert np.array_equal(m.to_rns(), ev)
+        m.intt_all_in_place()
+    if _forced("test_ntt_small_rings", "MXX_HIP_NTT64", None, **case):
+        k.assert_ran("MXX_HIP_NTT64", None, moduli)
     assert np.array_equal(m.to_rns(), x)
     hip_env.set("MXX_HIP_NTT64", "int")
     i64 = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-    i64.ntt_all_in_place()
-    assert np.array_equal(i64.to_rns(), ev)
-    i64.intt_all_in_place()
+    with ran.launches() as k:
+        i64.ntt_all_in_place()
+        assert np.array_equal(i64.to_rns(), ev)
+        i64.intt_all_in_place()
+    if _forced("test_ntt_small_rings", "MXX_HIP_NTT64", "int", **case):
+        k.assert_ran("MXX_HIP_NTT64", "int", moduli)
     assert np.array_equal(i64.to_rns(), x)
     hip_env.unset("MXX_HIP_NTT64")
     hip_env.set("MXX_HIP_NTT_PATH", "generic")
     g = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-    g.ntt_all_in_place()
-    assert np.array_equal(g.to_rns(), ev)
-    g.intt_all_in_place()
+    with ran.launches() as k:
+        g.ntt_all_in_place()
+        assert np.array_equal(g.to_rns(), ev)
+        g.intt_all_in_place()
+    if _forced("test_ntt_small_rings", "MXX_HIP_NTT_PATH", "generic", **case):
+        k.assert_ran("MXX_HIP_NTT_PATH", "generic", moduli, forward=True, inverse=True)
     assert np.array_equal(g.to_rns(), x)
 
 
@@ -128,22 +236,33 @@ def test_ntt_u64_double_precision_kernels(gpu, oracle, hip_env, logn, bits):
     pats.append(spike)
     x = np.concatenate(pats, axis=1)
     want = oracle.matrix_ntt(x, moduli)
+    case, test = dict(logn=logn, bits=bits), "test_ntt_u64_double_precision_kernels"
     m = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-    m.ntt_all_in_place()
-    assert np.array_equal(m.to_rns(), want)
-    m.intt_all_in_place()
-    assert np.array_equal(m.to_rns(), x)
     e = gpu.GpuDCRTPolyMatrix.from_rns(p, x, True)  # the same patterns as evaluation-domain inputs of the inverse
-    e.intt_all_in_place()
+    with ran.launches() as k:
+        m.ntt_all_in_place()
+        assert np.array_equal(m.to_rns(), want)
+        m.intt_all_in_place()
+        assert np.array_equal(m.to_rns(), x)
+        e.intt_all_in_place()
+    if _forced(test, "MXX_HIP_NTT64", None, **case):
+        k.assert_ran("MXX_HIP_NTT64", None, moduli)
     assert np.array_equal(e.to_rns(), oracle.matrix_ntt(x, moduli, inverse=True))
-    dec = gpu.GpuDCRTPolyMatrix.from_rns(p, x[:, :2], False).decompose()
+    src = gpu.GpuDCRTPolyMatrix.from_rns(p, x[:, :2], False)
+    with ran.launches() as k:
+        dec = src.decompose()
+    if _forced(test, "MXX_HIP_DECOMPOSE_FUSED", None, **case):
+        k.assert_ran("MXX_HIP_DECOMPOSE_FUSED", None, moduli)
     want_dec = oracle.matrix_ntt(oracle.decompose(x[:, :2], moduli, 17), moduli)
     assert np.array_equal(dec.to_rns(), want_dec)
     hip_env.set("MXX_HIP_NTT64", "int")
     mi = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-    mi.ntt_all_in_place()
-    assert np.array_equal(mi.to_rns(), want)
-    assert np.array_equal(gpu.GpuDCRTPolyMatrix.from_rns(p, x[:, :2], False).decompose().to_rns(), want_dec)
+    with ran.launches() as k:
+        mi.ntt_all_in_place()
+        assert np.array_equal(mi.to_rns(), want)
+        assert np.array_equal(gpu.GpuDCRTPolyMatrix.from_rns(p, x[:, :2], False).decompose().to_rns(), want_dec)
+    if _forced(test, "MXX_HIP_NTT64", "int", **case):
+        k.assert_ran("MXX_HIP_NTT64", "int", moduli)
 
 
 @pytest.mark.parametrize("path", ["generic", "global"])
@@ -154,9 +273,12 @@ def test_ntt_alternate_kernels(gpu, oracle, hip_env, path, n, depth, bits, base)
     x = rand_matrix(oracle, 3, 1, 3, moduli, n)
     hip_env.set("MXX_HIP_NTT_PATH", path)
     m = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-    m.ntt_all_in_place()
-    assert np.array_equal(m.to_rns(), oracle.matrix_ntt(x, moduli))
-    m.intt_all_in_place()
+    with ran.launches() as k:
+        m.ntt_all_in_place()
+        assert np.array_equal(m.to_rns(), oracle.matrix_ntt(x, moduli))
+        m.intt_all_in_place()
+    if _forced("test_ntt_alternate_kernels", "MXX_HIP_NTT_PATH", path, path=path, n=n, bits=bits):
+        k.assert_ran("MXX_HIP_NTT_PATH", path, moduli, forward=True, inverse=True)
     assert np.array_equal(m.to_rns(), x)
 
 
@@ -167,9 +289,12 @@ def test_ntt_n16384_bench_moduli(gpu, oracle):
     moduli = p.moduli()
     x = rand_matrix(oracle, 4, 1, 2, moduli, n)
     m = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-    m.ntt_all_in_place()
-    assert np.array_equal(m.to_rns(), oracle.matrix_ntt(x, moduli))
-    m.intt_all_in_place()
+    with ran.launches() as k:
+        m.ntt_all_in_place()
+        assert np.array_equal(m.to_rns(), oracle.matrix_ntt(x, moduli))
+        m.intt_all_in_place()
+    if _forced("test_ntt_n16384_bench_moduli", "MXX_HIP_NTT14", None):  # the default at this ring: the grouped kernels
+        k.assert_ran("MXX_HIP_NTT14", None, moduli, forward=True, inverse=True)
     assert np.array_equal(m.to_rns(), x)
 
 
@@ -184,9 +309,12 @@ def test_ntt_n16384_both_kernel_designs(gpu, oracle, hip_env):
     for design in ("grouped", "unsigned", "whole"):
         hip_env.set("MXX_HIP_NTT14", design)
         m = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-        m.ntt_all_in_place()
-        assert np.array_equal(m.to_rns(), want), design
-        m.intt_all_in_place()
+        with ran.launches() as k:
+            m.ntt_all_in_place()
+            assert np.array_equal(m.to_rns(), want), design
+            m.intt_all_in_place()
+        if _forced("test_ntt_n16384_both_kernel_designs", "MXX_HIP_NTT14", design):
+            k.assert_ran("MXX_HIP_NTT14", design, moduli, forward=True, inverse=True)
         assert np.array_equal(m.to_rns(), x), design
 
 
@@ -282,6 +410,8 @@ def test_matmul_kernel_families(gpu, oracle, hip_env, path, shape):
     gb = gpu.GpuDCRTPolyMatrix.from_rns(p, b, True)
     hip_env.set("MXX_HIP_MATMUL_PATH", path)
     assert np.array_equal((ga * gb).to_rns(), oracle.matmul(a, b, moduli))
+    if _forced("test_matmul_kernel_families", "MXX_HIP_MATMUL_PATH", path, path=path, shape=shape):
+        assert p.ctx().last_kernel().startswith(ran.TABLE[("MXX_HIP_MATMUL_PATH", path)]["u32"].last), (path, p.ctx().last_kernel())
 
 
 @pytest.mark.parametrize("shape", [(32, 8, 16), (33, 12, 17), (64, 64, 64), (16, 4, 8), (40, 36, 5), (3, 16, 70), (32, 4, 32), (65, 20, 33)])
@@ -302,6 +432,8 @@ def test_matmul_dma_kernel(gpu, oracle, hip_env, shape, bits, path):
     gb = gpu.GpuDCRTPolyMatrix.from_rns(p, b, True)
     hip_env.set("MXX_HIP_MATMUL_PATH", path)
     assert np.array_equal((ga * gb).to_rns(), oracle.matmul(a, b, moduli))
+    if _forced("test_matmul_dma_kernel", "MXX_HIP_MATMUL_PATH", path, path=path, shape=shape, bits=bits):
+        assert p.ctx().last_kernel().startswith(ran.TABLE[("MXX_HIP_MATMUL_PATH", path)]["u32"].last), (path, p.ctx().last_kernel())
 
 
 @pytest.mark.parametrize("tile", ["184", "184p", "144", "144p", "284", "284p", "244", "244p", "344", "344p", "444", "444p", "382", "382p", "481", "481p", "881", "881p", "482", "482p"])
@@ -322,6 +454,14 @@ def test_matmul_register_tiles(gpu, oracle, hip_env, tile, bits):
         ga = gpu.GpuDCRTPolyMatrix.from_rns(p, a, True)
         gb = gpu.GpuDCRTPolyMatrix.from_rns(p, b, True)
         assert np.array_equal((ga * gb).to_rns(), oracle.matmul(a, b, moduli)), (tile, r, k, c)
+        if _forced("test_matmul_register_tiles", "MXX_HIP_MATMUL_TILE", "RCS[p]", tile=tile, bits=bits):
+            # the label of launch_matmul_cfg: matmul_kernel<u32,rows,cols,slots[,loads-ahead][,nt][,packed24 ...]>
+            label = p.ctx().last_kernel()
+            head = ran.TABLE[("MXX_HIP_MATMUL_TILE", "RCS[p]")]["u32"].last + f",{tile[0]},{tile[1]},{tile[2]}"
+            assert label.startswith(head), (tile, label)
+            rest = label[len(head):]
+            assert rest.startswith(",loads-ahead") == tile.endswith("p"), (tile, label)
+            assert rest.replace(",loads-ahead", "", 1).startswith((">", ",nt", ",packed24")), (tile, label)
 
 
 @pytest.mark.parametrize("shape", [(3, 5, 9), (3, 8, 4), (4, 7, 8), (4, 64, 17), (2, 33, 16), (1, 31, 15)])
@@ -434,12 +574,27 @@ def test_decompose_fused_with_ntt_at_2_14(gpu, oracle, hip_env, depth, bits, bas
     M = rand_matrix(oracle, 41, 2, 2, moduli, n)
     gm = gpu.GpuDCRTPolyMatrix.from_rns(p, M, False)
     want = oracle.matrix_ntt(oracle.decompose(M, moduli, base), moduli)
-    fused = gm.decompose()
+    test = "test_decompose_fused_with_ntt_at_2_14"
+    with ran.launches() as k:
+        fused = gm.decompose()
+    if _forced(test, "MXX_HIP_DECOMPOSE_FUSED", None, bits=bits):
+        k.assert_ran("MXX_HIP_DECOMPOSE_FUSED", None, moduli)
     assert fused.is_ntt and np.array_equal(fused.to_rns(), want)
     assert gm.ensure_eval().decompose() == fused  # EVAL source: private INTT copy feeds the fused kernel
-    small = gm.small_decompose()
+    with ran.launches() as k:
+        small = gm.small_decompose()
+    if _forced(test, "MXX_HIP_DECOMPOSE_FUSED", None, bits=bits):
+        k.assert_ran("MXX_HIP_DECOMPOSE_FUSED", None, moduli)
     assert np.array_equal(small.to_rns(), oracle.matrix_ntt(oracle.decompose(M, moduli, base, small=True), moduli))
     hip_env.set("MXX_HIP_DECOMPOSE_FUSED", "0")
+    with ran.launches() as k:
+        plain = gm.decompose()
+    with ran.launches() as k_small:
+        plain_small = gm.small_decompose()
+    if _forced(test, "MXX_HIP_DECOMPOSE_FUSED", "0", bits=bits):
+        k.assert_ran("MXX_HIP_DECOMPOSE_FUSED", "0", moduli)
+        k_small.assert_ran("MXX_HIP_DECOMPOSE_FUSED", "0", moduli)
+    assert plain == fused and plain_small == small
     assert gm.decompose() == fused and gm.small_decompose() == small
     G = gpu.GpuDCRTPolyMatrix.gadget_matrix(p, 2)
     assert G * fused == gm.ensure_eval()
@@ -475,16 +630,29 @@ def test_decompose_fused_with_ntt_tight_and_split_sizes(gpu, oracle, hip_env, lo
     _ffi.trace_begin()
     fused = gm.decompose()
     gpu.gpu_device_sync()
-    ran = [kernel_base(t["kernel"]) for t in _ffi.trace_end()]
+    launched = [kernel_base(t["kernel"]) for t in _ffi.trace_end()]
     # the two-step fallback gives the same bits, so the values below cannot tell whether the fused launcher ran
-    assert "decompose_kernel" not in ran and "decompose_rows_kernel" not in ran, ran
+    assert "decompose_kernel" not in launched and "decompose_rows_kernel" not in launched, launched
     family = _fused_decompose_family(logn, bits)
-    assert [k for k in ran if k in family] == family, (family, ran)
+    assert [k for k in launched if k in family] == family, (family, launched)
     assert fused.is_ntt and np.array_equal(fused.to_rns(), want)
     assert gm.ensure_eval().decompose() == fused
     small = gm.small_decompose()
     assert np.array_equal(small.to_rns(), oracle.matrix_ntt(oracle.decompose(M, moduli, base, small=True), moduli))
+    test, case = "test_decompose_fused_with_ntt_tight_and_split_sizes", dict(logn=logn, bits=bits)
+    if _forced(test, "MXX_HIP_DECOMPOSE_FUSED", None, **case):
+        with ran.launches() as k:
+            assert gm.decompose() == fused
+        k.assert_ran("MXX_HIP_DECOMPOSE_FUSED", None, moduli)
     hip_env.set("MXX_HIP_DECOMPOSE_FUSED", "0")
+    with ran.launches() as k:
+        plain = gm.decompose()
+    with ran.launches() as k_small:
+        plain_small = gm.small_decompose()
+    if _forced(test, "MXX_HIP_DECOMPOSE_FUSED", "0", **case):
+        k.assert_ran("MXX_HIP_DECOMPOSE_FUSED", "0", moduli)
+        k_small.assert_ran("MXX_HIP_DECOMPOSE_FUSED", "0", moduli)
+    assert plain == fused and plain_small == small
     assert gm.decompose() == fused and gm.small_decompose() == small
     hip_env.unset("MXX_HIP_DECOMPOSE_FUSED")
     assert gpu.GpuDCRTPolyMatrix.gadget_matrix(p, 1) * fused == gm.ensure_eval()
@@ -738,17 +906,25 @@ def test_ntt_28_bit_moduli_tight_lazy_kernels(gpu, oracle, hip_env, logn, bits):
     e = gpu.GpuDCRTPolyMatrix.from_rns(p, x, True)  # the same patterns as evaluation-domain inputs of the inverse
     e.intt_all_in_place()
     assert np.array_equal(e.to_rns(), oracle.matrix_ntt(x, moduli, inverse=True))
-    hip_env.set("MXX_HIP_NTT_PATH", "global" if logn > 15 else "generic")
+    test, case = "test_ntt_28_bit_moduli_tight_lazy_kernels", dict(logn=logn, bits=bits)
+    path = "global" if logn > 15 else "generic"
+    hip_env.set("MXX_HIP_NTT_PATH", path)
     g = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-    g.ntt_all_in_place()
+    with ran.launches() as k:
+        g.ntt_all_in_place()
+    if _forced(test, "MXX_HIP_NTT_PATH", path, **case):
+        k.assert_ran("MXX_HIP_NTT_PATH", path, moduli, forward=True)
     assert np.array_equal(g.to_rns(), want)
     hip_env.unset("MXX_HIP_NTT_PATH")
     if logn == 14:
         hip_env.set("MXX_HIP_NTT14", "whole")
         w = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-        w.ntt_all_in_place()
-        assert np.array_equal(w.to_rns(), want)
-        w.intt_all_in_place()
+        with ran.launches() as k:
+            w.ntt_all_in_place()
+            assert np.array_equal(w.to_rns(), want)
+            w.intt_all_in_place()
+        if _forced(test, "MXX_HIP_NTT14", "whole", **case):
+            k.assert_ran("MXX_HIP_NTT14", "whole", moduli, forward=True, inverse=True)
         assert np.array_equal(w.to_rns(), x)
 
 
@@ -791,15 +967,24 @@ def test_ntt_beyond_lds_split_kernels_equal_the_per_stage_path(gpu, oracle, hip_
     x[0, 0, :, :4] = 0
     x[1, 0, :, -4:] = (np.asarray(moduli, dtype=np.uint64) - np.uint64(1)).reshape(-1, 1)
     want = oracle.matrix_ntt(x, moduli)
+    test, case = "test_ntt_beyond_lds_split_kernels_equal_the_per_stage_path", dict(logn=logn, bits=bits)
     m = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-    m.ntt_all_in_place()
+    with ran.launches() as k_fwd:
+        m.ntt_all_in_place()
     assert np.array_equal(m.to_rns(), want)
     hip_env.set("MXX_HIP_NTT_PATH", "global")
     g = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-    g.ntt_all_in_place()
-    assert g == m
-    g.intt_all_in_place()
+    with ran.launches() as k:
+        g.ntt_all_in_place()
+        assert g == m
+        g.intt_all_in_place()
+    if _forced(test, "MXX_HIP_NTT_PATH", "global", **case):
+        k.assert_ran("MXX_HIP_NTT_PATH", "global", moduli, forward=True, inverse=True)
     assert np.array_equal(g.to_rns(), x)
     hip_env.unset("MXX_HIP_NTT_PATH")
-    m.intt_all_in_place()
+    with ran.launches() as k_inv:
+        m.intt_all_in_place()
+    if _forced(test, "MXX_HIP_NTT64", None, **case):  # 51 bits: the split double-precision kernels, not the integer ones
+        k_fwd.assert_ran("MXX_HIP_NTT64", None, moduli)
+        k_inv.assert_ran("MXX_HIP_NTT64", None, moduli)
     assert np.array_equal(m.to_rns(), x)

@@ -33,6 +33,7 @@ import numpy as np
 import pytest
 
 import plainref as P
+import ran
 from test_gpu_modulus_classes import MAX_INNER, SEED, _lazy_terms, _moduli, _params, _patterns, _root
 
 pytestmark = pytest.mark.gpu
@@ -202,8 +203,13 @@ def test_mul_sum(gpu, hip_env, cell):
     run(9, "separate", True, True)  # above 8 rows: products into scratch, one combine pass per term
     run(9, "none", False, False)
     hip_env.set("MXX_HIP_MUL_SUM_PATH", "tile")  # two row tiles of the term-table kernel
-    run(9, "out", False, True)
-    run(9, "separate", True, False)
+    with ran.launches() as launched:
+        run(9, "out", False, True)
+    with ran.launches() as launched_again:
+        run(9, "separate", True, False)
+    if FORCED["test_mul_sum"]["pairs"][("MXX_HIP_MUL_SUM_PATH", "tile")](dict(cell=cell)):
+        launched.assert_ran("MXX_HIP_MUL_SUM_PATH", "tile", moduli)
+        launched_again.assert_ran("MXX_HIP_MUL_SUM_PATH", "tile", moduli)
     hip_env.unset("MXX_HIP_MUL_SUM_PATH")
 
     # the in-place forms
@@ -578,3 +584,11 @@ def test_mul_decompose_many_large_u64_tile(gpu):
     for out, extra in zip(outs, ((q - 3) * (q - 1) % q, 0)):
         got = out.to_rns()
         assert got.shape == (BIG_ROWS // 2, BIG_COLS, 1, BIG_N) and (got == np.uint64((prod + extra) % q)).all()
+
+
+# forced kernel paths (tests/ran.py): gpupoly_matrix_mul_sum keeps the term-table kernel at every height under the
+# switch, with no condition of its own; evaluated over the parameter lists by tests/test_ran_table_host.py
+FORCED = {
+    "test_mul_sum": {"cls": lambda c: ran.Launched.word_class(_cell(c["cell"])[1]), "pairs": {
+        ("MXX_HIP_MUL_SUM_PATH", "tile"): lambda c: True}},
+}

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import plainref as P
+import ran
 from conftest import is_prime
 from mxx_amd.matrix import _bincode_read_varint
 
@@ -113,7 +114,8 @@ def _check_transform(gpu, hip_env, n, moduli, x, paths, u64_limbs=4):
     limbs = list(range(len(moduli))) if not wide else list(range(min(u64_limbs, len(moduli))))
     slots = _slots(n)
     m = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-    m.ntt_all_in_place()
+    with ran.launches() as k_default:
+        m.ntt_all_in_place()
     fwd = m.to_rns()
     want = _forward_ref(x, moduli, slots, limbs)
     got = fwd[0][:, limbs][:, :, slots]
@@ -121,17 +123,25 @@ def _check_transform(gpu, hip_env, n, moduli, x, paths, u64_limbs=4):
     m.intt_all_in_place()
     assert np.array_equal(m.to_rns(), x), "round trip"
     e = gpu.GpuDCRTPolyMatrix.from_rns(p, x, True)
-    e.intt_all_in_place()
+    with ran.launches() as k_default_inv:
+        e.intt_all_in_place()
+    if _path_runs(("MXX_HIP_NTT64", None), n, moduli):  # the default of this class is the double-precision family
+        k_default.assert_ran("MXX_HIP_NTT64", None, moduli)
+        k_default_inv.assert_ran("MXX_HIP_NTT64", None, moduli)
     inv = e.to_rns()
     back = _forward_ref(inv, moduli, slots, limbs)
     assert np.array_equal(back, x[0][:, limbs][:, :, slots]), "inverse transform: forward definition of its output"
     for name, value in paths:
         hip_env.set(name, value)
         f = gpu.GpuDCRTPolyMatrix.from_rns(p, x, False)
-        f.ntt_all_in_place()
-        assert np.array_equal(f.to_rns(), fwd), (name, value, "forward")
         g = gpu.GpuDCRTPolyMatrix.from_rns(p, x, True)
-        g.intt_all_in_place()
+        with ran.launches() as k:
+            f.ntt_all_in_place()
+            g.intt_all_in_place()
+        # the equal values below cannot tell a forced kernel from the default one it may have fallen back to
+        if _path_runs((name, value), n, moduli):
+            k.assert_ran(name, value, moduli, forward=True, inverse=True)
+        assert np.array_equal(f.to_rns(), fwd), (name, value, "forward")
         assert np.array_equal(g.to_rns(), inv), (name, value, "inverse")
         hip_env.unset(name)
 
@@ -141,6 +151,29 @@ def _forced_paths(moduli):
     if max(moduli) >> 31 and max(moduli).bit_length() <= 51:
         paths.append(("MXX_HIP_NTT64", "int"))
     return paths
+
+
+def _path_runs(pair, n, moduli):
+    """Does the kernel family that `pair` forces accept this ring?  None: the pair does not apply to these moduli.
+    generic: launch_ntt_typed (ntt.hip) sends a vector beyond 160 KB of LDS to the per-stage kernels instead; global:
+    always; the double-precision transforms and their integer counterpart: 64-bit words with every modulus at most 51
+    bits (f64_transforms, ntt_lds_u64.hip)."""
+    wide = max(moduli) >> 31 != 0
+    if pair == ("MXX_HIP_NTT_PATH", "generic"):
+        return n * (8 if wide else 4) <= 160 * 1024
+    if pair == ("MXX_HIP_NTT_PATH", "global"):
+        return True
+    if pair[0] == "MXX_HIP_NTT64":
+        return True if wide and max(moduli).bit_length() <= 51 else None
+    raise KeyError(pair)
+
+
+def _fused_digits_accept(n, moduli):
+    """launch_ntt_digits_u32 / _u64: lazy or tight moduli in 32-bit words (ntt14_switches), lazy ones in 64-bit words, and
+    a ring of the table in ntt_rings.h (2^10 .. 2^17 points)"""
+    bits = max(moduli).bit_length()
+    ok = bits + 7 <= 64 if max(moduli) >> 31 else bits + 4 <= 32
+    return ok and 1 << 10 <= n <= 1 << 17
 
 
 @pytest.mark.parametrize("bits,n", TRANSFORM_CELLS)
@@ -161,10 +194,17 @@ def test_transform_reference_sets(gpu, hip_env, n, depth, bits):
     _check_transform(gpu, hip_env, n, moduli, x, [("MXX_HIP_NTT_PATH", "global")], u64_limbs=depth)
 
 
+MIXED_WIDTHS = [(64, (24, 12)), (1 << 14, (51, 33))]  # (n, (bits of the widest limb, bits of a narrow one))
+
+
+def _mixed_moduli(n, widths):
+    return [P.primes(n, widths[0], 1)[0], P.primes(n, widths[1], 1, low=True)[0]]
+
+
 def test_transform_mixed_widths(gpu, hip_env):
     """The ABI accepts mixed widths; the kernels then pick their forms by the widest limb."""
-    for n, moduli in ((64, [P.primes(64, 24, 1)[0], P.primes(64, 12, 1, low=True)[0]]),
-                      (1 << 14, [P.primes(1 << 14, 51, 1)[0], P.primes(1 << 14, 33, 1, low=True)[0]])):
+    for n, widths in MIXED_WIDTHS:
+        moduli = _mixed_moduli(n, widths)
         x = _patterns(moduli, n, SEED + n)
         _check_transform(gpu, hip_env, n, moduli, x, _forced_paths(moduli))
 
@@ -331,13 +371,19 @@ def test_decompose(gpu, hip_env, n, spec, base):
     want = np.concatenate([P.digits(rows[r], moduli, base, dpt)[:, None] for r in range(rows.shape[0])])
     G = gpu.GpuDCRTPolyMatrix.gadget_matrix(p, rows.shape[0])
     assert np.array_equal(gpu.GpuDCRTPolyMatrix.gadget_matrix(p, 2).to_coeff_rns(), P.gadget(2, moduli, base, n))
-    for fused in ("1", "0"):
-        hip_env.set("MXX_HIP_DECOMPOSE_FUSED", fused)
+    for fused in (None, "1", "0"):  # unset: the fused form is the default
+        if fused is None:
+            hip_env.unset("MXX_HIP_DECOMPOSE_FUSED")
+        else:
+            hip_env.set("MXX_HIP_DECOMPOSE_FUSED", fused)
         for eval_in in (False, True):
             src = gpu.GpuDCRTPolyMatrix.from_rns(p, M, False)
             if eval_in:
                 src = src.ensure_eval()
-            dec = src.decompose()
+            with ran.launches() as launched:
+                dec = src.decompose()
+            if fused == "0" or _fused_digits_accept(n, moduli):
+                launched.assert_ran("MXX_HIP_DECOMPOSE_FUSED", fused, moduli)
             assert dec.size() == (rows.shape[0] * k, 1)
             assert np.array_equal(dec.to_coeff_rns(), want), (fused, eval_in)
             assert G * dec == gpu.GpuDCRTPolyMatrix.from_rns(p, M, False).ensure_eval(), "G G^-1(M) != M"
@@ -385,7 +431,10 @@ def test_compact_bytes_coeffs_and_modulus_switch(gpu, hip_env, mode, n, bits, de
         centred = [P.centred_crt(res[0, c, :, i], moduli) for c in range(2) for i in range(n)]
         assert centred == vals
         m = gpu.GpuDCRTPolyMatrix.from_rns(p, res, False)
-        data = m.to_compact_bytes()
+        with ran.launches() as launched:
+            data = m.to_compact_bytes()
+        if depth <= 16:  # the store tries its fast kernels up to 16 limbs (serde.hip), unless the switch says general
+            launched.assert_ran("MXX_HIP_SERDE", mode, moduli)
         pos = 2
         for _ in range(3):  # level, nrow, ncol
             _, pos = _bincode_read_varint(data, pos)
@@ -490,3 +539,44 @@ def test_modulus_of_63_bits_is_refused_through_the_abi(gpu):
         gpu.GpuDCRTPolyParams(4, [q], 1)
     with pytest.raises(GpuPolyError, match=r"modulus must be < 2\^62"):
         gpu.GpuDCRTPolyParams(4, [P.primes(4, 61, 1)[0], q], 1)  # one such limb in an otherwise valid basis
+
+
+# ---------------------------------------------------------------------------------------------- forced kernel paths
+def _transform_pairs(moduli_of):
+    """the pairs _check_transform asserts for a case, by the same predicate (_path_runs)"""
+    def pair_fn(pair):
+        def f(c):
+            moduli = moduli_of(c)
+            if pair[1] is not None and pair not in c.get("paths", _forced_paths(moduli)):
+                return None
+            return _path_runs(pair, c["n"], moduli)
+        return f
+    return {pair: pair_fn(pair) for pair in (("MXX_HIP_NTT_PATH", "generic"), ("MXX_HIP_NTT_PATH", "global"),
+                                             ("MXX_HIP_NTT64", "int"), ("MXX_HIP_NTT64", None))}
+
+
+def _class_of(moduli_of):
+    return lambda c: ran.Launched.word_class(moduli_of(c))
+
+
+_EDGE = lambda c: _moduli(c["n"], c["bits"])  # noqa: E731
+_REFSET = lambda c: P.primes(c["n"], c["bits"], 2)  # noqa: E731 - the class of the set; its depth does not matter here
+_MIXED = lambda c: _mixed_moduli(c["n"], c["widths"])  # noqa: E731
+_CELL = lambda c: _cell_moduli(c["n"], c["spec"])  # noqa: E731
+
+# test -> pairs -> case -> True (asserts that the forced kernel ran) / False (the kernel declines the case) / None (the
+# case does not use the pair); evaluated over the parameter lists by tests/test_ran_table_host.py
+FORCED = {
+    "test_transform_edge_primes": {"cls": _class_of(_EDGE), "pairs": _transform_pairs(_EDGE)},
+    "test_transform_reference_sets": {"cls": _class_of(_REFSET), "fixed": {"paths": [("MXX_HIP_NTT_PATH", "global")]},
+                                      "pairs": _transform_pairs(_REFSET)},
+    "test_transform_mixed_widths": {"cls": _class_of(_MIXED), "cases": [dict(n=n, widths=w) for n, w in MIXED_WIDTHS],
+                                    "pairs": _transform_pairs(_MIXED)},
+    "test_decompose": {"cls": _class_of(_CELL), "pairs": {
+        ("MXX_HIP_DECOMPOSE_FUSED", None): lambda c: _fused_digits_accept(c["n"], _CELL(c)),
+        ("MXX_HIP_DECOMPOSE_FUSED", "1"): lambda c: _fused_digits_accept(c["n"], _CELL(c)),
+        ("MXX_HIP_DECOMPOSE_FUSED", "0"): lambda c: True}},
+    "test_compact_bytes_coeffs_and_modulus_switch": {"pairs": {
+        ("MXX_HIP_SERDE", None): lambda c: c["depth"] <= 16 if c["mode"] is None else None,
+        ("MXX_HIP_SERDE", "general"): lambda c: c["depth"] <= 16 if c["mode"] == "general" else None}},
+}

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import plainref as PR
+import ran
 from conftest import make_params
 
 pytestmark = pytest.mark.gpu
@@ -203,7 +204,11 @@ def test_nine_rows_placed_and_negated(gpu, oracle, ring, ks_id):
 def test_nine_rows_through_the_term_table_kernel(gpu, oracle, hip_env, ring, ks_id):
     """two row tiles of the 8-row tile: the switch keeps the term-table kernel above 8 rows"""
     hip_env.set("MXX_HIP_MUL_SUM_PATH", "tile")
-    run_case(gpu, oracle, ring, rows=9, ks_id=ks_id, placed=True, addend="out")
+    with ran.launches() as launched:
+        run_case(gpu, oracle, ring, rows=9, ks_id=ks_id, placed=True, addend="out")
+    if FORCED["test_nine_rows_through_the_term_table_kernel"]["pairs"][("MXX_HIP_MUL_SUM_PATH", "tile")](dict(ring=ring)):
+        # the values cannot tell: above 8 rows the default is products into scratch and one combine pass per term
+        launched.assert_ran("MXX_HIP_MUL_SUM_PATH", "tile", pool(gpu, oracle, ring)["moduli"])
 
 
 def test_a_level_below_the_top(gpu, oracle):
@@ -450,3 +455,11 @@ def test_mirror(gpu, oracle):
     assert out.is_ntt and out.size() == (rows, cols) and out == l_ * r_
     assert M.mul_sum([l_], [r_], negate=True) == -(l_ * r_)
     assert M.mul_sum([], [], addend=a) == a
+
+
+# forced kernel paths (tests/ran.py): gpupoly_matrix_mul_sum keeps the term-table kernel at every height under the
+# switch, with no condition of its own; evaluated over the parameter lists by tests/test_ran_table_host.py
+FORCED = {
+    "test_nine_rows_through_the_term_table_kernel": {"cls": lambda c: ran.Launched.word_class([1 << (RINGS[c["ring"]][2] - 1)]), "pairs": {
+        ("MXX_HIP_MUL_SUM_PATH", "tile"): lambda c: True}},
+}

@@ -4,6 +4,7 @@ import os
 import numpy as np
 import pytest
 
+import ran
 from conftest import make_params, rand_matrix
 
 pytestmark = pytest.mark.gpu
@@ -132,7 +133,11 @@ def test_compact_store_fast_forms_equal_the_general_kernels_and_the_oracle(gpu, 
         if mode == "general":
             hip_env.set("MXX_HIP_SERDE", "general")
         m = gpu.GpuDCRTPolyMatrix.from_rns(p, coeff, False)
-        blob = m.to_compact_bytes()
+        with ran.launches() as launched:
+            blob = m.to_compact_bytes()
+        value = None if mode == "fast" else "general"
+        if _forced("MXX_HIP_SERDE", value, depth=depth, bits=bits):
+            launched.assert_ran("MXX_HIP_SERDE", value, moduli)
         _, _, _, _, _, max_bits, bpc, payload = _payload_of(blob)
         assert (max_bits, bpc) == (want_bits, want_bpc) and payload == want_payload, mode
         assert gpu.GpuDCRTPolyMatrix.from_compact_bytes(p, blob) == m
@@ -172,3 +177,16 @@ def test_compact_view_is_the_same_bytes_without_a_host_copy(gpu, oracle):
     assert gpu.GpuDCRTPolyMatrix.from_compact_bytes(p, blob) == u
     assert _payload_of(blob)[7] == oracle.compact_payload(uni, moduli)[0]
     assert M._pinned_capacity() >= max(before, len(blob))
+
+
+# forced kernel paths (tests/ran.py): the store tries its fast kernels up to 16 limbs (serde.hip: `fast`), and the switch
+# keeps it off them; evaluated over the parameter lists by tests/test_ran_table_host.py
+FORCED = {
+    "test_compact_store_fast_forms_equal_the_general_kernels_and_the_oracle": {"pairs": {
+        ("MXX_HIP_SERDE", None): lambda c: c["depth"] <= 16,
+        ("MXX_HIP_SERDE", "general"): lambda c: c["depth"] <= 16}},
+}
+
+
+def _forced(switch, value, **case):
+    return FORCED["test_compact_store_fast_forms_equal_the_general_kernels_and_the_oracle"]["pairs"][(switch, value)](case)

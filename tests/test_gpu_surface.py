@@ -5,9 +5,80 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from conftest import make_params, rand_matrix
+import ran
+from conftest import is_prime, make_params, rand_matrix
 
 pytestmark = pytest.mark.gpu
+
+# ---- forced kernel paths: the acceptance conditions of the kernels that may decline, read from their launchers ----------
+MFMA_MAX_Q = 16711424  # mmfma::MAX_Q (matmul_mfma.hip): (q - 1) / 2 + 0x808080 < 2^24
+
+
+def _mfma_accepts(moduli, n, inner):
+    """launch_matmul_mfma_u32: 32-bit words, n a multiple of 16 slots, 0 < inner <= 128, every modulus in [256, MAX_Q) and
+    its epilogue bound 2 Kpad h^2 + 2 q < 2^(31 + bits(q)), h = (q - 1) / 2 + 1, Kpad = inner rounded up to 32"""
+    if max(moduli) >> 31 or n % 16 or not 0 < inner <= 128:
+        return False
+    kpad = -(-inner // 32) * 32
+    return all(256 <= q < MFMA_MAX_Q and 2 * kpad * ((q - 1) // 2 + 1) ** 2 + 2 * q < 1 << (31 + q.bit_length()) for q in moduli)
+
+
+def _streamed_accepts(n, inner, slots):
+    """launch_matmul_dma_u32 (64 slots) / launch_matmul_dma32_u32 (32): n a multiple of the slots, inner a multiple of 4"""
+    return n % slots == 0 and inner >= 4 and inner % 4 == 0
+
+
+def _mfma_moduli(oracle, n, bits):
+    """the test's basis; "below MAX_Q": the two largest primes = 1 (mod 2n) that the matrix-core kernel still takes"""
+    if bits != "below MAX_Q":
+        return oracle.gen_crt_basis(n, 2, bits)
+    out, q = [], MFMA_MAX_Q - 1 - (MFMA_MAX_Q - 2) % (2 * n)
+    while len(out) < 2:
+        if is_prime(q):
+            out.append(q)
+        q -= 2 * n
+    return out
+
+
+def _oracle():
+    from oracle import oracle as O
+
+    return O
+
+
+def _ntt14_accepts(c):
+    """launch_mul_intt_u32 (ntt_lds_u32.hip) at 2^14 points: the grouped kernels take lazy moduli only (ntt14_grouped
+    without the tight forms: at most 25 bits), their signed inverse at most 24 bits (ntt14_signed); whole: any modulus
+    with a tuned kernel.  The switch is read at this ring alone."""
+    if c["n"] != 16384:
+        return None
+    return {"grouped": c["bits"] <= 24, "unsigned": c["bits"] <= 25, "whole": c["bits"] <= 28}[c["design"]]
+
+
+FORCED = {
+    "test_mul_scalar_intt_fused": {"pairs": {("MXX_HIP_NTT14", d): (lambda c, d=d: _ntt14_accepts(c) if c["design"] == d else None)
+                                             for d in ("grouped", "unsigned", "whole")}},
+    "test_matmul_mfma_kernel": {"fixed": {"n": 128}, "cls": lambda c: "u32", "pairs": {
+        ("MXX_HIP_MATMUL_PATH", "mfma"): lambda c: _mfma_accepts(_mfma_moduli(_oracle(), c["n"], c["bits"]), c["n"], c["shape"][1])}},
+    "test_matmul_mfma_equals_valu_at_full_size": {"fixed": {"n": 16384, "bits": 24, "inner": 64}, "pairs": {
+        ("MXX_HIP_MATMUL_PATH", "dma"): lambda c: _streamed_accepts(c["n"], c["inner"], 64),
+        ("MXX_HIP_MATMUL_PATH", "wide"): lambda c: _streamed_accepts(c["n"], c["inner"], 32),
+        ("MXX_HIP_MATMUL_PATH", "mfma"): lambda c: _mfma_accepts(_oracle().gen_crt_basis(c["n"], 8, c["bits"]), c["n"], c["inner"])}},
+    "test_matmul_lazy_window_worst_case_both_operands": {"fixed": {"n": 128, "bits": 31, "inner": 96}, "pairs": {
+        ("MXX_HIP_MATMUL_PATH", "reg"): lambda c: True if c["path"] == "reg" else None,
+        ("MXX_HIP_MATMUL_PATH", "lds"): lambda c: c["n"] % 64 == 0 if c["path"] == "lds" else None,
+        ("MXX_HIP_MATMUL_PATH", "dma"): lambda c: _streamed_accepts(c["n"], c["inner"], 64) if c["path"] == "dma" else None}},
+}
+
+
+def _forced(test, switch, value, **case):
+    e = FORCED[test]
+    return e["pairs"][(switch, value)](dict(e.get("fixed", {}), **case))
+
+
+def _assert_product_kernel(p, path):
+    ran_kernel = p.ctx().last_kernel()
+    assert ran_kernel.startswith(ran.TABLE[("MXX_HIP_MATMUL_PATH", path)]["u32"].last), (path, ran_kernel)
 
 
 def _seed(gpu, i):
@@ -212,24 +283,31 @@ def test_mul_scalar_intt_fused(gpu, oracle, hip_env, n, depth, bits, design):
     x[0, 0] = (np.asarray(moduli, dtype=np.uint64) - np.uint64(1)).reshape(-1, 1)  # worst-case residues q-1
     gx, gw = gpu.GpuDCRTPolyMatrix.from_rns(p, x, True), gpu.GpuDCRTPolyMatrix.from_rns(p, w, True)
     want = oracle.matrix_ntt(oracle.pointwise("mul", x, w, moduli), moduli, inverse=True)
-    out = gx.mul_scalar_intt(gw)
+    with ran.launches() as k:
+        out = gx.mul_scalar_intt(gw)
     assert not out.is_ntt and np.array_equal(out.to_rns(), want)
     assert np.array_equal(gx.to_rns(), x)  # the operand is untouched
-    _ffi.check_status(_ffi.lib().gpupoly_matrix_mul_scalar_intt(gx.raw, gx.raw, gw.raw), "gpupoly_matrix_mul_scalar_intt")
+    with ran.launches() as k_in_place:
+        _ffi.check_status(_ffi.lib().gpupoly_matrix_mul_scalar_intt(gx.raw, gx.raw, gw.raw), "gpupoly_matrix_mul_scalar_intt")
+    if _forced("test_mul_scalar_intt_fused", "MXX_HIP_NTT14", design, n=n, bits=bits, design=design):
+        k.assert_ran("MXX_HIP_NTT14", design, moduli, inverse=True)
+        k_in_place.assert_ran("MXX_HIP_NTT14", design, moduli, inverse=True)
     gx.is_ntt = False
     assert np.array_equal(gx.to_rns(), want)
 
 
 @pytest.mark.parametrize("shape", [(32, 32, 32), (64, 64, 64), (33, 12, 40), (40, 100, 70), (3, 16, 70), (64, 128, 32), (70, 5, 33)])
-@pytest.mark.parametrize("bits", [24, 22, 17])
+@pytest.mark.parametrize("bits", [24, "below MAX_Q", 22, 17])
 def test_matmul_mfma_kernel(gpu, oracle, hip_env, shape, bits):
     """Matrix-core form of the R_q product (matmul_mfma.hip: centred residues as three balanced int8 digits,
     v_mfma_i32_32x32x32_i8 into five significance planes, 64-bit recombination + Barrett): bit-exact against the
     CPU restatement on full and ragged 32x32 tiles, inner dimensions that are not multiples of 32, and the
-    residues at the centring boundary (0, (q-1)/2, (q+1)/2, q-1)."""
+    residues at the centring boundary (0, (q-1)/2, (q+1)/2, q-1).  The largest 24-bit primes (bits = 24) lie above the
+    kernel's modulus bound, so that basis only ever showed the dispatcher's fall-back; "below MAX_Q" is the widest basis
+    the kernel takes."""
     r, k, c = shape
     n = 128
-    moduli = oracle.gen_crt_basis(n, 2, bits)
+    moduli = _mfma_moduli(oracle, n, bits)
     p = gpu.GpuDCRTPolyParams(n, moduli, 8)
     a = rand_matrix(oracle, 27, r, k, moduli, n)
     b = rand_matrix(oracle, 28, k, c, moduli, n)
@@ -243,6 +321,10 @@ def test_matmul_mfma_kernel(gpu, oracle, hip_env, shape, bits):
     gb = gpu.GpuDCRTPolyMatrix.from_rns(p, b, True)
     hip_env.set("MXX_HIP_MATMUL_PATH", "mfma")
     assert np.array_equal((ga * gb).to_rns(), oracle.matmul(a, b, moduli))
+    if _forced("test_matmul_mfma_kernel", "MXX_HIP_MATMUL_PATH", "mfma", shape=shape, bits=bits):
+        _assert_product_kernel(p, "mfma")
+    else:
+        assert not p.ctx().last_kernel().startswith("mmfma::"), "the kernel ran where its launcher's conditions say it declines"
 
 
 def test_matmul_mfma_equals_valu_at_full_size(gpu, oracle, hip_env):
@@ -251,12 +333,21 @@ def test_matmul_mfma_equals_valu_at_full_size(gpu, oracle, hip_env):
     us = gpu.GpuDCRTPolyUniformSampler()
     a = us.sample_uniform(p, 64, 64, gpu.DistType.FinRingDist())
     b = us.sample_uniform(p, 64, 64, gpu.DistType.FinRingDist())
+    test = "test_matmul_mfma_equals_valu_at_full_size"
     hip_env.set("MXX_HIP_MATMUL_PATH", "dma")
     want = a * b
+    if _forced(test, "MXX_HIP_MATMUL_PATH", "dma"):
+        _assert_product_kernel(p, "dma")
     hip_env.set("MXX_HIP_MATMUL_PATH", "mfma")
-    assert a * b == want
+    got = a * b
+    if _forced(test, "MXX_HIP_MATMUL_PATH", "mfma"):
+        _assert_product_kernel(p, "mfma")
+    assert got == want
     hip_env.set("MXX_HIP_MATMUL_PATH", "wide")
-    assert a * b == want
+    got = a * b
+    if _forced(test, "MXX_HIP_MATMUL_PATH", "wide"):
+        _assert_product_kernel(p, "wide")
+    assert got == want
 
 
 @pytest.mark.parametrize("shape,n", [((2, 72, 4), 256), ((5, 9, 7), 256), ((1, 3, 1), 64), ((8, 40, 9), 4096), ((3, 70, 5), 16)])
@@ -313,6 +404,8 @@ def test_matmul_lazy_window_worst_case_both_operands(gpu, oracle, hip_env, path)
     b = np.broadcast_to(top, (k, c, len(moduli), n)).copy()
     hip_env.set("MXX_HIP_MATMUL_PATH", path)
     got = (gpu.GpuDCRTPolyMatrix.from_rns(p, a, True) * gpu.GpuDCRTPolyMatrix.from_rns(p, b, True)).to_rns()
+    if _forced("test_matmul_lazy_window_worst_case_both_operands", "MXX_HIP_MATMUL_PATH", path, path=path):
+        _assert_product_kernel(p, path)
     assert np.array_equal(got, oracle.matmul(a, b, moduli))
 
 
