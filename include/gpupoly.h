@@ -964,6 +964,48 @@ int gpupoly_matrix_scale_round(GpuMatrix *out, const GpuMatrix *in, uint64_t t, 
  * (recompose those with the per-level calls).                                                                     */
 int gpupoly_matrix_crt_recompose_rounded(GpuMatrix *out, const GpuMatrix *const *terms, const int *signs,
                                          size_t terms_per_level, size_t num_slots);
+/* The nested-RNS gadget on the device (extension).  p_moduli are p_count pairwise coprime small integers
+ * (sample_crt_primes, src/gadgets/arith/nested_rns/encoding.rs:14-71: 3, 4, 5, 7, 11, ... - not all prime), P their
+ * product; the window is limbs level_offset .. level_offset + active_levels - 1 of the matrix's L limbs
+ * (resolve_nested_rns_active_window, :146-160), Q_act their product, Q the product of all L.  With
+ *   rdiv(a, b) = floor((a + floor(b/2)) / b),  inv_j = ((P/p_j) mod p_j)^-1 mod p_j,
+ *   terms(x_0..): y_j = (x_j mod p_j) inv_j mod p_j, w = rdiv(sum_j rdiv(y_j scale, p_j), scale)            (:196-214)
+ *   slot(a, x_0..) = ((sum_j y_j (P/p_j) - w P) rc_a) mod Q,  rc_a = (Q_act/q_a) ((Q_act/q_a) mod q_a)^-1    (:166-180,:222-238)
+ * and slot(a, s) = slot(a, s mod p_0, ...) for an integer s, with D = p_count and A = active_levels:
+ *
+ * gpupoly_matrix_nested_rns_decompose is nested_rns_gadget_decomposed (:273-338; callers
+ * src/gadgets/arith/nested_rns/poly.rs:1682-1693 and src/gadgets/fhe/ring_gsw_nested_rns.rs:33-92): `out` is
+ * rows A (D+1) x cols for a rows x cols `src`; with r the residue of coefficient k of src[row][col] in limb
+ * level_offset + a and (y, w) = terms(r mod p_0, ...), coefficient k of out[row A (D+1) + a (D+1) + d][col] is
+ * slot(a, y_d) for d < D and slot(a, w) for d = D, as its residue in every limb (zero in the window's other limbs).
+ * `src` may be COEFF or EVAL (an EVAL source is inverse-transformed in scratch of the call) and is never modified; `out`
+ * is written whole and tagged out_format (GPU_POLY_FORMAT_EVAL: one forward transform at the end - over the full window
+ * only of the one non-zero limb per row, in scratch, before it is spread over `out`).
+ *
+ * gpupoly_matrix_fill_nested_rns_gadget is nested_rns_gadget_vector (:240-271): `out` is 1 x A (D+1); every
+ * coefficient of entry a (D+1) + d is slot(a, g), g = (P/p_d) mod q_a for d < D and (q_a - P mod q_a) mod q_a for d = D,
+ * q_a limb level_offset + a.  Tagged out_format as the reference's from_biguints of n equal coefficients would be.
+ *
+ * gpupoly_matrix_nested_rns_residues is the first stage alone: out[row A D + a D + j][col] holds r mod p_j at
+ * coefficient k, the same small integer in every limb - the slot-wise form of encode_nested_rns_poly_with_offset
+ * (:401-420) that ciphertext_inputs_from_native (ring_gsw_nested_rns.rs:368-419) builds one coefficient at a time.
+ * `out` is rows A D x cols and is tagged COEFF.
+ *
+ * The tables of a set of arguments (per-p reciprocals and look-ups, per-limb constants, slot(a, s) for every small s)
+ * are built on the first call with it and kept by the context.  Enqueued on the context's stream; the host does not
+ * block (but for that first build).  0 rows or 0 columns launch nothing and set the tag.
+ * Overlap: rule 3 - `out` must not overlap `src`, row views included (the message contains "overlap").
+ * Refused, with nothing launched and `out` (contents and tag) untouched, the message naming the entry: a null argument;
+ * an out_format that is neither; a context, level or shape mismatch (`out` at src's level); active_levels = 0 or
+ * level_offset + active_levels beyond the matrix's limbs; any overlap of `out` with `src`.  Refused likewise with an
+ * error containing "unsupported": p_count outside 1..64, a p_j outside [2, 2^16), moduli that are not pairwise coprime,
+ * scale = 0, (p_max - 1) scale + p_max/2 or p_count scale + scale/2 at or above 2^64.                             */
+int gpupoly_matrix_nested_rns_decompose(GpuMatrix *out, const GpuMatrix *src, const uint64_t *p_moduli, size_t p_count,
+                                        uint64_t scale, size_t level_offset, size_t active_levels, int out_format);
+int gpupoly_matrix_fill_nested_rns_gadget(GpuMatrix *out, const uint64_t *p_moduli, size_t p_count, uint64_t scale,
+                                          size_t level_offset, size_t active_levels, int out_format);
+int gpupoly_matrix_nested_rns_residues(GpuMatrix *out, const GpuMatrix *src, const uint64_t *p_moduli, size_t p_count,
+                                       size_t level_offset, size_t active_levels);
 /* Every coefficient of `mat` as its value in [0, Q_level): little-endian 64-bit words, words_per_coeff words each
  * (zero above the words Q_level needs), order [row][col][k], into host memory `out` (synchronous).  COEFF or EVAL
  * input (an EVAL input is inverse-transformed in scratch; `mat` is left as it was).  Replaces the host CRT of

@@ -203,6 +203,9 @@ SIGNATURES = {
     "gpupoly_launch_count": (C.c_uint64, []),
     "gpupoly_matrix_scale_round": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int]),
     "gpupoly_matrix_crt_recompose_rounded": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int), _sz, _sz]),
+    "gpupoly_matrix_nested_rns_decompose": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), _sz, C.c_uint64, _sz, _sz, C.c_int]),
+    "gpupoly_matrix_fill_nested_rns_gadget": (C.c_int, [_vp, C.POINTER(C.c_uint64), _sz, C.c_uint64, _sz, _sz, C.c_int]),
+    "gpupoly_matrix_nested_rns_residues": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), _sz, _sz, _sz]),
     "gpupoly_matrix_store_coeff_words": (C.c_int, [_vp, C.POINTER(C.c_uint64), _sz]),
     "gpupoly_matrix_load_coeff_words": (C.c_int, [_vp, C.POINTER(C.c_uint64), _sz, _sz, C.c_int]),
     "gpupoly_matrix_centered_max_abs": (C.c_int, [_vp, C.POINTER(C.c_uint64), _sz]),

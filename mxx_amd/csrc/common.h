@@ -130,6 +130,10 @@ struct GpuContext {
     // constant C of gpupoly_matrix_mul_decompose_gadget_const_many (gadget_scalar.hip): built on the first call with that
     // constant, under `mutex`, freed with the context; a bounded number of them is kept
     std::map<std::vector<uint64_t>, void *> gadget_const_tables;
+    // {word bytes, limbs, level offset, active levels, scale, p_0, ...} -> the device tables of the nested-RNS gadget
+    // (nested_rns.hip): built on the first call with those arguments, under `mutex`, freed with the context; a bounded
+    // number of bounded size is kept
+    std::map<std::vector<uint64_t>, void *> nested_rns_tables;
 };
 
 // the layout tag of a matrix's storage, copyable (local views copy a GpuMatrix) and read without the lock on the fast path

@@ -525,6 +525,7 @@ static void context_release(GpuContext *ctx) {
     if (ctx->d_tw2s_inv) (void)hipFree(ctx->d_tw2s_inv);
     for (auto &kv : ctx->gadget_weights) (void)hipFree(kv.second);
     for (auto &kv : ctx->gadget_const_tables) (void)hipFree(kv.second);
+    for (auto &kv : ctx->nested_rns_tables) (void)hipFree(kv.second);
     if (ctx->timer_start) (void)hipEventDestroy(ctx->timer_start);
     if (ctx->timer_stop) (void)hipEventDestroy(ctx->timer_stop);
     for (hipEvent_t ev : ctx->marks)

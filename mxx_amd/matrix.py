@@ -1073,6 +1073,48 @@ class GpuDCRTPolyMatrix:
             rows.append(row)
         return rows[0].concat_rows(rows[1:])
 
+    # ---- the nested-RNS gadget (extension; NestedRnsContext in nested_rns.py sits on these) ----
+    @staticmethod
+    def _p_moduli_arg(p_moduli):
+        ps = [int(p) for p in p_moduli]
+        if any(not (0 <= p < 1 << 64) for p in ps):
+            raise ValueError("p moduli must fit 64 bits")
+        return (C.c_uint64 * max(1, len(ps)))(*ps), len(ps)
+
+    def nested_rns_decompose(self, p_moduli, scale: int, level_offset: int, active_levels: int,
+                             eval_format: bool = True) -> "GpuDCRTPolyMatrix":
+        """`nested_rns_gadget_decomposed` (src/gadgets/arith/nested_rns/encoding.rs:273-338) of this matrix against the
+        window [level_offset, level_offset + active_levels) of its limbs: rows * active_levels * (len(p_moduli) + 1) x
+        cols, one device call (gpupoly_matrix_nested_rns_decompose).  This matrix is left as it was."""
+        parr, D = self._p_moduli_arg(p_moduli)
+        out = GpuDCRTPolyMatrix(self.params, self.nrow * active_levels * (D + 1), self.ncol, self.level, eval_format)
+        fmt = GPU_POLY_FORMAT_EVAL if eval_format else GPU_POLY_FORMAT_COEFF
+        st = _ffi.lib().gpupoly_matrix_nested_rns_decompose(out.raw, self.raw, parr, D, scale, level_offset, active_levels, fmt)
+        check_status(st, "gpupoly_matrix_nested_rns_decompose")
+        return out
+
+    @classmethod
+    def nested_rns_gadget_vector(cls, params, p_moduli, scale: int, level_offset: int, active_levels: int,
+                                 eval_format: bool = True, level=None) -> "GpuDCRTPolyMatrix":
+        """`nested_rns_gadget_vector` (encoding.rs:240-271): 1 x active_levels * (len(p_moduli) + 1), written on the device
+        (gpupoly_matrix_fill_nested_rns_gadget)."""
+        parr, D = cls._p_moduli_arg(p_moduli)
+        out = cls(params, 1, active_levels * (D + 1), params.crt_depth() - 1 if level is None else level, eval_format)
+        fmt = GPU_POLY_FORMAT_EVAL if eval_format else GPU_POLY_FORMAT_COEFF
+        st = _ffi.lib().gpupoly_matrix_fill_nested_rns_gadget(out.raw, parr, D, scale, level_offset, active_levels, fmt)
+        check_status(st, "gpupoly_matrix_fill_nested_rns_gadget")
+        return out
+
+    def nested_rns_residues(self, p_moduli, level_offset: int, active_levels: int) -> "GpuDCRTPolyMatrix":
+        """Row (row * active_levels + a) * D + j holds, coefficient by coefficient, (residue in limb level_offset + a)
+        mod p_j as a small integer in every limb (gpupoly_matrix_nested_rns_residues): the slot-wise form of
+        `encode_nested_rns_poly_with_offset` (encoding.rs:401-420).  COEFF; this matrix is left as it was."""
+        parr, D = self._p_moduli_arg(p_moduli)
+        out = GpuDCRTPolyMatrix(self.params, self.nrow * active_levels * D, self.ncol, self.level, False)
+        st = _ffi.lib().gpupoly_matrix_nested_rns_residues(out.raw, self.raw, parr, D, level_offset, active_levels)
+        check_status(st, "gpupoly_matrix_nested_rns_residues")
+        return out
+
     @classmethod
     def from_compact_bytes(cls, params, data: bytes) -> "GpuDCRTPolyMatrix":
         """gpu_dcrt_poly.rs:1004-1044."""
