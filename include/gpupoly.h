@@ -117,6 +117,12 @@ void gpu_pinned_free(void *ptr);
 int gpu_matrix_create(GpuContext *ctx, int level, size_t rows, size_t cols, int format, GpuMatrix **out);
 void gpu_matrix_destroy(GpuMatrix *mat);
 int gpu_matrix_copy(GpuMatrix *dst, const GpuMatrix *src);
+/* gpu_matrix_copy_block / gpu_matrix_add_block: the window rule is offset <= extent and count <= extent - offset on each
+ * of the four axes (an offset + count that wraps around size_t is out of bounds like any other); add_block takes at
+ * most 65535 columns.  A successful call retags the whole of `out` with src's format, as the reference does; a refused
+ * one - "source block out of bounds", "destination block out of bounds", "block too wide" - launches nothing and leaves
+ * out's words and tag as they were.  The same holds for gpu_matrix_mul and gpupoly_matrix_fill_identity refused with
+ * "matrix too large". */
 int gpu_matrix_copy_block(GpuMatrix *out, const GpuMatrix *src, size_t dst_row, size_t dst_col, size_t src_row,
                           size_t src_col, size_t rows, size_t cols);
 

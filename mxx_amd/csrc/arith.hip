@@ -766,8 +766,8 @@ static int launch_tensor_typed(GpuMatrix *out, const GpuMatrix *a, const GpuMatr
     constexpr int VNATIVE = 16 / sizeof(W);
     const size_t wpp = matrix_limbs(out) * static_cast<size_t>(ctx->N);
     const size_t polys = matrix_polys(out);
-    const size_t gy = std::min<size_t>(polys, 65535), gz = (polys + gy - 1) / gy;
-    if (gz > 65535) return set_error("gpupoly_matrix_tensor: matrix too large");
+    size_t gy, gz;
+    if (!fold_yz(polys, gy, gz)) return set_error("gpupoly_matrix_tensor: matrix too large");
     if (ctx->N >= VNATIVE) {
         const dim3 grid(static_cast<unsigned>(std::min<size_t>((wpp / VNATIVE + 255) / 256, 64)), static_cast<unsigned>(gy), static_cast<unsigned>(gz));
         MXX_LAUNCH((tensor_kernel<W, VNATIVE>), grid, dim3(256), 0, ctx->stream, static_cast<W *>(words_ptr(out)),
@@ -812,15 +812,23 @@ extern "C" int gpu_matrix_mul(GpuMatrix *out, const GpuMatrix *lhs, const GpuMat
     if (lhs->format != GPU_POLY_FORMAT_EVAL || rhs->format != GPU_POLY_FORMAT_EVAL)
         return set_error("gpu_matrix_mul requires Eval format");
     if (storage_overlaps(out, lhs) || storage_overlaps(out, rhs)) return set_error("gpu_matrix_mul: output must not alias an input");
-    out->format = GPU_POLY_FORMAT_EVAL;
-    if (matrix_polys(out) == 0) return 0;
+    // the tag is written once nothing can refuse the call any more: a grid that does not fit ("matrix too large", from the
+    // dispatcher) leaves `out` as it was, words and tag
+    if (matrix_polys(out) == 0) {
+        out->format = GPU_POLY_FORMAT_EVAL;
+        return 0;
+    }
     if (ctx_activate(out->ctx)) return 1;
     if (lhs->cols == 0) {
         HIP_TRY(hipMemsetAsync(words_ptr(out), 0, out->bytes, out->ctx->stream));
+        out->format = GPU_POLY_FORMAT_EVAL;
         return 0;
     }
     MXX_TRACE_BYTES(static_cast<double>(lhs->bytes) + rhs->bytes + out->bytes);  // (r m + m c + r c) n L w
-    return launch_matmul(out, lhs, rhs);
+    const int rc = launch_matmul(out, lhs, rhs);
+    if (rc == 0) out->format = GPU_POLY_FORMAT_EVAL;
+    else MXX_TRACE_BYTES(0);  // nothing was launched: the bytes stated above must not ride on the thread's next launch
+    return rc;
     ABI_GUARD_END
 }
 

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/gpupoly.h"
+#include "grid_plan.h"
 
 constexpr size_t GPUPOLY_MAX_LIMBS = 64;  // cuda/include/Runtime.cuh:51 of the reference
 
@@ -188,15 +189,7 @@ struct P1KeyEntry {
 };
 
 // ---- one thread per item -----------------------------------------------------------------------
-// HIP rejects launches with gridDim.x * blockDim.x >= 2^32 ("invalid configuration argument"), which a
-// 64x1024 gadget matrix at n = 2^14 already exceeds: such kernels use item_grid() / item_index().
-static inline dim3 item_grid(size_t items, unsigned threads) {
-    const size_t blocks = (items + threads - 1) / threads;
-    const size_t max_x = (static_cast<size_t>(1) << 31) / threads;
-    if (blocks <= max_x) return dim3(static_cast<unsigned>(blocks ? blocks : 1));
-    const size_t y = (blocks + max_x - 1) / max_x;
-    return dim3(static_cast<unsigned>((blocks + y - 1) / y), static_cast<unsigned>(y));
-}
+// item_grid() and the other launch-grid rules: grid_plan.h (no HIP dependency, so a host program can check them)
 #if defined(__HIPCC__)
 __device__ __forceinline__ size_t item_index() {
     return (static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;

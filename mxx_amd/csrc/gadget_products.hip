@@ -184,20 +184,7 @@ int gadget_table(GpuContext *ctx, uint32_t base_bits, const GadgetWeight **out) 
     return 0;
 }
 
-// grid: x = chunks of a limb vector (each lane one 16-byte access per pass, up to four passes), (y, z) = limb vectors
-struct VectorGrid {
-    dim3 grid, block;
-};
-VectorGrid vector_grid(uint32_t vectors, uint32_t N, uint32_t vn) {
-    const uint32_t lanes = (N + vn - 1) / vn;  // accesses per limb vector
-    const uint32_t threads = std::min<uint32_t>(256, (lanes + 63) / 64 * 64);
-    const uint32_t per_block = threads * 4;
-    const uint32_t gx = (lanes + per_block - 1) / per_block;
-    const uint32_t gy = std::min<uint32_t>(vectors, 65535);
-    const uint32_t gz = (vectors + gy - 1) / gy;  // vectors < 2^32 / 65535 * 65535: checked with the refusals
-    return {dim3(gx, gy, gz), dim3(threads)};
-}
-constexpr uint64_t kMaxVectors = 65535ull * 65535ull;
+// the grid, x = chunks of a limb vector and (y, z) = limb vectors: vector_grid and kMaxVectors (grid_plan.h)
 
 template <typename W>
 int launch_mul_gadget(GpuContext *ctx, void *out, const void *addend, const void *lhs, const void *scalar, const GadgetWeight *table,

@@ -269,8 +269,9 @@ int launch_const_vn(GpuContext *ctx, const ScalarLaunch &g, const ScalarWeight *
     const uint32_t lanes = (N + VN - 1) / VN;
     const uint32_t threads = std::min<uint32_t>(256, (lanes + 63) / 64 * 64);
     const uint32_t gx = (lanes + threads * 4 - 1) / (threads * 4);
-    const uint32_t gy = std::min<uint32_t>(units, 65535);
-    const dim3 grid(gx, gy, (units + gy - 1) / gy), block(threads);
+    size_t gy, gz;
+    (void)fold_yz(units, gy, gz);  // grid_plan.h; units <= kMaxUnits: checked with the refusals
+    const dim3 grid(gx, static_cast<unsigned>(gy), static_cast<unsigned>(gz)), block(threads);
     MXX_TRACE_BYTES(g.bytes);
 #define MXX_CONST(D)                                                                                                                     \
     MXX_LAUNCH((gadget_const_kernel<W, VN, D>), grid, block, 0, ctx->stream, g.ops, g.count, table, ctx->d_limbs, L, N, dpt, negate, units)

@@ -346,7 +346,8 @@ int combine_group(const LookupCall &call, GpuMatrix *const *outs, const GpuMatri
     a.S = static_cast<uint32_t>(Sg), a.r = static_cast<uint32_t>(call.r), a.c = static_cast<uint32_t>(c);
     a.L = call.L, a.dpt = call.dpt, a.logN = ctx->logN, a.row_tiles = t.row_tiles, a.col_tiles = t.col_tiles;
     const size_t vecs = wpp / vn;
-    const size_t gy = std::min<size_t>(a.entries, 65535), gz = (a.entries + gy - 1) / gy;
+    size_t gy, gz;
+    (void)fold_yz(a.entries, gy, gz);  // grid_plan.h; the count was held to 65535 x 65535 with the refusals (grid_fits)
     const unsigned threads = static_cast<unsigned>(std::min<size_t>(256, (vecs + 63) / 64 * 64));
     const dim3 grid(static_cast<unsigned>(std::min<size_t>((vecs + threads - 1) / threads, 64)), static_cast<unsigned>(gy), static_cast<unsigned>(gz));
     // [V_s; K_s] read once per row tile, Lhs once per column tile, mid_id's chunk and mid_gy's dpt words per output word, the

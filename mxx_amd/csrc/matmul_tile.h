@@ -93,10 +93,7 @@ int dispatch_stacked_tile(const GpuContext *ctx, TileShape t, F &&f) {
     return f(TileCfg<uint32_t, 8, 8, 1>());
 }
 
-// the grid's y extent holds row tiles x column tiles
-inline bool tile_grid_fits(uint64_t rows, uint64_t cols, uint32_t tr, uint32_t tc) {
-    return ((rows + tr - 1) / tr) * ((cols + tc - 1) / tc) <= 65535;
-}
+// the grid's y extent holds row tiles x column tiles: tile_grid_fits (grid_plan.h)
 
 // x: slots (SV per lane), y: row tiles x column tiles (tile_grid_fits is the caller's to check), z: limbs
 struct TileGrid {

@@ -189,28 +189,37 @@ int launch_copy_block(GpuMatrix *out, const GpuMatrix *src, size_t dst_row, size
     if (!out || !src) return set_error(std::string(who) + ": null matrix");
     if (out->ctx != src->ctx) return set_error(std::string(who) + ": context mismatch");
     if (out->level != src->level) return set_error(std::string(who) + ": level mismatch");
-    if (src_row + rows > src->rows || src_col + cols > src->cols)
+    // offset > extent || count > extent - offset: the sum offset + count can wrap in size_t
+    if (src_row > src->rows || rows > src->rows - src_row || src_col > src->cols || cols > src->cols - src_col)
         return set_error(std::string(who) + ": source block out of bounds");
-    if (dst_row + rows > out->rows || dst_col + cols > out->cols)
+    if (dst_row > out->rows || rows > out->rows - dst_row || dst_col > out->cols || cols > out->cols - dst_col)
         return set_error(std::string(who) + ": destination block out of bounds");
-    // quirk kept from the reference: the whole destination is retagged with the
-    // source's format even for a partial block (MatrixData.cu:519,531,558)
+    // blockIdx.y of the accumulating kernel is limited to 65535 and one launch covers whole rows of the block
+    if (add && rows != 0 && cols > 65535) return set_error(std::string(who) + ": block too wide");
     const bool shared = storage_overlaps(out, src);  // judged before anything is unpacked
-    out->format = src->format;
-    if (rows == 0 || cols == 0) return 0;
+    const bool empty = rows == 0 || cols == 0;
     GpuContext *ctx = out->ctx;
-    if (ctx_activate(ctx)) return 1;
-    size_t wpp = matrix_limbs(out) * static_cast<size_t>(ctx->N);
+    const size_t wpp = matrix_limbs(out) * static_cast<size_t>(ctx->N), wb = static_cast<size_t>(ctx->word_bytes);
+    // shared storage: the source block is staged first (tightly, rows x cols) and read from the copy.  Whatever can fail
+    // before anything is enqueued - the refusals above, the device, this allocation - comes before the tag is written
+    CtxBlock staged(ctx);  // back to the cache at scope exit, error paths included
+    if (!empty) {
+        if (ctx_activate(ctx)) return 1;
+        if (shared && staged.alloc(rows * cols * wpp * wb)) return 1;
+    }
+    // quirk kept from the reference: the whole destination is retagged with the
+    // source's format even for a partial block (MatrixData.cu:519,531,558); a call that returns an error before this
+    // line has launched nothing and leaves words and tag as they were
+    out->format = src->format;
+    if (empty) return 0;
     if (!add) {
-        size_t wb = static_cast<size_t>(ctx->word_bytes);
         const char *s = static_cast<const char *>(words_ptr(src)) + (src_row * src->cols + src_col) * wpp * wb;
         char *d = static_cast<char *>(words_ptr(out)) + (dst_row * out->cols + dst_col) * wpp * wb;
         if (shared) {
             // the blocks may overlap (the same matrix, or row views of one parent): the source block is read in full
-            // before the first write (hipMemcpy2D has undefined overlap semantics); use a temp
-            CtxBlock tmp(ctx);  // back to the cache at scope exit, error paths included
+            // before the first write (hipMemcpy2D has undefined overlap semantics); through the staging block
+            CtxBlock &tmp = staged;
             size_t row_bytes = cols * wpp * wb;
-            if (tmp.alloc(rows * row_bytes)) return 1;
             MXX_TRACED_COPY("copy_block (2-D runtime copy)", ctx->stream, 2.0 * rows * row_bytes,
                             HIP_TRY(hipMemcpy2DAsync(tmp.ptr, row_bytes, s, src->cols * wpp * wb, row_bytes, rows,
                                                      hipMemcpyDeviceToDevice, ctx->stream)));
@@ -229,20 +238,15 @@ int launch_copy_block(GpuMatrix *out, const GpuMatrix *src, size_t dst_row, size
         }
         return 0;
     }
-    size_t entries = rows * cols;
     // blockIdx.y is limited to 65535: chunk over row groups
     size_t rows_per_launch = std::max<size_t>(1, 65535 / cols);
-    if (cols > 65535) return set_error(std::string(who) + ": block too wide");
-    (void)entries;
     unsigned gx = grid_for(wpp, 256, 64);
     // shared storage: the kernel's blocks would read source words that other blocks have already accumulated into, so the
-    // source block is staged first (tightly, rows x cols) and the kernel reads the copy
-    CtxBlock staged(ctx);
+    // kernel reads the staged copy
     const void *src_words = words_ptr(src);
     size_t from_cols = src->cols, from_row = src_row, from_col = src_col;
     if (shared) {
-        const size_t wb = static_cast<size_t>(ctx->word_bytes), row_bytes = cols * wpp * wb;
-        if (staged.alloc(rows * row_bytes)) return 1;
+        const size_t row_bytes = cols * wpp * wb;
         const char *s = static_cast<const char *>(src_words) + (src_row * src->cols + src_col) * wpp * wb;
         MXX_TRACED_COPY("copy_block (2-D runtime copy)", ctx->stream, 2.0 * rows * row_bytes,
                         HIP_TRY(hipMemcpy2DAsync(staged.ptr, row_bytes, s, src->cols * wpp * wb, row_bytes, rows,
@@ -418,8 +422,8 @@ extern "C" int gpupoly_matrix_transpose(GpuMatrix *out, const GpuMatrix *src) {
     }
     const size_t vec_per_poly = poly_bytes / 16;
     const unsigned gx = static_cast<unsigned>(std::min<size_t>((vec_per_poly + 255) / 256, 64));
-    const size_t gy = std::min<size_t>(polys, 65535), gz = (polys + gy - 1) / gy;
-    if (gz > 65535) return set_error("gpupoly_matrix_transpose: matrix too large");
+    size_t gy, gz;
+    if (!fold_yz(polys, gy, gz)) return set_error("gpupoly_matrix_transpose: matrix too large");
     MXX_LAUNCH(transpose_kernel, dim3(gx, static_cast<unsigned>(gy), static_cast<unsigned>(gz)), dim3(256), 0, ctx->stream,
                        static_cast<uint4 *>(words_ptr(out)), static_cast<const uint4 *>(words_ptr(src)), src->rows, src->cols, vec_per_poly);
     HIP_TRY(hipGetLastError());
@@ -519,8 +523,8 @@ static int column_blocks(GpuMatrix *whole, GpuMatrix *const *blocks, size_t n, b
         for (uint32_t t = cb.count; t < COLUMN_BLOCKS_MAX; ++t) cb.ptr[t] = nullptr;
         if (cb.count == 0) break;
         const size_t entries = whole->rows * (at - first);
-        const size_t gy = std::min<size_t>(entries, 65535), gz = (entries + gy - 1) / gy;
-        if (gz > 65535 || at >> 32) return set_error(std::string(who) + ": matrix too large");
+        size_t gy, gz;
+        if (!fold_yz(entries, gy, gz) || at >> 32) return set_error(std::string(who) + ": matrix too large");
         MXX_TRACE_BYTES(2.0 * static_cast<double>(entries) * poly_bytes);
         if (split)
             MXX_LAUNCH(column_blocks_kernel<true>, dim3(gx, static_cast<unsigned>(gy), static_cast<unsigned>(gz)), dim3(256), 0, ctx->stream,
@@ -581,11 +585,12 @@ extern "C" int gpupoly_matrix_fill_identity(GpuMatrix *out, const GpuMatrix *sca
         if (scalar->format != GPU_POLY_FORMAT_EVAL) return set_error("gpupoly_matrix_fill_identity requires an Eval scalar");
         if (storage_overlaps(scalar, out)) return set_error("gpupoly_matrix_fill_identity: output must not alias the scalar");
     }
+    // one diagonal entry per blockIdx.y; refused before the tag is written, so that a refused call leaves `out` as it was
+    if (out->bytes != 0 && out->rows > 65535) return set_error("gpupoly_matrix_fill_identity: matrix too large");
     out->format = GPU_POLY_FORMAT_EVAL;
     if (out->bytes == 0) return 0;
     GpuContext *ctx = out->ctx;
     if (ctx_activate(ctx)) return 1;
-    if (out->rows > 65535) return set_error("gpupoly_matrix_fill_identity: matrix too large");
     HIP_TRY(hipMemsetAsync(words_ptr(out), 0, out->bytes, ctx->stream));
     const size_t words = matrix_limbs(out) * static_cast<size_t>(ctx->N);
     const dim3 grid(static_cast<unsigned>(std::min<size_t>((words + 255) / 256, 256)), static_cast<unsigned>(out->rows));

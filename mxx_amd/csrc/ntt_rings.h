@@ -135,21 +135,7 @@ static int launch_split(GpuContext *ctx, W *data, size_t vectors, uint32_t L, bo
 // the tests compare); MXX_HIP_NTT14=unsigned keeps the grouped inverse kernel on the unsigned butterflies
 static bool ntt14_signed(const GpuContext *ctx) { return ctx->signed_ok && ctx->d_tw2s_inv && ctx->env.ntt14 != 2; }
 
-// grid of the grouped 2^14 kernels: (limb, poly) with the poly index split over y and z (each <= 65535)
-static bool ntt14_grid(size_t vectors, uint32_t L, dim3 &grid) {
-    if (L == 0 || vectors % L != 0) return false;
-    const size_t polys = vectors / L;
-    size_t z = (polys + 65534) / 65535;
-    if (z == 0) z = 1;
-    if (z > 65535 || polys % z != 0) {  // keep the grid exact (no out-of-range blocks): find a divisor split
-        z = 0;
-        for (size_t cand = (polys + 65534) / 65535; cand <= 65535 && cand <= polys; ++cand)
-            if (polys % cand == 0 && polys / cand <= 65535) { z = cand; break; }
-        if (z == 0) return false;
-    }
-    grid = dim3(L, static_cast<unsigned>(polys / z), static_cast<unsigned>(z));
-    return true;
-}
+// the grid of the grouped 2^14 kernels, (limb, poly) with the poly index split exactly over y and z: ntt14_grid (grid_plan.h)
 
 // Do the context and the switches admit a fused form of the grouped kernels?  tight_too: the form has a TIGHT instance;
 // phase_too: it takes the phase switch (MXX_HIP_NTT_PHASE)

@@ -113,8 +113,8 @@ __global__ void preimage_scatter_kernel(RequestTable req, const W *__restrict__ 
 // grid over `entries` polynomials of `words_per_poly` words, VN words per lane (column_blocks' shape, matrix.hip)
 static bool poly_grid(size_t entries, size_t words_per_poly, int vn, dim3 &grid) {
     const size_t vecs = words_per_poly / vn;
-    const size_t gy = std::min<size_t>(entries, 65535), gz = (entries + gy - 1) / gy;
-    if (gz > 65535) return false;
+    size_t gy, gz;
+    if (!fold_yz(entries, gy, gz)) return false;
     grid = dim3(static_cast<unsigned>(std::min<size_t>((vecs + 255) / 256, 64)), static_cast<unsigned>(gy), static_cast<unsigned>(gz));
     return true;
 }

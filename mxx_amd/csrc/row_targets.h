@@ -256,8 +256,8 @@ template <typename F>
 int launch_combine(const char *who, GpuContext *ctx, double bytes, size_t entries, uint32_t L, uint32_t logN, uint32_t dpt, F &&launch) {
     const size_t vn = ctx->N % (16 / ctx->word_bytes) == 0 ? 16 / ctx->word_bytes : 1;
     const size_t wpp = static_cast<size_t>(L) << logN, vecs = wpp / vn;
-    const size_t gy = std::min<size_t>(entries, 65535), gz = (entries + gy - 1) / gy;
-    if (gz > 65535) return set_error(std::string(who) + ": too many target polynomials in one group");
+    size_t gy, gz;
+    if (!fold_yz(entries, gy, gz)) return set_error(std::string(who) + ": too many target polynomials in one group");
     const unsigned threads = static_cast<unsigned>(std::min<size_t>(256, (vecs + 63) / 64 * 64));
     const dim3 grid(static_cast<unsigned>(std::min<size_t>((vecs + threads - 1) / threads, 64)), static_cast<unsigned>(gy), static_cast<unsigned>(gz));
     MXX_TRACE_BYTES(bytes);

@@ -399,7 +399,7 @@ int sample_impl(GpuMatrix *out, int dist, double sigma, GpuRngSeed seed, size_t 
         return set_error("gpu_matrix_sample_distribution: invalid dist_type");
     if (dist == GPU_MATRIX_DIST_GAUSS && !(sigma > 0.0))
         return set_error("gpu_matrix_sample_distribution: sigma must be positive for Gaussian sampling");
-    if (col_offset + out->cols > full_ncol)
+    if (col_offset > full_ncol || out->cols > full_ncol - col_offset)  // the sum col_offset + cols can wrap in size_t
         return set_error("gpu_matrix_sample_distribution_columns: column window out of range");
     // stream ids (global polynomial index + 1) are 48 bits wide in the nonce layout of rng.h: refuse what would wrap
     const size_t row_limit = full_ncol ? ((size_t(1) << 48) - 2) / full_ncol : ~size_t(0);

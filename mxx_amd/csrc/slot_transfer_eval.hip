@@ -412,7 +412,8 @@ int combine_group(const SlotEvalCall &call, GpuMatrix *const *outs, const GpuMat
         const uint32_t lanes = static_cast<uint32_t>(ctx->N / vn);
         const uint32_t threads = std::min<uint32_t>(256, (lanes + 63) / 64 * 64);
         la.slot_blocks = (lanes + threads - 1) / threads;
-        const size_t gy = std::min<size_t>(la.entries, 65535), gz = (la.entries + gy - 1) / gy;
+        size_t gy, gz;
+        (void)fold_yz(la.entries, gy, gz);  // grid_plan.h; the count was held to 65535 x 65535 with the refusals (grid_fits)
         const dim3 grid(static_cast<unsigned>(la.slot_blocks * L), static_cast<unsigned>(gy), static_cast<unsigned>(gz));
         // every term's c_in and mid read once, LhsA and LhsB written once (an in-place A segment is neither read nor written)
         double moved = 0;
@@ -436,7 +437,8 @@ int combine_group(const SlotEvalCall &call, GpuMatrix *const *outs, const GpuMat
     a.r = static_cast<uint32_t>(call.r), a.c = static_cast<uint32_t>(call.c), a.logN = ctx->logN;
     a.row_tiles = t.row_tiles, a.col_tiles = t.col_tiles;
     const size_t vecs = wpp / vn;
-    const size_t gy = std::min<size_t>(a.entries, 65535), gz = (a.entries + gy - 1) / gy;
+    size_t gy, gz;
+    (void)fold_yz(a.entries, gy, gz);  // grid_plan.h; the count was held to 65535 x 65535 with the refusals (grid_fits)
     const unsigned threads = static_cast<unsigned>(std::min<size_t>(256, (vecs + 63) / 64 * 64));
     const dim3 grid(static_cast<unsigned>(std::min<size_t>((vecs + threads - 1) / threads, 64)), static_cast<unsigned>(gy), static_cast<unsigned>(gz));
     // [Pg_s; D_s; P1_s] read once per row tile, [c_b0 | LhsA_s | LhsB_s] once per column tile, the outputs' block written once

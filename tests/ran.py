@@ -92,7 +92,14 @@ TABLE = {
 
 
 class Launched(list):
-    """The names of the launches inside a `launches()` block, in launch order (filled when the block ends)."""
+    """The names of the launches inside a `launches()` block, in launch order (filled when the block ends).  `records` holds
+    the trace's own entries in the same order: kernel, blocks (grid x * y * z; 0 for a runtime copy), threads, bytes, ms."""
+
+    records = ()
+
+    def blocks_of(self, prefix):
+        """the block counts of the launches whose name starts with `prefix`, in launch order"""
+        return [r["blocks"] for r in self.records if r["kernel"].strip().startswith(prefix)]
 
     @staticmethod
     def word_class(moduli):
@@ -119,4 +126,5 @@ def launches():
     try:
         yield names
     finally:
-        names.extend(t["kernel"].strip() for t in _ffi.trace_end())
+        names.records = _ffi.trace_end()
+        names.extend(t["kernel"].strip() for t in names.records)
