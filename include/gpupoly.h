@@ -263,7 +263,9 @@ int gpupoly_matrix_mul_batch(GpuMatrix *const *outs, const GpuMatrix *const *lhs
  * src/circuit/poly_circuit/eval.rs:269-345): products go out up to 64 per launch (gpupoly_matrix_mul_batch), the
  * point-wise gates - add, sub, negate, product by a 1x1 ring element (Small / LargeScalarMul) - up to 64 per launch,
  * decompositions through their tuned paths.  One context; no output may be another gate's operand or output; formats
- * and shapes as for the single-gate entry points named below.                                                      */
+ * and shapes as for the single-gate entry points named below.  The matrices of a gate share one level (the MUL gates of
+ * a call one level among themselves): a gate of mixed levels is refused with "level mismatch" before anything is
+ * launched, whatever the other gates of the call are.                                                              */
 #define GPUPOLY_OP_MUL 0           /* gpu_matrix_mul(out, lhs, rhs) */
 #define GPUPOLY_OP_ADD 1           /* gpu_matrix_add(out, lhs, rhs); out may be lhs */
 #define GPUPOLY_OP_SUB 2           /* gpu_matrix_sub */

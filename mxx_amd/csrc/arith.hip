@@ -1147,6 +1147,9 @@ extern "C" int gpupoly_batch(const GpuBatchOp *ops, size_t count, uint32_t base_
         if (!unary && !o.rhs) return set_error("gpupoly_batch: null right operand");
         if (!ctx) ctx = o.out->ctx;
         if (o.out->ctx != ctx || o.lhs->ctx != ctx || (!unary && o.rhs->ctx != ctx)) return set_error("gpupoly_batch: context mismatch");
+        // a gate's matrices share one level (gates may differ among themselves); judged here, for every gate, because the
+        // products below are launched before the point-wise gates and the decompositions reach their own checks
+        if (o.out->level != o.lhs->level || (!unary && o.rhs->level != o.lhs->level)) return set_error("gpupoly_batch: level mismatch");
     }
     // every overlap refusal before the first launch (bytes, not objects: row views share their parent's storage)
     for (size_t i = 0; i < count; ++i) {

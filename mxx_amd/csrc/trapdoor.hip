@@ -1088,6 +1088,12 @@ extern "C" int gpu_matrix_sample_p1_full(const GpuMatrix *a_mat, const GpuMatrix
     if (out && ((tp2 && storage_overlaps(tp2, out)) || (a_mat && storage_overlaps(a_mat, out)) ||
                 (b_mat && storage_overlaps(b_mat, out)) || (d_mat && storage_overlaps(d_mat, out))))
         return set_error("gpu_matrix_sample_p1_full: output must not alias an input");
+    // the covariance kernels run inside the cache's constructor: what the sampler behind it would refuse about the
+    // levels is refused here, before they are launched
+    if (check_p1_inputs(a_mat, b_mat, d_mat, sigma, s, dgg_stddev, "gpu_matrix_sample_p1_full")) return 1;
+    if (tp2 && out && (tp2->ctx != a_mat->ctx || out->ctx != a_mat->ctx)) return set_error("context mismatch in gpu_matrix_sample_p1_full");
+    if (tp2 && out && (tp2->level != a_mat->level || out->level != a_mat->level))
+        return set_error("level mismatch in gpu_matrix_sample_p1_full");
     GpuP1CovarianceCache *cache = nullptr;
     int rc = gpu_matrix_create_p1_covariance_cache(a_mat, b_mat, d_mat, sigma, s, dgg_stddev, &cache);
     if (rc) return rc;

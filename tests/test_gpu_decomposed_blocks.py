@@ -74,6 +74,39 @@ def test_every_block_equals_the_window_entry_alone(gpu, oracle, ctx, dist):
                                 assert np.array_equal(got[:, t * c:(t + 1) * c], want), (t, small, rows, (full, off, c), is_ntt)
 
 
+@pytest.mark.parametrize("level", [0, 1])
+@pytest.mark.parametrize("dist", DISTS)
+def test_an_output_below_the_top_level(gpu, oracle, dist, level):
+    """`out` at level 0 / 1 of the three-limb ring: k = dpt * (level + 1) digit rows per source row with dpt from the CONTEXT's
+    crt_bits (the same number, in this same-width basis, as oracle.decompose derives from the truncated basis it is handed);
+    every block against the CPU restatement at that basis and against the window entry alone, seeded and hashed forms."""
+    from mxx_amd.matrix import device_hash_seeds
+
+    p = make_params(gpu, oracle, *CONTEXTS["ggh15_small_ring"])
+    M, n, code, base = gpu.GpuDCRTPolyMatrix, p.ring_dimension(), oracle.DIST[dist], p.base_bits()
+    moduli = p.moduli()[: level + 1]
+    dpt = -(-p.crt_bits() // base)
+    assert level < p.crt_depth() - 1 and oracle.digits_per_tower(moduli, base) == dpt
+    seeds = [gseed(gpu, 7500 + t) for t in range(3)]
+    tags = [b"low_" + bytes([t]) for t in range(3)]
+    rows, (full, off, c) = 2, WINDOWS[1]
+    for small in (False, True):
+        k = dpt * (1 if small else level + 1)
+        for is_ntt in (True, False):
+            wide = M.sample_decomposed_blocks(p, seeds, rows, full, off, c, code, small=small, is_ntt=is_ntt, level=level)
+            assert wide.level == level and wide.size() == (rows * k, 3 * c) and wide.is_ntt == is_ntt
+            got = wide.to_rns()
+            for t, block in enumerate(blocks_of(wide, 3, c)):
+                src = oracle.sample_distribution(rows, c, moduli, n, dist, 0.0, seed_bytes(7500 + t), full_ncol=full, col_offset=off)
+                want = oracle.decompose(src, moduli, base, small)
+                assert np.array_equal(got[:, t * c:(t + 1) * c], oracle.matrix_ntt(want, moduli) if is_ntt else want), (t, small, is_ntt)
+                alone = M.sample_distribution_decomposed_window(p, rows, full, off, c, code, 0.0, seeds[t], small, is_ntt=is_ntt, level=level)
+                assert block == alone, (t, small, is_ntt)
+            hashed = M.sample_hash_decomposed_blocks(p, KEY, tags, rows, full, off, c, code, small=small, is_ntt=is_ntt, level=level)
+            assert hashed == M.sample_decomposed_blocks(p, device_hash_seeds(p, KEY, tags), rows, full, off, c, code, small=small,
+                                                        is_ntt=is_ntt, level=level), (small, is_ntt)
+
+
 def test_hashed_form_equals_the_seeds_given_form_for_every_tag_form(gpu, oracle):
     from mxx_amd.matrix import device_hash_seeds
 

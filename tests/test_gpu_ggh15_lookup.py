@@ -228,6 +228,54 @@ def test_outputs_equal_the_plain_reference_in_the_original_association(gpu, orac
             assert np.array_equal(got[s].to_rns(), want), (ctx, chunk, s)
 
 
+@pytest.mark.parametrize("level", [0, 1])
+@pytest.mark.parametrize("bits,base", [(24, 12), (51, 17)])
+def test_operands_below_the_top_level_equal_the_plain_reference(gpu, oracle, bits, base, level):
+    """Every matrix of the call at level 0 / 1 of a three-limb context (the refusal list below only shows that MIXED levels
+    are turned away): m_g = d * dpt * (level + 1) with dpt from the CONTEXT's crt_bits (one width per basis here, so plainref
+    derives the same dpt from the truncated basis), V_s sampled in limbs 0..level only, and the stage-2 formula of the header
+    in plainref at moduli[: level + 1] - the stage-1 products are given as random matrices, the formula needs no more; the
+    combine entry with the digits given must write the same words."""
+    n, d, S, r = 16, 2, 3, 2
+    p = make_params(gpu, oracle, n, 3, bits, base)
+    M, moduli = gpu.GpuDCRTPolyMatrix, p.moduli()[: level + 1]
+    L, dpt = level + 1, -(-p.crt_bits() // base)
+    assert P.digits_per_tower(moduli, base) == dpt
+    k = L * dpt
+    m_g, w = d * k, d * (k + 2)
+    slots = list(range(n))
+    q_col = np.asarray([int(q) for q in moduli], dtype=object).reshape(1, 1, L, 1)
+    rnd = lambda seed, rows, cols: oracle.random_matrix(seed + level, rows, cols, moduli, n)  # noqa: E731
+    mids_np = [rnd(760 + 3 * i, S * r, m_g) for i in range(5)] + [rnd(775, S * r, w)]
+    mid_id, mid_gy, mid_v, mid_vx, mid_rand, mid_g1 = mids_np
+    mids = [M.from_rns(p, a, True) for a in mids_np]
+    xs_np = [rnd(780 + 3 * s, 1, 1) for s in range(S)]  # non-constant plaintexts: EVAL residues
+    xs = [M.from_rns(p, x, True) for x in xs_np]
+    ys = list(y_values(moduli)[2:5])  # Q - 1, Q + 5 and the three-word y
+    tags = [b"ggh15_low_level_v_" + bytes([48 + s]) for s in range(S)]
+    for chunk in ((0, min(4, m_g)), (k - 1, 2)):
+        cols = slice(chunk[0], chunk[0] + chunk[1])
+        ks_np = [rnd(790 + 3 * s, w, chunk[1]) for s in range(S)]
+        ks = [M.from_rns(p, a, True) for a in ks_np]
+        got = M.ggh15_lookup(mids, ks, xs, chunk[0], chunk[1], ys, KEY, tags)
+        vs = []
+        for s in range(S):
+            rows = slice(s * r, (s + 1) * r)
+            u = oracle.sample_distribution(d, chunk[1], moduli, n, "uniform", 0.0, gpu.hash_seed_for_matrix(KEY, tags[s]),
+                                           full_ncol=m_g, col_offset=chunk[0])
+            v = digits_eval(u, moduli, base, dpt, slots)
+            vs.append(v)
+            x = xs_np[s][0, 0].astype(object).reshape(1, 1, L, n)
+            lhs = ((mid_v[rows].astype(object) + x * mid_vx[rows].astype(object) + mid_rand[rows].astype(object)) % q_col).astype(np.uint64)
+            plus = P.slot_mul_sum(mid_id[rows, cols], [mid_gy[rows], lhs], [gy_block(moduli, n, base, dpt, ys[s], d, chunk), v], moduli, False)
+            want = P.slot_mul_sum(plus, [mid_g1[rows]], [ks_np[s]], moduli, True)
+            assert got[s].level == level and got[s].is_ntt and got[s].size() == (r, chunk[1])
+            assert np.array_equal(got[s].to_rns(), want), (bits, level, chunk, s)
+        given = M.ggh15_lookup_combine(mids, ks, xs, M.from_rns(p, np.concatenate(vs, axis=1), True), chunk[0], chunk[1], ys)
+        for s in range(S):
+            assert given[s] == got[s], (bits, level, chunk, s)
+
+
 # ---------------------------------------------------------------------------------------------------
 # 3. the combine entry alone in every width class
 # ---------------------------------------------------------------------------------------------------

@@ -187,6 +187,54 @@ def test_targets_equal_the_plain_reference(gpu, oracle, ctx):
             assert np.array_equal(target.to_rns(), want), (ctx, chunk, idx, y)
 
 
+@pytest.mark.parametrize("level", [0, 1])
+@pytest.mark.parametrize("bits,base", [(24, 12), (51, 17)])
+def test_operands_below_the_top_level_equal_the_plain_reference(gpu, oracle, bits, base, level):
+    """The four operands and the outputs at level 0 / 1 of a three-limb context: m = d * dpt * (level + 1) with dpt from the
+    CONTEXT's crt_bits (these bases have one width, so plainref derives the same dpt from the truncated basis), the hashed
+    samples of limbs 0..level only, and the plain reference above handed moduli[: level + 1]; then the combine kernel alone
+    with operands at the level."""
+    n, d, T = 16, 2, 3
+    p = make_params(gpu, oracle, n, 3, bits, base)
+    M, moduli = gpu.GpuDCRTPolyMatrix, p.moduli()[: level + 1]
+    L, dpt = level + 1, -(-p.crt_bits() // base)
+    assert P.digits_per_tower(moduli, base) == dpt
+    k = L * dpt
+    m = d * k
+    slots = list(range(n))
+    w_id, w_gy, w_v, w_vx = (oracle.random_matrix(340 + level + i, d, m, moduli, n) for i in range(4))
+    ws = [M.from_rns(p, w, True) for w in (w_id, w_gy, w_v, w_vx)]
+    q_col = np.asarray([int(q) for q in moduli], dtype=object).reshape(1, 1, L, 1)
+    tag = lambda idx: f"ggh15_lut_v_idx_{LUT_ID}_{idx}".encode("ascii")  # noqa: E731
+    for chunk in ((0, min(4, m)), (k - 1, 2)):
+        rows = rows_of(moduli, 20)[7:7 + T]
+        got = M.lut_targets(*ws, chunk[0], chunk[1], [y for _, y in rows], [i for i, _ in rows], KEY, [tag(i) for i, _ in rows])
+        for (idx, y), target in zip(rows, got):
+            assert target.level == level and target.is_ntt and target.size() == (d, chunk[1])
+            u = oracle.sample_distribution(d, chunk[1], moduli, n, "uniform", 0.0, gpu.hash_seed_for_matrix(KEY, tag(idx)),
+                                           full_ncol=m, col_offset=chunk[0])
+            v = np.zeros((m, chunk[1], L, n), dtype=np.uint64)
+            for r in range(d):
+                for cc in range(chunk[1]):
+                    v[r * k:(r + 1) * k, cc] = _eval_slots(P.digits(u[r, cc], moduli, base, dpt), moduli, slots)
+            v_idx = ((v.astype(object) * (np.asarray([idx % int(q) for q in moduli], dtype=object).reshape(1, 1, L, 1))) % q_col).astype(np.uint64)
+            want = P.slot_mul_sum(w_id[:, chunk[0]:chunk[0] + chunk[1]], [w_gy, w_v, w_vx],
+                                  [gy_block(moduli, n, base, dpt, y, d, chunk), v, v_idx], moduli, False)
+            assert np.array_equal(target.to_rns(), want), (bits, level, chunk, idx, y)
+    # the combine kernel alone: the product [top; bottom] as given, every (tower, digit) column of the level
+    rng = np.random.default_rng(2000 + bits + level)
+    prod = _rand(rng, 2 * d, T * m, moduli, n)
+    ys = [int(rng.integers(0, 1 << 62)) * int(rng.integers(1, 1 << 62)) for _ in range(T)]
+    idxs = [int(rng.integers(0, 1 << 63)) * 2 + 1 for _ in range(T)]
+    got = combine(gpu, p, w_id, w_gy, prod, T, 0, m, ys, idxs)
+    for t in range(T):
+        idx_l = np.asarray([idxs[t] % int(q) for q in moduli], dtype=object).reshape(1, 1, L, 1)
+        top, bot = prod[:d, t * m:(t + 1) * m].astype(object), prod[d:, t * m:(t + 1) * m].astype(object)
+        addend = ((w_id.astype(object) + top + idx_l * bot) % q_col).astype(np.uint64)
+        want = P.slot_mul_sum(addend, [w_gy], [gy_block(moduli, n, base, dpt, ys[t], d, (0, m))], moduli, False)
+        assert np.array_equal(got[t], want), (bits, level, t)
+
+
 def combine(gpu, p, w_id, w_gy, prod, T, col_start, c, ys, idxs):
     """gpupoly_matrix_lut_targets_combine over uploaded residues -> the T outputs' residues"""
     from mxx_amd import _ffi

@@ -257,6 +257,47 @@ def test_outputs_equal_the_plain_reference(gpu, oracle, ctx):
             assert np.array_equal(got[s].to_rns(), want), (ctx, chunk, s)
 
 
+@pytest.mark.parametrize("level", [0, 1])
+@pytest.mark.parametrize("bits,base", [(24, 12), (51, 17)])
+def test_operands_below_the_top_level_equal_the_plain_reference(gpu, oracle, bits, base, level):
+    """Every matrix of the call at level 0 / 1 of a three-limb context (the refusal list below only shows that MIXED levels
+    are turned away): m_g = d * dpt * (level + 1) with dpt from the CONTEXT's crt_bits (one width per basis here, so plainref
+    derives the same dpt from the truncated basis), U_s sampled in limbs 0..level only, the plain reference above at
+    moduli[: level + 1]; into fresh outputs and into a column block of wider ones, and the combine entry with the digits given."""
+    n, d, S, r = 16, 2, 3, 2
+    p = make_params(gpu, oracle, n, 3, bits, base)
+    M, moduli = gpu.GpuDCRTPolyMatrix, p.moduli()[: level + 1]
+    L, dpt = level + 1, -(-p.crt_bits() // base)
+    assert P.digits_per_tower(moduli, base) == dpt
+    k = L * dpt
+    m_g, w = d * k, 5
+    slots = list(range(n))
+    rnd = lambda seed, rows, cols: oracle.random_matrix(seed + level, rows, cols, moduli, n)  # noqa: E731
+    cbs_np, czs_np = [rnd(650 + 3 * s, r, w) for s in range(S)], [rnd(660 + 3 * s, r, m_g) for s in range(S)]
+    cbs, czs = [M.from_rns(p, a, True) for a in cbs_np], [M.from_rns(p, a, True) for a in czs_np]
+    tags = [b"lwe_low_level_" + bytes([48 + s]) for s in range(S)]
+    for chunk in ((0, min(4, m_g)), (k - 1, 2)):
+        khs_np = [rnd(670 + 3 * s, w, chunk[1]) for s in range(S)]
+        khs = [M.from_rns(p, a, True) for a in khs_np]
+        got = M.lwe_lookup(None, cbs, khs, czs, chunk[0], KEY, tags)
+        frame = rnd(680, r, chunk[1] + 3)
+        wide = [M.from_rns(p, frame, True) for _ in range(S)]
+        M.lwe_lookup(wide, cbs, khs, czs, chunk[0], KEY, tags, dst_col=2)
+        vs = []
+        for s in range(S):
+            u = oracle.sample_distribution(d, chunk[1], moduli, n, "uniform", 0.0, gpu.hash_seed_for_matrix(KEY, tags[s]), full_ncol=m_g,
+                                           col_offset=chunk[0])
+            vs.append(digits_eval(u, moduli, base, dpt, slots))
+            want = P.slot_mul_sum(None, [cbs_np[s], czs_np[s]], [khs_np[s], vs[s]], moduli, False)
+            assert got[s].level == level and got[s].is_ntt and np.array_equal(got[s].to_rns(), want), (bits, level, chunk, s)
+            placed = frame.copy()
+            placed[:, 2:2 + chunk[1]] = want
+            assert np.array_equal(wide[s].to_rns(), placed), (bits, level, chunk, s, "a block of a wider output")
+        given = M.lwe_lookup_combine(None, cbs, khs, czs, M.from_rns(p, np.concatenate(vs, axis=1), True), chunk[0])
+        for s in range(S):
+            assert given[s] == got[s], (bits, level, chunk, s)
+
+
 # ---------------------------------------------------------------------------------------------------
 # 3. the combine entry alone in every width class
 # ---------------------------------------------------------------------------------------------------

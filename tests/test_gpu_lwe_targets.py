@@ -167,6 +167,52 @@ def test_targets_equal_the_plain_reference(gpu, oracle, ctx):
             assert np.array_equal(target.to_rns(), want), (ctx, chunk, entry, x, y)
 
 
+@pytest.mark.parametrize("level", [0, 1])
+@pytest.mark.parametrize("bits,base", [(24, 12), (51, 17)])
+def test_operands_below_the_top_level_equal_the_plain_reference(gpu, oracle, bits, base, level):
+    """Both operands and the outputs at level 0 / 1 of a three-limb context: m = d * dpt * (level + 1) with dpt from the
+    CONTEXT's crt_bits (one width per basis here, so plainref derives the same dpt from the truncated basis), the hashed
+    samples of limbs 0..level only, and the plain reference above handed moduli[: level + 1]; then the combine alone."""
+    n, d, T = 16, 2, 3
+    p = make_params(gpu, oracle, n, 3, bits, base)
+    M, moduli = gpu.GpuDCRTPolyMatrix, p.moduli()[: level + 1]
+    L, dpt = level + 1, -(-p.crt_bits() // base)
+    assert P.digits_per_tower(moduli, base) == dpt
+    k = L * dpt
+    m = d * k
+    slots = list(range(n))
+    a_z, a_lt = oracle.random_matrix(540 + level, d, m, moduli, n), oracle.random_matrix(545 + level, d, m, moduli, n)
+    g_az, g_alt = M.from_rns(p, a_z, True), M.from_rns(p, a_lt, True)
+    G = gadget_slots(moduli, base, n, d)
+    tag = lambda entry: f"lwe_low_level_{entry}".encode("ascii")  # noqa: E731
+    for chunk in ((0, min(4, m)), (k - 1, 2)):
+        cols = slice(chunk[0], chunk[0] + chunk[1])
+        rows = rows_of(moduli, 20)[7:7 + T]
+        got = M.lwe_targets(g_az, g_alt, chunk[0], chunk[1], [y for _, _, y in rows], [x for _, x, _ in rows], KEY, [tag(e) for e, _, _ in rows])
+        for (entry, x, y), target in zip(rows, got):
+            assert target.level == level and target.is_ntt and target.size() == (d, chunk[1])
+            u = oracle.sample_distribution(d, chunk[1], moduli, n, "uniform", 0.0, gpu.hash_seed_for_matrix(KEY, tag(entry)),
+                                           full_ncol=m, col_offset=chunk[0])
+            v = np.zeros((m, chunk[1], L, n), dtype=np.uint64)
+            for r in range(d):
+                for cc in range(chunk[1]):
+                    v[r * k:(r + 1) * k, cc] = _eval_slots(P.digits(u[r, cc], moduli, base, dpt), moduli, slots)
+            ext = minus(a_z, times_constant(G, x, moduli), moduli)
+            addend = minus(a_lt[:, cols], times_constant(G[:, cols], y, moduli), moduli)
+            want = P.slot_mul_sum(addend, [ext], [v], moduli, True)
+            assert np.array_equal(target.to_rns(), want), (bits, level, chunk, entry, x, y)
+    rng = np.random.default_rng(2100 + bits + level)
+    digits, prod = _rand(rng, m, T * m, moduli, n), _rand(rng, d, T * m, moduli, n)
+    ys = [int(rng.integers(0, 1 << 62)) * int(rng.integers(1, 1 << 62)) for _ in range(T)]
+    xs = [int(rng.integers(0, 1 << 63)) * 2 + 1 for _ in range(T)]
+    got = combine(gpu, p, a_lt, digits, prod, T, 0, m, ys, xs)
+    for t in range(T):
+        block = slice(t * m, (t + 1) * m)
+        addend = minus(minus(a_lt, times_constant(G, ys[t], moduli), moduli), prod[:, block], moduli)
+        want = P.slot_mul_sum(addend, [times_constant(G, xs[t], moduli)], [digits[:, block]], moduli, False)
+        assert np.array_equal(got[t], want), (bits, level, t)
+
+
 # ---------------------------------------------------------------------------------------------------
 # 4. the combine alone at the accumulator's bound, in every width class
 # ---------------------------------------------------------------------------------------------------

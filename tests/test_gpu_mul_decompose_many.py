@@ -140,6 +140,48 @@ def test_bit_exact_against_the_existing_entry_points_and_inputs_untouched(gpu, o
         assert raw_same(outs[j], sequence(l_, rhs, a_, s_)), f"operand {j}"
 
 
+@pytest.mark.parametrize("level", [0, 1])
+@pytest.mark.parametrize("rhs_eval", [False, True], ids=["rhs_coeff", "rhs_eval"])
+@pytest.mark.parametrize("ring", ["n16_18bit", "n256_51bit"])
+def test_a_level_below_the_top(gpu, oracle, ring, rhs_eval, level):
+    """Every matrix of the call at level 0 / 1 of the three-limb rings, through the raw entry (the mirror takes k from the
+    context): k = dpt * (level + 1) digit rows per source row with dpt from the CONTEXT's crt_bits - the same number in
+    these same-width bases as oracle.decompose derives from the truncated basis it is handed."""
+    n, depth, bits, base = RINGS[ring]
+    p = make_params(gpu, oracle, n, depth, bits, base)
+    M, moduli = gpu.GpuDCRTPolyMatrix, p.moduli()[: level + 1]
+    dpt = -(-p.crt_bits() // base)
+    assert level < depth - 1 and oracle.digits_per_tower(moduli, base) == dpt
+    k = dpt * (level + 1)
+    rows = [3, 1, 0, 9, 2]
+    B = oracle.random_matrix(930 + level, RHS_ROWS, RHS_COLS, moduli, n)
+    D = oracle.matrix_ntt(oracle.decompose(B, moduli, base), moduli)
+    S = oracle.random_matrix(931 + level, sum(rows), RHS_ROWS * k, moduli, n)
+    A = oracle.random_matrix(932 + level, sum(rows), RHS_COLS, moduli, n)
+    sc = oracle.random_matrix(933 + level, 1, 1, moduli, n)
+    prod = oracle.matmul(S, D, moduli)
+    lhss, adds, scs, want, r0 = [], [], [], [], 0
+    for j, h in enumerate(rows):
+        sl = slice(r0, r0 + h)
+        r0 += h
+        lhss.append(M.from_rns(p, S[sl], True))
+        adds.append(None if j % 3 == 0 else M.from_rns(p, A[sl], True))
+        scs.append(M.from_rns(p, sc, True) if j % 3 == 2 else None)
+        w = prod[sl]
+        if j % 3 == 1:
+            w = add_mod(w, A[sl], moduli)
+        elif j % 3 == 2:
+            w = add_mod(w, addend_term(A[sl], sc[0, 0], moduli), moduli)
+        want.append(w)
+    rhs = M.from_rns(p, oracle.matrix_ntt(B, moduli) if rhs_eval else B, rhs_eval)
+    outs = [M(p, h, RHS_COLS, level, False) for h in rows]
+    assert raw_call(outs, lhss, adds, scs, rhs, base) == 0
+    for j, (o, w) in enumerate(zip(outs, want)):
+        o.is_ntt = True  # tagged EVAL by the entry: the store refuses any other tag
+        assert o.level == level and np.array_equal(o.to_rns(), w), f"operand {j} of {rows} at level {level}"
+    assert np.array_equal(rhs.to_rns(), oracle.matrix_ntt(B, moduli) if rhs_eval else B)
+
+
 # shapes that reach the tiles the small cases do not: 64-bit words' 4x4x2 / 2x4x2 / 1x4x2 / 2x2x1 register tiles (chosen by
 # how far rows x columns fill the chip) and, for 32-bit words, a digit matrix above 256 MB under ONE row tile (streamed with
 # non-temporal loads) and under several.  The operands are samples (PACKED24 where the ring allows it: unpacked first).

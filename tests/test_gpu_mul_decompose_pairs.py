@@ -164,6 +164,43 @@ def test_mixed_forms_of_the_right_operands_in_one_call(gpu, oracle, ring):
         assert rhss[j].is_ntt == (j % 2 == 1)
 
 
+@pytest.mark.parametrize("level", [0, 1])
+@pytest.mark.parametrize("ring", ["n16_18bit", "n256_51bit"])
+def test_a_level_below_the_top(gpu, oracle, ring, level):
+    """Every matrix of the call at level 0 / 1 of the three-limb rings, through the raw entry (the mirror takes k from the
+    context): k = dpt * (level + 1) with dpt from the CONTEXT's crt_bits, the module's CPU restatement at the truncated basis
+    (same-width limbs: oracle.decompose derives the same dpt from it); own right operand per j, both forms, scalar and
+    addend mixed, both signs."""
+    n, depth, bits, base = RINGS[ring]
+    p = make_params(gpu, oracle, n, depth, bits, base)
+    M, moduli = gpu.GpuDCRTPolyMatrix, p.moduli()[: level + 1]
+    dpt = -(-p.crt_bits() // base)
+    assert level < depth - 1 and oracle.digits_per_tower(moduli, base) == dpt
+    k = dpt * (level + 1)
+    rows = [2, 1, 0, 9, 3]
+    sc = oracle.random_matrix(943, 1, 1, moduli, n)
+    for negate in (0, 1):
+        lhss, adds, scs, rhss, outs, want = [], [], [], [], [], []
+        for j, h in enumerate(rows):
+            B = oracle.random_matrix(940 + 7 * j + level, RHS_ROWS, RHS_COLS, moduli, n)
+            D = oracle.matrix_ntt(oracle.decompose(np.ascontiguousarray(B[:, COL_START:COL_START + WIN]), moduli, base), moduli)
+            S = oracle.random_matrix(941 + 7 * j + level, h, RHS_ROWS * k, moduli, n)
+            A = oracle.random_matrix(942 + 7 * j + level, h, WIN, moduli, n)
+            lhss.append(M.from_rns(p, S, True))
+            rhss.append(M.from_rns(p, oracle.matrix_ntt(B, moduli) if j % 2 else B, j % 2 == 1))
+            w = oracle.matmul(S, D, moduli) if h else np.zeros((0, WIN, level + 1, n), dtype=np.uint64)
+            scs.append(M.from_rns(p, sc, True) if j % 2 == 0 else None)
+            if j % 2 == 0:
+                w = mulmod(w, sc[0, 0], moduli)
+            adds.append(M.from_rns(p, A, True) if j % 3 != 0 else None)
+            want.append(combine(A if j % 3 != 0 else None, w, negate, moduli))
+            outs.append(M(p, h, WIN, level, False))
+        assert raw_call(outs, adds, lhss, rhss, scs, COL_START, base, negate) == 0
+        for j, (o, w) in enumerate(zip(outs, want)):
+            o.is_ntt = True  # tagged EVAL by the entry: the store refuses any other tag
+            assert o.level == level and np.array_equal(o.to_rns(), w), f"operand {j} of {rows} at level {level}, negate={negate}"
+
+
 @pytest.mark.parametrize("rhs_eval", [False, True], ids=["rhs_coeff", "rhs_eval"])
 @pytest.mark.parametrize("ring", list(RINGS))
 def test_bit_exact_against_the_existing_entry_points_and_inputs_untouched(gpu, oracle, ring, rhs_eval):

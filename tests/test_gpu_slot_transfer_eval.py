@@ -295,6 +295,46 @@ def test_outputs_equal_the_plain_reference_in_the_original_association(gpu, orac
             assert np.array_equal(got[s].to_rns(), want), (ctx, chunk, s)
 
 
+@pytest.mark.parametrize("level", [0, 1])
+@pytest.mark.parametrize("bits,base", [(24, 12), (51, 17)])
+def test_operands_below_the_top_level_equal_the_plain_reference(gpu, oracle, bits, base, level):
+    """Every matrix of the call at level 0 / 1 of a three-limb context (the refusal list below only shows that MIXED levels
+    are turned away): m_g = d * dpt * (level + 1) with dpt from the CONTEXT's crt_bits (one width per basis here, so plainref
+    derives the same dpt from the truncated basis), A_s sampled in limbs 0..level only, x^shift from the roots of limbs
+    0..level, and plain_eval above at moduli[: level + 1]; one and two terms per output, the combine entry with the digits
+    given."""
+    n, d, r, w0, w1 = 16, 2, 2, 3, 4
+    p = make_params(gpu, oracle, n, 3, bits, base)
+    M, moduli = gpu.GpuDCRTPolyMatrix, p.moduli()[: level + 1]
+    L, dpt = level + 1, -(-p.crt_bits() // base)
+    assert P.digits_per_tower(moduli, base) == dpt
+    k = L * dpt
+    m_g = d * k
+    slots = list(range(n))
+    rnd = lambda seed, rows, ncols: oracle.random_matrix(seed + level, rows, ncols, moduli, n)  # noqa: E731
+    up = lambda a: M.from_rns(p, a, True)  # noqa: E731
+    c_b0 = rnd(850, r, w0)
+    specs = [[(0, 1, full_modulus(moduli) - 1)], [(3, 3, 5), (2 * n - 1, (1 << 32) - 1, (1 << 70) + 9)]]  # (shift, kappa, mu) per term
+    terms_np = [[(rnd(860 + 10 * s + 2 * t, r, m_g), rnd(861 + 10 * s + 2 * t, r, w1)) + spec for t, spec in enumerate(ts)] for s, ts in enumerate(specs)]
+    terms = [[(up(c_in), up(mid), shift, kappa, mu) for c_in, mid, shift, kappa, mu in ts] for ts in terms_np]
+    tags = [b"slot_low_level_" + bytes([48 + s]) for s in range(2)]
+    g_c_b0 = up(c_b0)
+    for chunk in ((0, min(4, m_g)), (k - 1, 2)):
+        pg_np, p1_np = [rnd(880 + s, w0, chunk[1]) for s in range(2)], [rnd(890 + s, w1, chunk[1]) for s in range(2)]
+        pgs, p1s = [up(a) for a in pg_np], [up(a) for a in p1_np]
+        got = M.slot_transfer_eval(None, g_c_b0, pgs, p1s, terms, chunk[0], KEY, tags)
+        ds = []
+        for s in range(2):
+            u = oracle.sample_distribution(d, chunk[1], moduli, n, "uniform", 0.0, gpu.hash_seed_for_matrix(KEY, tags[s]), full_ncol=m_g,
+                                           col_offset=chunk[0])
+            ds.append(digits_eval(u, moduli, base, dpt, slots))
+            want = plain_eval(c_b0, pg_np[s], p1_np[s], ds[s], terms_np[s], moduli, n)
+            assert got[s].level == level and got[s].is_ntt and np.array_equal(got[s].to_rns(), want), (bits, level, chunk, s)
+        given = M.slot_transfer_eval_combine(None, g_c_b0, pgs, p1s, terms, up(np.concatenate(ds, axis=1)), chunk[0])
+        for s in range(2):
+            assert given[s] == got[s], (bits, level, chunk, s)
+
+
 # ---------------------------------------------------------------------------------------------------
 # 4. the combine entry alone in every width class: the lazy windows of both kernels
 # ---------------------------------------------------------------------------------------------------

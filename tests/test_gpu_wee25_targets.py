@@ -247,6 +247,54 @@ def test_targets_equal_the_plain_reference(gpu, oracle, ctx):
         assert {q for _, q in hit_parts} == {0, 1}
 
 
+@pytest.mark.parametrize("level", [0, 1])
+@pytest.mark.parametrize("bits,base", [(24, 12), (51, 17)])
+def test_operands_below_the_top_level_equal_the_plain_reference(gpu, oracle, bits, base, level):
+    """T_bottom and the outputs at level 0 / 1 of a three-limb context: k = dpt * (level + 1) with dpt from the CONTEXT's
+    crt_bits (one width per basis here, so plainref derives the same dpt from the truncated basis), m_g = s k and m_b = s (k + 2)
+    at the level, W sampled in limbs 0..level only, and the plain reference above handed moduli[: level + 1]; the product
+    entry with the stacked W given must write the same words."""
+    from types import SimpleNamespace
+
+    from mxx_amd.commit import Wee25Commit
+
+    n, s = 16, 2
+    p = make_params(gpu, oracle, n, 3, bits, base)
+    M, moduli = gpu.GpuDCRTPolyMatrix, p.moduli()[: level + 1]
+    L, dpt = level + 1, -(-p.crt_bits() // base)
+    assert P.digits_per_tower(moduli, base) == dpt
+    k = L * dpt
+    w = SimpleNamespace(secret_size=s, log_base_q=k, m_g=s * k, m_b=s * (k + 2))  # the sizes of a Wee25Commit at the level
+    m_b = w.m_b
+    tb = oracle.random_matrix(940 + level, m_b, 3 * m_b, moduli, n)
+    t_bottom = M.from_rns(p, tb, True)
+    slots = list(range(n))
+    G = gadget_slots(moduli, base, n, s)
+    idxs = [dpt - 1, w.m_g + k + 1, 2 * w.m_g + w.m_g - 1]  # block groups 0, 1, 2; rows 0, 1 and s - 1; not consecutive
+    tags = [Wee25Commit.tag(i) for i in idxs]
+    got = M.wee25_targets(t_bottom, 0, 2, s, idxs, KEY, tags)
+    hits, stacked = 0, []
+    for t, idx in enumerate(idxs):
+        w_eval = _eval_slots(oracle.sample_distribution(s, m_b, moduli, n, "uniform", 0.0, gpu.hash_seed_for_matrix(KEY, tags[t])), moduli, slots)
+        stacked.append(w_eval)
+        for part in range(2):
+            rows = literal_rows(w, idx, part, moduli, base, n)
+            hits += bool(rows.any())
+            j = np.zeros((s * k, m_b, L, n), dtype=np.uint64)
+            for i in range(s):
+                for cc in range(m_b):
+                    j[i * k:(i + 1) * k, cc] = _eval_slots(P.digits(rows[i, cc], moduli, base, dpt), moduli, slots)
+            gj = P.slot_mul_sum(None, [G], [j], moduli, False)  # G_s J
+            want = P.slot_mul_sum(gj, [w_eval], [tb[:, part * m_b:(part + 1) * m_b]], moduli, True)
+            assert got[t][part].level == level and got[t][part].is_ntt
+            assert np.array_equal(got[t][part].to_rns(), want), (bits, level, idx, part)
+    assert hits >= 2  # the constants of at least two blocks land inside the window
+    given = M.wee25_targets_product(M.from_rns(p, np.concatenate(stacked, axis=0), True), t_bottom, 0, 2, s, idxs)
+    for t in range(len(idxs)):
+        for part in range(2):
+            assert given[t][part] == got[t][part], (bits, level, t, part)
+
+
 # ---------------------------------------------------------------------------------------------------
 # 4. the product alone past the accumulator's window, in every width class
 # ---------------------------------------------------------------------------------------------------
