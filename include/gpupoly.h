@@ -932,6 +932,52 @@ int gpupoly_matrix_slot_transfer_eval_combine(GpuMatrix *const *outs, size_t nou
                                               const GpuMatrix *const *b1_preimages, const GpuSlotTerm *terms,
                                               const size_t *term_offsets, const uint64_t *mu_words, size_t words_per_mu,
                                               size_t col_start, uint32_t base_bits, const GpuMatrix *digits);
+/* ---- BGG+ encodings for many slots (extension).  BGGPolyEncodingSampler::sample
+ * (src/bgg/sampler.rs:224-364; on the device src/bgg/sampler_gpu.rs:81-172) is a plain loop over the slots that per slot
+ * (src/bgg/sampler_gpu.rs:110-160) loads the slot's secret mask from compact bytes, forms t = s S_slot, samples a fresh
+ * Gaussian 1 x P m error, builds the plaintext row (from_poly_vec_row), multiplies t A_all, multiplies t G against a fully
+ * filled gadget, takes the tensor product with the plaintexts, subtracts, adds, slices the row into P vectors and stores
+ * compact bytes; BGGEncodingSampler::sample (src/bgg/sampler.rs:133-182) is the same sequence for one slot with t = s.  With
+ * d the secret size, k = dpt * (level + 1), dpt = ceil(crt_bits / base_bits), m = d * k and P = 1 + the number of plaintexts:
+ *   outs[i][sigma, :] = t_sigma A_i  -  pt[sigma][i] o (t_sigma G)  +  e_sigma[:, i m .. (i + 1) m),   i < P,  pt[sigma][0] = 1,
+ *   secrets      S x d, EVAL: row sigma is t_sigma (the plain encoding sampler: S = 1 and the row is s itself)
+ *   pubkeys[i]   d x m, EVAL; the same matrix may stand for several inputs
+ *   plaintexts   S x (P - 1), EVAL, entry (sigma, i - 1) input i's plaintext in slot sigma; NULL exactly when P == 1
+ *   outs[i]      S x m, made by the caller; tagged EVAL on success
+ *   sigma == 0: no error, nothing is sampled, `seeds` may be NULL; sigma > 0: e_sigma is, bit for bit, what
+ *   gpu_matrix_sample_distribution(GPU_MATRIX_DIST_GAUSS, sigma, seeds[sigma]) writes into a 1 x P m matrix.
+ * (t G)[c] is t[c / k] times a constant that is non-zero in the one limb tower(c), where it is (2^base_bits)^e mod q
+ * (gpupoly_matrix_mul_gadget's weights), so every output word is ONE lazy accumulator: the error residue (or 0) first, the
+ * d products, and - in the limb the gadget hits, decided per workgroup - the term (q - pt t mod q) w; folded every lazy_terms
+ * terms wherever they fall, reduced once, stored once.  Exact arithmetic on canonical residues: the result equals the
+ * reference's sequence bit for bit.  One context and one level, which may be below the top.
+ * The slots go in groups whose scratch - per slot the error row 1 x P m and the int64 samples staged for it - stays under
+ * 1 GiB (MXX_HIP_BGG_ENCODE_BUDGET=<bytes> overrides the cap).  Per group: the launches of gpupoly_matrix_sample_gauss_blocks
+ * for Sg seeds (STACKED layout, into scratch of the context's allocator), ONE staged copy of the table (the outs and pubkeys
+ * pointers, the gadget weights) and ONE main kernel, whatever S and P; with sigma == 0 one copy and one kernel.  A lane owns
+ * up to 4 slots x one column of one input in one limb, 16 bytes per load and store (one word where a limb vector is
+ * narrower), and loads the d words of A_i[., c] once for the tile's slots.  Scratch is released stream-ordered; the host
+ * does not block; PACKED24 operands are unpacked first; P = 0, S = 0, d = 0 and m = 0 succeed with nothing launched.
+ * Overlap: an outs[i] must overlap no operand and no other output, row views included; disjoint views of one parent are
+ * accepted (the message contains "overlap").
+ * Refused, with nothing launched and every output (residues AND tag) untouched, everything checked before the first launch,
+ * the message naming this entry: a null array or entry; plaintexts NULL with P > 1 or given with P == 1; a context, level or
+ * shape mismatch (the input in the message); an operand not in EVAL form; m != d k; base_bits of 0 or >= 63; a sigma that is
+ * negative or not finite; seeds NULL with sigma > 0; S > 2^20; the overlaps above.  Refused likewise with "unsupported" in
+ * the text, as the Gaussian block sampler refuses them, and judged after everything above so that a mistake in the
+ * operands is named first: sigma > 0 on a ring of n < 128, and sigma > 0 on a context created under
+ * MXX_HIP_RNG_COMPAT=reference.  The outputs are tagged once the last group has been enqueued: a call that fails after its
+ * checks (an allocation, a launch) returns non-zero and leaves the tags as they were.                                    */
+int gpupoly_matrix_bgg_encode_slots(GpuMatrix *const *outs, size_t ninputs_P, const GpuMatrix *secrets,
+                                    const GpuMatrix *const *pubkeys, const GpuMatrix *plaintexts, uint32_t base_bits,
+                                    double sigma, const GpuRngSeed *seeds);
+/* Test instrument, and the mirror's path where the block sampler is "unsupported": the same with the errors GIVEN -
+ * `errors` is S x (P * m), EVAL, or NULL for none - instead of sampled: the table copy and the main kernel alone, one group
+ * whatever S.  It lets a test reach the lazy accumulator's bound with errors no sampler produces.  Arguments, overlap rule
+ * and refusals as above (`errors` counts as an operand; no sigma, no seeds, any ring and any RNG keying).                */
+int gpupoly_matrix_bgg_encode_slots_combine(GpuMatrix *const *outs, size_t ninputs_P, const GpuMatrix *secrets,
+                                            const GpuMatrix *const *pubkeys, const GpuMatrix *plaintexts,
+                                            uint32_t base_bits, const GpuMatrix *errors);
 /* Exact scale-and-round of every coefficient (extension): coefficient k of out[i][j] becomes
  *   floor((t * c + h) / Q) mod t,   h = round_half ? floor(Q/2) : 0,
  * c the coefficient of in[i][j] as coeffs() gives it (in [0, Q)), Q the context's FULL modulus; written as its residue

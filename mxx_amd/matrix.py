@@ -2587,6 +2587,50 @@ class GpuDCRTPolyMatrix:
                                                           terms_by_out, col_start, dst_col, digits.raw)
 
     @staticmethod
+    def _bgg_encode_call(entry: str, outs, secrets, pubkeys, plaintexts, *last) -> list:
+        """`entry(outs, P, secrets, pubkey array, plaintexts, base, *last)`; `outs` None: P fresh S x m outputs"""
+        pubkeys = list(pubkeys)
+        count = len(pubkeys)
+        if outs is None:
+            outs = [GpuDCRTPolyMatrix(secrets.params, secrets.nrow, pk.ncol, secrets.level, True) for pk in pubkeys]
+        else:
+            outs = list(outs)
+            assert len(outs) == count, "bgg_encode_slots: one output per public key"
+        if count == 0:
+            return outs
+        for out in outs:
+            out._touch()
+        st = getattr(_ffi.lib(), entry)(GpuDCRTPolyMatrix._raw_array(outs), count, secrets.raw, GpuDCRTPolyMatrix._raw_array(pubkeys),
+                                        None if plaintexts is None else plaintexts.raw, secrets.params.base_bits(), *last)
+        check_status(st, entry)
+        for out in outs:
+            out.is_ntt = True
+        return outs
+
+    @staticmethod
+    def bgg_encode_slots(secrets, pubkeys, plaintexts, sigma: float, seeds, outs=None) -> list:
+        """The BGG+ encoding vectors of len(pubkeys) inputs in S = secrets.nrow slots in one call
+        (gpupoly_matrix_bgg_encode_slots):
+            outs[i][s, :] = secrets[s, :] pubkeys[i] - plaintexts[s, i - 1] o (secrets[s, :] G) + e_s[:, i m .. (i + 1) m),
+        secrets S x d (row s is the slot's secret t_s), pubkeys[i] d x m, plaintexts S x (len(pubkeys) - 1) or None with one
+        input (input 0's plaintext is the constant 1), e_s = sample_distribution(params, 1, len(pubkeys) * m, GAUSS, sigma,
+        seeds[s]); sigma == 0: no error and `seeds` is not read.  `outs` None: fresh S x m matrices.  Raises GpuPolyError
+        (text contains "unsupported") with sigma > 0 for rings below n = 128 and under MXX_HIP_RNG_COMPAT=reference."""
+        arr = None
+        if sigma > 0:
+            seeds = list(seeds)
+            assert len(seeds) == secrets.nrow, "bgg_encode_slots: one seed per slot"
+            arr = (GpuRngSeed * max(len(seeds), 1))(*seeds)
+        return GpuDCRTPolyMatrix._bgg_encode_call("gpupoly_matrix_bgg_encode_slots", outs, secrets, pubkeys, plaintexts, float(sigma), arr)
+
+    @staticmethod
+    def bgg_encode_slots_combine(secrets, pubkeys, plaintexts, errors, outs=None) -> list:
+        """`bgg_encode_slots` with the errors given as the S x (len(pubkeys) * m) EVAL matrix `errors`, or None for none
+        (gpupoly_matrix_bgg_encode_slots_combine): a test instrument, and the path for errors of the plain sampler."""
+        return GpuDCRTPolyMatrix._bgg_encode_call("gpupoly_matrix_bgg_encode_slots_combine", outs, secrets, pubkeys, plaintexts,
+                                                  None if errors is None else errors.raw)
+
+    @staticmethod
     def sample_p1_full_cached_segments(cache: GpuP1CovarianceCache, tp2, seeds, seg_cols) -> "GpuDCRTPolyMatrix":
         """`sample_p1_full_cached` over column segments with a seed each (tp2 is taken to the coefficient domain in place)."""
         out = GpuDCRTPolyMatrix.new_empty(tp2.params, tp2.nrow, tp2.ncol)
