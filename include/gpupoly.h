@@ -978,6 +978,68 @@ int gpupoly_matrix_bgg_encode_slots(GpuMatrix *const *outs, size_t ninputs_P, co
 int gpupoly_matrix_bgg_encode_slots_combine(GpuMatrix *const *outs, size_t ninputs_P, const GpuMatrix *secrets,
                                             const GpuMatrix *const *pubkeys, const GpuMatrix *plaintexts,
                                             uint32_t base_bits, const GpuMatrix *errors);
+/* ---- the message stream of the commitment-based lookup (extension).  The commit evaluator's stream
+ * (build_msg_stream_for_lut_eval, src/lookup/commit_eval.rs:417-522) holds one d x m_b message block per LUT row of every
+ * lookup gate and builds each on its own (:461-517): two hash samples, a gadget fill with a mul_scalar, a zero fill and a
+ * concat_columns, a d x m_b * m_b x m_b product, a constant upload with a mul_scalar, a decomposition, a d x m_g * m_g x m_b
+ * product and three additions or subtractions - per row, again in setup, commit_all_lut_matrices and every public_lookup.
+ *
+ * The message blocks of T LUT rows of `ngates` gates.  With d the secret size, k = dpt * (level + 1), m_g = d * k,
+ * m_b = d * (k + 2), g = gate_of_row[t]:
+ *   R_t        = the d x m_b uniform matrix under hash_seed_for_matrix(key, tag_t)
+ *   canceler_t = (b_1 * V_t + R_t) o iota_t,    V_t = verifier[:, vslot[t] * m_b .. (vslot[t] + 1) * m_b),
+ *                                               iota_t = (idx[t] + 1)^-1 mod q_l in limb l
+ *   outs[t]    = [ a_outs[g] - G_d o y_t | 0_{d x (m_b - m_g)} ] + R_t - pubkey_sums[g] * G^-1(canceler_t),
+ * y_t a constant polynomial.
+ *   outs[t]          d x m_b, made by the caller, tagged EVAL on success
+ *   b_1              d x m_b, EVAL
+ *   verifier         m_b x (nV * m_b), EVAL, any nV >= 1; the library does not tie vslot[t] to idx[t]
+ *   pubkey_sums[g]   d x m_g, EVAL: A_in,g + A_one,g
+ *   a_outs[g]        d x m_g, EVAL
+ *   gate_of_row      host memory: T gate numbers below ngates
+ *   y_words          host memory: T integers of words_per_y little-endian 64-bit words each, reduced mod every q_l
+ *                    (gpupoly_matrix_load_coeff_words's rule; from_elem_to_constant of the reference)
+ *   idx              host memory: T LUT row indices
+ *   tags             T tags (GpuHashTags above) naming R_t: "R_<g>_" followed by the decimal index is the INDEXED_DECIMAL
+ *                    form for a consecutive run of one gate.  The library does not tie tags[t] to idx[t]
+ * One context and one level (it may be below the top; k follows it).  Everything is exact arithmetic on canonical residues,
+ * so the result equals the reference's sequence bit for bit.  Column (j, tw, e) of G_d o y_t is (y_t mod q_tw) B^e mod q_tw in
+ * every slot of limb tw of row j and zero elsewhere; G is never filled.  One product of b_1 - as it is, no copy - against
+ * the verifier gives every b_1 * V_t of the call.  The rows go in groups whose digit scratch m_g x (Tg * m_b) stays under
+ * 1 GiB, at most 2^20 rows (MXX_HIP_COMMIT_LUT_BUDGET=<bytes> lowers the cap); per group: one staged copy of the rows' table
+ * (output and operand pointers, vslot, iota_t mod q_l and (y_t mod q_tw) B^e mod q_tw, computed on the host), the stacked
+ * block sample [R_0 | R_1 | ...], one elementwise kernel C[:, t-th block] = (BV[:, vslot_t block] + R_t) o iota_t, the
+ * decomposition of the d x (Tg * m_b) matrix C (inverse transform, digits, forward transforms), and ONE register-tiled
+ * product whose left operand is chosen per row - pubkey_sums[g] read in place - and whose epilogue negates the reduced sum
+ * canonically (q - r, 0 stays 0), adds R_t's word and, in columns below m_g, a_outs[g]'s word and the negated gadget constant
+ * in the one limb and row where it is non-zero, and stores every word once, straight into outs[t]; where the modulus leaves
+ * room for fewer terms the sums are reduced in every lazy window.  The launches of a group depend on neither T nor ngates:
+ * no per-row upload, launch or synchronisation.  Scratch comes from the context's allocator and is released stream-ordered;
+ * the host does not block; PACKED24 operands are unpacked first; T = 0 succeeds with nothing launched.
+ * Overlap: an outs[t] must overlap no operand and no other output, row views included (the message contains "overlap").
+ * Refused, with nothing launched and every output (residues AND tag) untouched, everything checked for every t before the
+ * first launch, the message naming this entry: a null array with T > 0, a null operand or outs[t]; ngates == 0 with T > 0;
+ * gate_of_row[t] >= ngates; vslot[t] >= nV; a verifier whose column count is not a positive multiple of its row count; a
+ * context, level or shape mismatch (b_1 and outputs d x m_b, verifier m_b rows, per-gate operands d x m_g); an operand not
+ * in EVAL form; words_per_y == 0; base_bits of 0 or >= 63; idx[t] + 1 = 0 mod q_l for some limb (no inverse; the message
+ * names the row); everything gpupoly_hash_seeds refuses of `tags`; the overlaps above.  Refused likewise with "unsupported"
+ * in the text: a context created under MXX_HIP_RNG_COMPAT=reference.                                                   */
+int gpupoly_matrix_commit_lut_messages(GpuMatrix *const *outs, size_t nrows_T, const GpuMatrix *b_1, const GpuMatrix *verifier,
+                                       const uint64_t *vslot, const GpuMatrix *const *pubkey_sums,
+                                       const GpuMatrix *const *a_outs, size_t ngates, const uint32_t *gate_of_row,
+                                       uint32_t base_bits, const uint64_t *y_words, size_t words_per_y, const uint64_t *idx,
+                                       const GpuHashTags *tags);
+/* Test instrument: the combine kernel of gpupoly_matrix_commit_lut_messages alone, with [R_0 | R_1 | ...] - `r_stacked` is
+ * d x (T * m_b), EVAL, row t's columns at t * m_b - and the digits - `digits` is m_g x (T * m_b), EVAL, likewise - GIVEN
+ * instead of sampled, multiplied and decomposed:
+ *   outs[t] = [ a_outs[g] - G_d o y_t | 0 ] + r_stacked[:, t*m_b .. (t+1)*m_b) - pubkey_sums[g] * digits[:, t*m_b .. (t+1)*m_b).
+ * It lets a test reach the lazy accumulator's bound with operands no sampler produces (every residue q - 1).  One group
+ * whatever T; arguments, overlap rule and refusals as above (`r_stacked` and `digits` count as operands; no verifier, vslot,
+ * idx or tags, any keying).                                                                                            */
+int gpupoly_matrix_commit_lut_messages_combine(GpuMatrix *const *outs, size_t nrows_T, const GpuMatrix *r_stacked,
+                                               const GpuMatrix *digits, const GpuMatrix *const *pubkey_sums,
+                                               const GpuMatrix *const *a_outs, size_t ngates, const uint32_t *gate_of_row,
+                                               uint32_t base_bits, const uint64_t *y_words, size_t words_per_y);
 /* Exact scale-and-round of every coefficient (extension): coefficient k of out[i][j] becomes
  *   floor((t * c + h) / Q) mod t,   h = round_half ? floor(Q/2) : 0,
  * c the coefficient of in[i][j] as coeffs() gives it (in [0, Q)), Q the context's FULL modulus; written as its residue

@@ -58,5 +58,6 @@ from . import ggh15_eval  # noqa: F401,E402
 from . import slot_transfer  # noqa: F401,E402
 from . import commit  # noqa: F401,E402
 from . import bgg  # noqa: F401,E402
+from . import commit_lookup  # noqa: F401,E402
 from . import nested_rns  # noqa: F401,E402
 from .nested_rns import NestedRnsContext  # noqa: F401,E402

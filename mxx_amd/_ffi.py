@@ -196,6 +196,11 @@ SIGNATURES = {
     "gpupoly_matrix_bgg_encode_slots": (C.c_int, [C.POINTER(C.c_void_p), _sz, _vp, C.POINTER(C.c_void_p), _vp, C.c_uint32, C.c_double,
                                         C.POINTER(GpuRngSeed)]),
     "gpupoly_matrix_bgg_encode_slots_combine": (C.c_int, [C.POINTER(C.c_void_p), _sz, _vp, C.POINTER(C.c_void_p), _vp, C.c_uint32, _vp]),
+    "gpupoly_matrix_commit_lut_messages": (C.c_int, [C.POINTER(C.c_void_p), _sz, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_void_p), _sz, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64), _sz,
+                                           C.POINTER(C.c_uint64), C.POINTER(GpuHashTags)]),
+    "gpupoly_matrix_commit_lut_messages_combine": (C.c_int, [C.POINTER(C.c_void_p), _sz, _vp, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                   _sz, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64), _sz]),
     "gpupoly_matrix_sample_p1_full_cached_segments":(C.c_int, [_vp, _vp, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz, _vp]),
     "gpupoly_matrix_gauss_samp_gq_arb_base_segments": (C.c_int, [_vp, C.c_uint32, C.c_double, C.c_double, C.POINTER(GpuRngSeed), C.POINTER(_sz), _sz, _vp]),
     "gpupoly_matrix_concat_columns": (C.c_int, [_vp, C.POINTER(C.c_void_p), _sz]),

@@ -66,6 +66,7 @@ struct EnvSwitches {
     size_t lwe_lookup_budget = 0;  // MXX_HIP_LWE_LOOKUP_BUDGET=<bytes>: scratch cap of a slot group of gpupoly_matrix_lwe_lookup (likewise)
     size_t slot_eval_budget = 0;   // MXX_HIP_SLOT_EVAL_BUDGET=<bytes>: scratch cap of an output group of gpupoly_matrix_slot_transfer_eval (likewise)
     size_t bgg_encode_budget = 0;  // MXX_HIP_BGG_ENCODE_BUDGET=<bytes>: scratch cap of a slot group of gpupoly_matrix_bgg_encode_slots (likewise)
+    size_t commit_lut_budget = 0;  // MXX_HIP_COMMIT_LUT_BUDGET=<bytes>: digit-scratch cap of a row group of gpupoly_matrix_commit_lut_messages (likewise)
     char mul_sum_path = 0;        // MXX_HIP_MUL_SUM_PATH: 0 auto, 't' the term-table tile kernel at every height, 's' products into
                                   // scratch + one combine pass per term above 8 rows (matmul_sum.hip; A/B, tests)
     size_t crt_recompose_chunk_bytes = size_t(256) << 20;  // MXX_HIP_CRT_RECOMPOSE_CHUNK_BYTES=<bytes>: scratch cap of

@@ -300,6 +300,7 @@ void EnvSwitches::load() {
     if (const char *e = std::getenv("MXX_HIP_LWE_LOOKUP_BUDGET")) lwe_lookup_budget = static_cast<size_t>(std::strtoull(e, nullptr, 10));
     if (const char *e = std::getenv("MXX_HIP_SLOT_EVAL_BUDGET")) slot_eval_budget = static_cast<size_t>(std::strtoull(e, nullptr, 10));
     if (const char *e = std::getenv("MXX_HIP_BGG_ENCODE_BUDGET")) bgg_encode_budget = static_cast<size_t>(std::strtoull(e, nullptr, 10));
+    if (const char *e = std::getenv("MXX_HIP_COMMIT_LUT_BUDGET")) commit_lut_budget = static_cast<size_t>(std::strtoull(e, nullptr, 10));
     if (const char *e = std::getenv("MXX_HIP_CRT_RECOMPOSE_CHUNK_BYTES")) {
         const size_t v = static_cast<size_t>(std::strtoull(e, nullptr, 10));
         if (v >= 1) crt_recompose_chunk_bytes = v;

@@ -2441,6 +2441,62 @@ class GpuDCRTPolyMatrix:
                                              lambda i_ptr: (w_stacked.raw, t_bottom.raw, part_start, secret_size, base, i_ptr))
 
     @staticmethod
+    def _commit_lut_call(entry: str, outs, count, pubkey_sums, a_outs, gate_of_row, ys, head, tail) -> list:
+        """`entry(outs, T, *head, P array, A_out array, ngates, gate array, base, y words, words, *tail(arrays kept alive))`;
+        `outs` None: T fresh d x m_b outputs, m_b = m_g + 2 d"""
+        pubkey_sums, a_outs, ys = list(pubkey_sums), list(a_outs), [int(y) for y in ys]
+        gate_of_row = [int(g) for g in gate_of_row]
+        assert len(pubkey_sums) == len(a_outs), "commit_lut_messages: one pubkey sum and one A_out per gate"
+        assert len(ys) == len(gate_of_row) == count, "commit_lut_messages: one y and one gate per row"
+        if outs is None:
+            first = a_outs[0]
+            outs = [GpuDCRTPolyMatrix(first.params, first.nrow, first.ncol + 2 * first.nrow, first.level, True) for _ in range(count)]
+        else:
+            outs = list(outs)
+            assert len(outs) == count, "commit_lut_messages: one output per row"
+        if count == 0:
+            return outs
+        y_arr, wpy = GpuDCRTPolyMatrix._int_rows(ys)
+        g_arr = np.array(gate_of_row, dtype=np.uint32)
+        for out in outs:
+            out._touch()
+        st = getattr(_ffi.lib(), entry)(GpuDCRTPolyMatrix._raw_array(outs), count, *head, GpuDCRTPolyMatrix._raw_array(pubkey_sums),
+                                        GpuDCRTPolyMatrix._raw_array(a_outs), len(a_outs), g_arr.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        a_outs[0].params.base_bits(), y_arr.ctypes.data_as(C.POINTER(C.c_uint64)), wpy, *tail)
+        check_status(st, entry)
+        for out in outs:
+            out.is_ntt = True
+        return outs
+
+    @staticmethod
+    def commit_lut_messages(b_1, verifier, vslots, pubkey_sums, a_outs, gate_of_row, ys, idxs, key: bytes, tags, hash_name: str = "keccak256",
+                            outs=None) -> list:
+        """The message blocks of len(ys) LUT rows of the commitment-based public lookup in one call
+        (gpupoly_matrix_commit_lut_messages), g = gate_of_row[t]:
+            [a_outs[g] - G_d o ys[t] | 0] + R_t - pubkey_sums[g] G^-1((b_1 V_t + R_t) o (idxs[t] + 1)^-1),
+        R_t the d x m_b uniform matrix under hash_seed_for_matrix(key, tags[t]), V_t the block vslots[t] of the
+        m_b x (nV m_b) EVAL matrix `verifier`; ys[t] non-negative integers of any size, idxs[t] below 2^64.  b_1 is d x m_b,
+        pubkey_sums[g] and a_outs[g] are d x m_g, EVAL, of one level.  Returns the rows' d x m_b matrices."""
+        vslots, idxs = [int(v) for v in vslots], [int(i) for i in idxs]
+        arg, keep, count = hash_tags_arg(key, tags, hash_name)
+        assert len(vslots) == len(idxs) == count, "commit_lut_messages: one verifier slot, one index and one tag per row"
+        u64p = C.POINTER(C.c_uint64)
+        v_arr, i_arr = np.array(vslots, dtype=np.uint64), np.array(idxs, dtype=np.uint64)
+        out = GpuDCRTPolyMatrix._commit_lut_call("gpupoly_matrix_commit_lut_messages", outs, count, pubkey_sums, a_outs, gate_of_row, ys,
+                                                 (b_1.raw, verifier.raw, v_arr.ctypes.data_as(u64p)), (i_arr.ctypes.data_as(u64p), C.byref(arg)))
+        del keep
+        return out
+
+    @staticmethod
+    def commit_lut_messages_combine(r_stacked, digits, pubkey_sums, a_outs, gate_of_row, ys, outs=None) -> list:
+        """Test instrument (gpupoly_matrix_commit_lut_messages_combine): `commit_lut_messages` with [R_0 | R_1 | ...] given
+        as the d x (len(ys) * m_b) EVAL matrix `r_stacked` and the digits of the cancelers as the m_g x (len(ys) * m_b) EVAL
+        matrix `digits`, instead of sampled, multiplied and decomposed."""
+        ys = list(ys)
+        return GpuDCRTPolyMatrix._commit_lut_call("gpupoly_matrix_commit_lut_messages_combine", outs, len(ys), pubkey_sums, a_outs,
+                                                  gate_of_row, ys, (r_stacked.raw, digits.raw), ())
+
+    @staticmethod
     def _ggh15_lookup_call(entry: str, mids, lut_preimages, xs, col_start, col_len, ys, last) -> list:
         """len(ys) fresh r x col_len outputs and `entry(outs, S, *mids, K array, x array, col_start, base, y words, words, last)`"""
         mids, lut_preimages, xs, ys = list(mids), list(lut_preimages), list(xs), [int(y) for y in ys]
